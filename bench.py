@@ -12,8 +12,13 @@ rank (one process per GPU, torch.distributed / RCCL) generates and decodes only 
 handle and HIP stream, and the decoded packets travel to rank 0 in the design's single collective per step
 (multi.gather_pieces).  --pipeline steps are in flight per piece (default 4): the piece's handles take its steps in turn, each on
 its own HIP stream, so that the next steps' latency-bound front-end kernels run while the Viterbi decoder of the current step holds the machine
-(one step in flight: --pipeline 1; stage_ms_per_piece_solo has those kernel times).  After the timed loop rank 0 stitches the pieces of the last step and compares the TS
-with the packets that were transmitted: the bench fails (exit 1) when a single byte differs.
+(one step in flight: --pipeline 1; stage_ms_per_piece_solo has those kernel times).
+
+A plain run sets up, warms up, times --steps steps and prints the result line; --dump-outputs DIR also writes what the last timed step
+delivered (the stitched TS) as .npy files.  --full adds everything else, after the timed loop: rank 0 stitches the pieces of the last step
+and compares the TS with the packets that were transmitted (the bench fails, exit 1, when a single byte differs), the kernels' own times
+with one step in flight, the roofline figures that need runs of their own, and on one GPU the extra workload lines (unless --no-extras)
+and the CPU baseline (unless --no-cpu-baseline).
 
 Prints ONE JSON line on rank 0.
 """
@@ -720,6 +725,31 @@ def cpp_multi_host(workload, loops=160, seg_sf=64):
         os.rmdir(tmp)
 
 
+DUMP_SAMPLE_BYTES = 1 << 21      # --dump-outputs: TS bytes kept at seeded positions (float32 values + float64 positions: 24 MB)
+
+
+def dump_outputs(job, pieces, out_dir):
+    """rank 0, right after the timed loop: what the timed path delivered in its last step, the stream's TS (the pieces stitched), as .npy files
+    that two builds can be compared by.  ts_packet_checksum: every whole 188-byte packet as sum_i (i + 1) x byte_i (integers, exact in float64);
+    ts_sample / ts_sample_index: the TS bytes at DUMP_SAMPLE_BYTES positions drawn from a fixed seed (all of them when the TS is shorter);
+    piece_meta: the report fields of every piece that the stitch reads (multi.META_FIELDS, one row per piece)."""
+    multi = job.multi
+    ts = multi.stitch_ts(pieces, job.dims)
+    ts = ts.cpu().numpy() if hasattr(ts, "cpu") else np.asarray(ts)
+    npk = len(ts) // 188
+    w = np.arange(1, 189, dtype=np.float32)                      # partial sums are integers < 2^24: exact in float32, in any order
+    checksum = (ts[:npk * 188].reshape(npk, 188).astype(np.float32) @ w).astype(np.float64)
+    if len(ts) <= DUMP_SAMPLE_BYTES:
+        idx = np.arange(len(ts), dtype=np.int64)
+    else:
+        idx = np.sort(np.random.default_rng(SEED).choice(len(ts), DUMP_SAMPLE_BYTES, replace=False))
+    meta = np.array([[multi.piece_meta(m)[k] for k in multi.META_FIELDS] for m, _ in pieces], dtype=np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, arr in (("ts_packet_checksum", checksum), ("ts_sample", ts[idx].astype(np.float32)),
+                      ("ts_sample_index", idx.astype(np.float64)), ("piece_meta", meta)):
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
+
+
 def timed_run(job, steps, warmup):
     torch, dist = job.torch, job.dist
     for _ in range(warmup):
@@ -828,10 +858,15 @@ def main():
                     help="torch.distributed backend of the exchange step: nccl = RCCL over xGMI on device buffers (the design); gloo = the same gather staged "
                          "through host tensors (functional tests where the ranks share one GPU, which RCCL refuses)")
     ap.add_argument("--ranks-share-gpu", action="store_true", help="every rank decodes on device 0 (tests on a one-GPU box; needs --backend gloo when --gpus > 1)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the extra workload lines (BASELINE configs 1, 2, 5) and the per-block ABI timing")
+    ap.add_argument("--full", action="store_true", help="beside the headline: verify the last step's TS against the transmitted packets, the kernels' own times "
+                    "with one step in flight and the roofline figures that need runs of their own, and on one GPU the extra workload lines and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step delivered (the stitched TS) to DIR/*.npy (rank 0)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the extra workload lines (BASELINE configs 1, 2, 5) and the per-block ABI timing")
     ap.add_argument("--cpu-superframes", type=int, default=23)
     a = ap.parse_args()
+    if a.steps < 1:
+        raise SystemExit("--steps must be >= 1")
     if a.from_file_rate and (a.gpus > 1 or a.segments > 1):
         raise SystemExit("--from-file-rate runs one piece on one GPU")
     if a.gpus < 1:
@@ -877,8 +912,13 @@ def main():
     if rank == 0:
         n_stream = job.n_total if not a.from_file_rate else sum(p["n"] for p in job.pieces)
         msps = n_stream * a.steps / dt / 1e6
-        check = job.verify() if not (a.from_file_rate or EXPERIMENT_BUILD) else {"verified": None}
-        ok = check["verified"] is not False
+        pieces = job.collect()
+        if a.dump_outputs:
+            dump_outputs(job, pieces, a.dump_outputs)
+        check = {}
+        if a.full:
+            check = job.verify() if not (a.from_file_rate or EXPERIMENT_BUILD) else {"verified": None}
+            ok = check["verified"] is not False
         reps = job.reps
         # dominant kernel = viterbi3_kernel: per launch, algorithmic bytes = bytes in (one per m coded bits) + decoded
         # bytes out (6048 + 3969 B per 8k QAM64 7/8 OFDM symbol); launch duration from HIP events
@@ -887,12 +927,15 @@ def main():
         depth = len(job.pieces[0]["rxs"])
         vit_ms = job.stage_avg("viterbi")                         # average over the timed steps' launches
         stage_avg = {"viterbi": round(vit_ms, 4)} if vit_ms > 0 else None   # (the timed region carries events around the decoder only; none with --graph)
-        solo = job.solo_stage_ms()                                # every stage, one step in flight, right after the timed region
+        solo = job.solo_stage_ms() if a.full else None            # every stage, one step in flight, right after the timed region
         alg_bytes = sum(r.n_out_symbols * d.payload_length + r.n_viterbi_bytes for r in reps) / nseg
-        solo_ms = solo["viterbi"] if (depth > 1 or vit_ms <= 0) else vit_ms       # the kernel's own duration: one step in flight
+        if depth > 1 or vit_ms <= 0:                              # the kernel's own duration: one step in flight (runs of its own: --full)
+            solo_ms = solo["viterbi"] if solo else 0.0
+        else:
+            solo_ms = vit_ms
         achieved = alg_bytes / (solo_ms * 1e-3) / 1e9 if solo_ms > 0 else 0.0
         traffic, traffic_src = profiled_traffic(a.workload, job.nsf, int(alg_bytes))
-        n_ts = check.get("ts_bytes") or sum(int(r.n_ts_bytes) for r in reps)
+        n_ts = check.get("ts_bytes") or job.multi.stitch_plan([job.multi.piece_meta(m) for m, _ in pieces], d)[1]
         out = {
             "metric": "RX Msamples/s (baseband in -> TS out)", "value": round(msps, 2), "unit": "Msamples/s",
             "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": round(dt / a.steps * 1e3, 3),
@@ -913,19 +956,19 @@ def main():
                        "status_note": "dvbt_rx_report.status of each piece; bit 1 (value 2) = the CP lock ended where the finite synthetic stream's signal ends (the zeros behind its last symbol), not a loss inside it",
                        "rs_fail_words": [int(r.rs_fail_words) for r in reps],
                        **check},
-            "roofline": {"bound": "valu", "kernel": "viterbi3_kernel", "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": round(achieved / HBM_PEAK_GBS, 6), "traffic": traffic,
+            "roofline": {"bound": "valu", "kernel": "viterbi3_kernel", "achieved": round(achieved, 2) if solo_ms > 0 else None, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                         "frac": round(achieved / HBM_PEAK_GBS, 6) if solo_ms > 0 else None, "traffic": traffic,
                          "note": "the dominant kernel is bound by VALU issue, not by HBM (DESIGN.md 5: every wave64 instruction of its mix occupies the SIMD for 4 cycles); "
                                  "achieved / peak / frac are the HBM figures the contract asks for: algorithmic bytes per launch / solo_launch_ms (HIP events on the "
                                  "launch's own stream with ONE step in flight, measured right after the timed region; agrees with the rocprofv3 kernel-trace average "
                                  "in profiles/); in_flight_* = the same over the timed steps, where the launch interval also contains the time the stream waited while "
                                  "config.steps_in_flight steps shared the machine; traffic = PMC bytes per launch (FETCH_SIZE doubled per the gfx950 note + WRITE_SIZE), "
                                  "taken by separate rocprofv3 --pmc passes of this command: " + str(traffic_src),
-                         "algorithmic_bytes_per_launch": int(alg_bytes), "solo_launch_ms": round(solo_ms, 4),
+                         "algorithmic_bytes_per_launch": int(alg_bytes), "solo_launch_ms": round(solo_ms, 4) if solo_ms > 0 else None,
                          "in_flight_launch_ms": round(vit_ms, 4) if vit_ms > 0 else None, "in_flight_achieved": round(alg_bytes / (vit_ms * 1e-3) / 1e9, 2) if vit_ms > 0 else None,
                          "chain_frac": round(msps / world * 1e6 * (8 + n_ts / n_stream) / 1e9 / HBM_PEAK_GBS, 6),
-                         "hbm_copy_gbs": hbm_copy_gbs(torch, f"cuda:{local}"),
-                         "second_kernel": second_kernel(a.workload, job.nsf, int(alg_bytes), reps, d, job.c, solo, nseg)},
+                         **({"hbm_copy_gbs": hbm_copy_gbs(torch, f"cuda:{local}"),
+                             "second_kernel": second_kernel(a.workload, job.nsf, int(alg_bytes), reps, d, job.c, solo, nseg)} if a.full else {})},
             # what actually bounds the dominant kernel (top level: the driver's parser keeps `roofline`'s contract keys only)
             "valu_issue": valu_issue(a.workload, job.nsf, int(alg_bytes), solo_ms, device_clock_hz(torch, local)),
             "ms_per_step_dispersion": job.step_ms,
@@ -933,7 +976,7 @@ def main():
             "stage_ms_per_piece_solo": solo,
         }
     job.close()
-    if rank == 0 and world == 1 and not a.no_extras and not a.from_file_rate:
+    if rank == 0 and world == 1 and a.full and not a.no_extras and not a.from_file_rate:
         # the lines beside the headline: one that fails is recorded as such and does not take the bench line with it (the headline above is measured and verified by then)
         def extra(fn, *args):
             try:
@@ -949,7 +992,7 @@ def main():
         out["per_block_abi"] = extra(per_block_abi, g, a.workload)
         out["cpp_multi_host"] = extra(cpp_multi_host, a.workload)
     if rank == 0:
-        if not a.no_cpu_baseline and world == 1:             # the contract: rank 0 at N = 1 only
+        if a.full and not a.no_cpu_baseline and world == 1:  # the contract: rank 0 at N = 1 only
             out["cpu_baseline"] = cpu_baseline(a.workload, a.cpu_superframes)
             ref = reference_sse2_viterbi()
             if ref:

@@ -31,6 +31,11 @@ def test_shared_gpu_needs_gloo():
     assert r.returncode != 0 and "gloo" in r.stderr
 
 
+def test_steps_must_be_positive():
+    r = _run(["--steps", "0"])
+    assert r.returncode != 0 and "--steps must be >= 1" in r.stderr and not r.stdout.strip()
+
+
 def test_valu_issue_figure_from_the_committed_pmc_passes():
     """roofline.valu_issue: pure arithmetic on profiles/r*_pmc_summary_*.json -- what the judge recomputed by hand in VERDICT r04 (0.92 of the issue slots)"""
     sys.path.insert(0, ROOT)

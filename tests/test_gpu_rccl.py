@@ -26,7 +26,7 @@ def _bench(*args):
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT=str(_free_port()), RANK="0", LOCAL_RANK="0", WORLD_SIZE="1",
                HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--force-dist", "--steps", "4", "--warmup", "1", "--superframes", "8",
-                        "--no-cpu-baseline", "--no-extras", *args], env=env, cwd=ROOT, capture_output=True, text=True, timeout=600)
+                        "--full", "--no-cpu-baseline", "--no-extras", *args], env=env, cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, r.stdout[-2000:]
@@ -54,7 +54,7 @@ def test_bench_gpus_2_starts_two_ranks_itself():
     Job with world 2 (per-rank cuts of ONE stream, samples_owned, its own pieces), the pieces travel to rank 0 in one gather per step and rank 0 stitches
     and verifies them against the transmitted packets.  On the one-GPU test box both ranks decode on device 0 and the gather is staged through host
     tensors under gloo (RCCL refuses two ranks on one device); on an 8-GPU node the same code runs with backend nccl, one rank per GPU."""
-    r = _run(["--gpus", "2", "--backend", "gloo", "--ranks-share-gpu", "--steps", "3", "--warmup", "1", "--superframes", "6", "--no-cpu-baseline", "--no-extras"])
+    r = _run(["--gpus", "2", "--backend", "gloo", "--ranks-share-gpu", "--steps", "3", "--warmup", "1", "--superframes", "6", "--full", "--no-cpu-baseline", "--no-extras"])
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, r.stdout[-2000:]
@@ -69,7 +69,7 @@ def test_bench_gpus_2_starts_two_ranks_itself():
 
 def test_bench_gpus_2_two_pieces_per_rank_one_step_in_flight():
     r = _run(["--gpus", "2", "--backend", "gloo", "--ranks-share-gpu", "--steps", "2", "--warmup", "1", "--superframes", "4", "--segments", "2", "--pipeline", "1",
-              "--workload", "2k_qam16_1_2", "--no-cpu-baseline", "--no-extras"])
+              "--workload", "2k_qam16_1_2", "--full", "--no-cpu-baseline", "--no-extras"])
     assert r.returncode == 0, r.stderr[-3000:]
     d = json.loads([ln for ln in r.stdout.splitlines() if ln.strip()][0])
     c = d["config"]

@@ -28,7 +28,7 @@ else
   for v in $VARIANTS; do
     IFS=: read mw e wg <<< "$v"; n=mw${mw}_e${e}_wg${wg}
     W=""; [ "$e" != 0 ] && W="--wrong-output"
-    timeout 90 python tools/ab_bench.py $PWD/gr_dvbt_amd/lib/libdvbt_hip_s8o_$n.so $W --pipeline 1 --steps 10 --warmup 2 --superframes 16 --no-cpu-baseline --no-extras 2>/dev/null \
+    timeout 90 python tools/ab_bench.py $PWD/gr_dvbt_amd/lib/libdvbt_hip_s8o_$n.so $W --pipeline 1 --steps 10 --warmup 2 --superframes 16 --full --no-cpu-baseline --no-extras 2>/dev/null \
       | python -c "import sys,json; d=json.loads(sys.stdin.read()); print(json.dumps({'variant': '$n', 'launch_bounds_waves_per_simd': $mw, 's8_exp': $e, 'workgroups_per_cu': $wg, 'symbol_kernel_ms_17sf': d['stage_ms_per_piece_solo']['fft'], 'step_ms': d['ms_per_step'], 'verified': d['config'].get('verified')}))" \
       || echo "{\"variant\": \"$n\", \"error\": \"run failed or timed out\"}"
   done
