@@ -388,6 +388,89 @@ class RxStream:
             pass
 
 
+TX_SCALE = 0.0022097087      # multiply_const behind the cyclic prefixer in apps/dvbt_tx_demo*.grc
+
+
+class TxParams(C.Structure):
+    _fields_ = [("constellation", C.c_int), ("hierarchy", C.c_int), ("code_rate", C.c_int), ("guard_interval", C.c_int),
+                ("transmission_mode", C.c_int), ("include_cell_id", C.c_int), ("cell_id", C.c_int), ("scale", C.c_float),
+                ("max_packets", C.c_size_t), ("first_packet", C.c_int64), ("keep_carriers", C.c_int), ("device", C.c_int)]
+
+
+def _tx_lib():
+    L = lib()
+    if not getattr(L, "_tx_typed", False):
+        L.dvbt_tx_create.argtypes = [C.POINTER(TxParams), C.POINTER(C.c_void_p)]
+        L.dvbt_tx_samples_for.restype = C.c_int64
+        L.dvbt_tx_samples_for.argtypes = [C.c_void_p, C.c_size_t]
+        L.dvbt_tx_run.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
+        L.dvbt_tx_run_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(C.c_size_t)]
+        L.dvbt_tx_read_carriers.restype = C.c_int64
+        L.dvbt_tx_read_carriers.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+        L.dvbt_tx_reset.argtypes = [C.c_void_p]
+        L.dvbt_tx_destroy.argtypes = [C.c_void_p]
+        L._tx_typed = True
+    return L
+
+
+class Tx:
+    """dvbt_tx_*: the modulator of apps/dvbt_tx_demo*.grc on the GPU.  One transport stream, delivered over any number of run() /
+    run_device() calls of any number of 188-byte packets; the concatenated outputs are those of one run over the whole stream."""
+
+    def __init__(self, constellation, code_rate, mode, guard=G1_32, hierarchy=NH, include_cell_id=0, cell_id=0, scale=TX_SCALE,
+                 max_packets=1 << 16, first_packet=0, keep_carriers=False, device=0):
+        self.L = _tx_lib()
+        self.p = TxParams(constellation, hierarchy, code_rate, guard, mode, include_cell_id, cell_id, scale, max_packets, first_packet,
+                          int(bool(keep_carriers)), device)
+        self.h = C.c_void_p()
+        _chk(self.L.dvbt_tx_create(C.byref(self.p), C.byref(self.h)))
+        self.dims = get_dims(constellation, code_rate, mode, guard, hierarchy)
+
+    def samples_for(self, npackets):
+        """samples the NEXT call with npackets packets will produce"""
+        return _chk(self.L.dvbt_tx_samples_for(self.h, npackets))
+
+    def run(self, ts):
+        """TS bytes (a whole number of 188-byte packets) -> complex64 baseband of the whole OFDM symbols they complete"""
+        ts = np.ascontiguousarray(np.frombuffer(ts, np.uint8) if isinstance(ts, (bytes, bytearray)) else ts, dtype=np.uint8).reshape(-1)
+        if len(ts) % 188:
+            raise ValueError("the TS must be a whole number of 188-byte packets")
+        npk = len(ts) // 188
+        out = np.zeros(max(self.samples_for(npk), 0), np.complex64)
+        n = C.c_size_t()
+        _chk(self.L.dvbt_tx_run(self.h, ts.ctypes.data_as(C.c_void_p), npk, out.ctypes.data_as(C.c_void_p), len(out), C.byref(n)))
+        return out[:n.value]
+
+    def run_device(self, ts_ptr, npackets, out_ptr, cap, stream=None):
+        """device pointers (ints): enqueues on `stream` (a hipStream_t as int, None: the default stream) and returns the sample count at once"""
+        n = C.c_size_t()
+        _chk(self.L.dvbt_tx_run_device(self.h, C.c_void_p(ts_ptr), npackets, C.c_void_p(out_ptr), cap, C.c_void_p(stream) if stream else None,
+                                       C.byref(n)))
+        return n.value
+
+    def carriers(self):
+        """keep_carriers: the last call's IFFT input, complex64[nsym, N] (carrier c at column zeros_on_left + c)"""
+        nbytes = _chk(self.L.dvbt_tx_read_carriers(self.h, None, 0))
+        out = np.zeros(nbytes // 8, np.complex64)
+        if nbytes:
+            _chk(self.L.dvbt_tx_read_carriers(self.h, out.ctypes.data_as(C.c_void_p), nbytes))
+        return out.reshape(-1, self.dims.fft_length)
+
+    def reset(self):
+        _chk(self.L.dvbt_tx_reset(self.h))
+
+    def close(self):
+        if self.h:
+            self.L.dvbt_tx_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 # ------------------------------------------------------------------ per-block C ABI (one triple per reference block)
 TAG_SYNC_START, TAG_SUPERFRAME_START, TAG_SYMBOL_INDEX = 1, 2, 3
 

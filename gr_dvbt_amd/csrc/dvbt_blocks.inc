@@ -105,15 +105,20 @@ extern "C" int dvbt_fft_create(const dvbt_fft_params *p, dvbt_fft **out)
   BLK_CREATE_PROLOGUE(dvbt_fft);
   h->p = *p;
   int N = p->fft_size;
-  if (!p->forward || !p->shift || N < 64 || N > 8192 || (N & (N - 1))) BLK_FAIL(DVBT_ERR_INVALID, "only forward, shifted, power-of-two sizes 64..8192 (the configuration of the RX flowgraphs)");
+  // forward: the RX flowgraphs' fft_vxx(forward, shift=True); forward = 0: the TX flowgraphs' fft_vxx(reverse, shift=True) (k_tx.hpp)
+  if (!p->shift || N < 64 || N > 8192 || (N & (N - 1))) BLK_FAIL(DVBT_ERR_INVALID, "only shifted, power-of-two sizes 64..8192 (the configuration of the RX and TX flowgraphs)");
   BLK_CHK(h->T.build_fft(N));
-  BLK_CHK(set_lds((const void *)fft_items_kernel, (size_t)(N + N / 32 + N / 128 + 129) * 8));
+  BLK_CHK(set_lds(p->forward ? (const void *)fft_items_kernel : (const void *)ifft_items_kernel, (size_t)(N + N / 32 + N / 128 + 129) * 8));
   *out = h; return DVBT_OK;
 }
 extern "C" int dvbt_fft_forecast(const dvbt_fft *, int n, int *req) { if (req) *req = n; return DVBT_OK; }
 static void fft_run(dvbt_fft *h, int n, const void *din, void *dout, hipStream_t s)
 {
   const size_t N = h->p.fft_size;
+  if (!h->p.forward) {
+    hipLaunchKernelGGL(ifft_items_kernel, dim3(n), dim3(FFT_THREADS), (N + N / 32 + N / 128 + 129) * 8, s, (const float2 *)din, (int)N, n, (const float2 *)h->T.tw, (float2 *)dout);
+    return;
+  }
   hipLaunchKernelGGL(fft_items_kernel, dim3(n), dim3(FFT_THREADS), (N + N / 32 + N / 128 + 129) * 8, s, (const float2 *)din, (int)N, n, (const float2 *)h->T.tw,
                      (const uint16_t *)h->T.perm, (float2 *)dout);
 }

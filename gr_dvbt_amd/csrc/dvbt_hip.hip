@@ -21,6 +21,7 @@
 #include "k_resample.hpp"
 #include "k_viterbi3.hpp"
 #include "k_soft4.hpp"
+#include "k_tx.hpp"
 
 using namespace dvbt;
 
@@ -1543,3 +1544,4 @@ extern "C" int dvbt_debug_peak_detect(const float *lam_host, const float *avg_ho
 #include "dvbt_stream.inc"
 #include "dvbt_rccl.inc"
 #include "dvbt_blocks.inc"
+#include "dvbt_tx.inc"

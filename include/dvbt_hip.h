@@ -108,7 +108,9 @@ void dvbt_ofdm_sym_acquisition_destroy(dvbt_ofdm_sym_acquisition *h);
 
 /* ------------------------------------------------------------------ A2 forward FFT (stock fft_vxx in the flowgraph)
  * replaces gr::fft::fft_vcc(fft_size, forward=True, rectangular, shift=True)
- * (apps/dvbt_rx_demo*.grc block fft_vxx_0). items of N cfloat in and out. */
+ * (apps/dvbt_rx_demo*.grc block fft_vxx_0). items of N cfloat in and out.
+ * forward = 0 (shift = 1): fft_vcc(fft_size, forward=False, shift=True) of apps/dvbt_tx_demo*.grc -- the input halves swapped, then
+ * out[t] = sum_k in'[k] e^{+2 pi i t k / N}, unnormalised.  shift = 0 is refused. */
 typedef struct { int fft_size; int forward; int shift; } dvbt_fft_params;
 typedef struct dvbt_fft dvbt_fft;
 int  dvbt_fft_create(const dvbt_fft_params *p, dvbt_fft **out);
@@ -624,6 +626,39 @@ const void *dvbt_rccl_step_device_buffer(const dvbt_rccl_comm *c);
 int  dvbt_rccl_comm_reserve(dvbt_rccl_comm *c, int root, int slot_packets, int flags);
 /* the two at once (blocking): one group and one synchronisation per step */
 int64_t dvbt_rx_stream_gather(dvbt_rx_stream *s, dvbt_rccl_comm *c, int root, int slot_packets, void *ts_host, size_t cap, dvbt_gather_chunk *chunks, int *all_done);
+
+/* ------------------------------------------------------------------ the modulator: transport stream -> OFDM baseband
+ * replaces the chain of apps/dvbt_tx_demo*.grc: energy_dispersal, reed_solomon_enc, convolutional_interleaver, inner_coder, bit_inner_interleaver,
+ * symbol_inner_interleaver(direction=1), dvbt_map, reference_signals, fft_vxx(forward=False, shift=True), the cyclic prefixer and multiply_const(scale).
+ * A handle modulates ONE transport stream delivered over any number of calls of any number of 188-byte packets.  Each call emits every whole OFDM symbol
+ * (N + cp cfloat samples, cyclic prefix first) that the packets received so far make possible; the outputs of all calls, concatenated, are the output of one
+ * modulator run over the whole stream: floor(P * 1632 / info_bits_per_symbol) symbols for P packets.  The handle carries the dispersal group phase, the byte
+ * interleaver's memory, the info bits that did not fill a symbol, the encoder's history and symbol_index / frame_index from call to call.  The encoder and the
+ * interleaver start from zero, symbol_index and frame_index from 0; first_packet sets only the phase of the 8-packet dispersal groups.  Hierarchical modes
+ * (hierarchy = ALPHA1/2/4) change the constellation's alpha and the TPS word; the bit interleaver is the non-hierarchical one (a single stream).
+ * DVBT_ERR_CAPACITY (npackets > max_packets, or cap_samples < the call's output) and DVBT_ERR_INVALID leave the stream's state unchanged.  One thread per handle;
+ * calls on different streams are ordered by the handle (an event).  There is no CPU path: without a GPU dvbt_tx_create returns DVBT_ERR_NO_DEVICE. */
+typedef struct {
+  int constellation, hierarchy, code_rate, guard_interval, transmission_mode, include_cell_id, cell_id;
+  float scale;            /* multiply_const behind the cyclic prefixer (apps/dvbt_tx_demo*.grc: 0.0022097087); must be > 0 */
+  size_t max_packets;     /* capacity of one call (at most 2^24) */
+  int64_t first_packet;   /* index of the first packet in the whole TS: sets only the phase of the 8-packet dispersal groups */
+  int keep_carriers;      /* 1: keep the last call's frequency-domain frames for dvbt_tx_read_carriers */
+  int device;
+} dvbt_tx_params;
+typedef struct dvbt_tx dvbt_tx;
+int     dvbt_tx_create(const dvbt_tx_params *p, dvbt_tx **out);
+int64_t dvbt_tx_samples_for(const dvbt_tx *h, size_t npackets);   /* samples the NEXT call with npackets will produce */
+/* host buffers: synchronous */
+int     dvbt_tx_run(dvbt_tx *h, const void *ts_host, size_t npackets, void *iq_host, size_t cap_samples, size_t *nsamples);
+/* device buffers (ts_device 4-byte aligned, iq_device 8-byte aligned): enqueues on `stream` (NULL: the default stream) and returns; *nsamples is known without
+ * waiting for the device */
+int     dvbt_tx_run_device(dvbt_tx *h, const void *ts_device, size_t npackets, void *iq_device, size_t cap_samples, void *stream, size_t *nsamples);
+/* keep_carriers: the last call's IFFT input, cfloat[nsym][N] in frequency order (carrier c at index zeros_on_left + c), unscaled; returns the bytes
+ * (dst_host NULL: the bytes it would copy); waits for the call */
+int64_t dvbt_tx_read_carriers(dvbt_tx *h, void *dst_host, size_t cap_bytes);
+int     dvbt_tx_reset(dvbt_tx *h);      /* back to the start of a stream */
+void    dvbt_tx_destroy(dvbt_tx *h);
 
 /* ------------------------------------------------------------------ test hooks (used by tests/ only)
  * the two peak detectors of the acquisition's trackers (lib/ofdm_sym_acquisition_impl.cc:72-146 restated sample by sample, and the wavefront-wide form the
