@@ -502,7 +502,17 @@ BLOCK_PARAMS = {
     "reed_solomon_dec": _params([(n, _I) for n in ("p", "m", "gfpoly", "n", "k", "t", "s", "blocks", "oracle_compat")]),
     "energy_descramble": _params([("nblocks", _I)]),
     "resampler": _params([("interpolation", _I), ("decimation", _I), ("scale", C.c_float)]),
+    # the transmit blocks (dvbt_txblocks.inc)
+    "energy_dispersal": _params([("nblocks", _I)]),
+    "reed_solomon_enc": _params([(n, _I) for n in ("p", "m", "gfpoly", "n", "k", "t", "s", "blocks")]),
+    "convolutional_interleaver": _params([("blocks", _I), ("I", _I), ("M", _I)]),
+    "inner_coder": _params([(n, _I) for n in ("ninput", "noutput", "constellation", "hierarchy", "code_rate")]),
+    "bit_inner_interleaver": _params([("nsize", _I), ("constellation", _I), ("hierarchy", _I), ("transmission_mode", _I)]),
+    "map": _params([("nsize", _I), ("constellation", _I), ("hierarchy", _I), ("transmission_mode", _I), ("gain", C.c_float)]),
+    "reference_signals": _params([(n, _I) for n in ("itemsize", "ninput", "noutput", "constellation", "hierarchy", "code_rate_hp",
+                                                    "code_rate_lp", "guard_interval", "transmission_mode", "include_cell_id", "cell_id")]),
 }
+TX_BLOCKS = ("energy_dispersal", "reed_solomon_enc", "convolutional_interleaver", "inner_coder", "bit_inner_interleaver", "map", "reference_signals")
 
 
 class Block:

@@ -22,6 +22,7 @@
 #include "k_viterbi3.hpp"
 #include "k_soft4.hpp"
 #include "k_tx.hpp"
+#include "k_txblocks.hpp"
 
 using namespace dvbt;
 
@@ -1545,3 +1546,4 @@ extern "C" int dvbt_debug_peak_detect(const float *lam_host, const float *avg_ho
 #include "dvbt_rccl.inc"
 #include "dvbt_blocks.inc"
 #include "dvbt_tx.inc"
+#include "dvbt_txblocks.inc"

@@ -9,8 +9,8 @@
 
 namespace {
 
-// TPS word of frame f: reference_signals_impl.cc:883-916 (format_tps_data), BCH(67,53) parity :352-382 (generate_bch_code)
-inline void tx_tps_word(const Dims &d, int include_cell_id, int cell_id, int frame_index, int w0, uint8_t *t)
+// TPS word of frame f (code rate HP = d.code_rate): reference_signals_impl.cc:883-916 (format_tps_data), BCH(67,53) parity :352-382 (generate_bch_code)
+inline void tx_tps_word(const Dims &d, int code_rate_lp, int include_cell_id, int cell_id, int frame_index, int w0, uint8_t *t)
 {
   auto set_bits = [&](int start, int stop, unsigned data) { for (int i = start; i >= stop; i--) { t[i] = data & 1; data >>= 1; } };
   memset(t, 0, 68);
@@ -21,7 +21,7 @@ inline void tx_tps_word(const Dims &d, int include_cell_id, int cell_id, int fra
   set_bits(26, 25, (unsigned)d.constellation);
   set_bits(29, 27, (unsigned)d.hierarchy);
   set_bits(32, 30, (unsigned)d.code_rate);
-  set_bits(35, 33, (unsigned)d.code_rate);
+  set_bits(35, 33, (unsigned)code_rate_lp);
   set_bits(37, 36, (unsigned)d.guard);
   set_bits(39, 38, (unsigned)d.mode);
   set_bits(47, 40, (unsigned)cell_id);
@@ -60,6 +60,32 @@ inline int tx_carrier_classes(const Dims &d, TxClasses &out)
     out.npil[cls] = np;
   }
   return DVBT_OK;
+}
+
+// TPS carriers, their base values 2 (0.5 - w_k) (w_k from the sign of the pilot reference) and the sign of symbol s in frame f: DBPSK over
+// the bits 1..s of the frame's TPS word (format_tps_data is re-run every symbol; the word changes only with frame_index)
+struct TxTps { std::vector<uint16_t> car; std::vector<float> base, sign; };
+inline void tx_tps_tables(const Dims &d, int code_rate_lp, int include_cell_id, int cell_id, const std::vector<float> &pref, TxTps &out)
+{
+  const std::vector<int> tpsc = tps_table(d);
+  out.car.assign(tpsc.begin(), tpsc.end());
+  out.base.resize(tpsc.size()); out.sign.resize(4 * 68);
+  for (size_t i = 0; i < tpsc.size(); i++) out.base[i] = (float)(2 * (0.5 - (pref[tpsc[i]] < 0.f ? 1 : 0)));
+  const int w0 = pref[0] < 0.f ? 1 : 0;
+  for (int f = 0; f < 4; f++) {
+    uint8_t t[68];
+    tx_tps_word(d, code_rate_lp, include_cell_id, cell_id, f, w0, t);
+    float sg = 1.f;
+    for (int s = 0; s < 68; s++) { if (s > 0 && t[s]) sg = -sg; out.sign[f * 68 + s] = sg; }
+  }
+}
+
+// the RS encoder's feedback rows enc[fb][i] = fb g_(15 - i): row fb is XORed into the 16-byte remainder register, reg[0] first
+inline std::vector<uint8_t> rs_encoder_rows()
+{
+  std::vector<uint8_t> div = rs_division_table(), enc(256 * 16);
+  for (int b = 0; b < 256; b++) for (int i = 0; i < 16; i++) enc[b * 16 + i] = div[b * 16 + 15 - i];
+  return enc;
 }
 
 template <class T> static int tx_upload(const std::vector<T> &v, T *&dptr) { return upload(v, &dptr); }
@@ -132,11 +158,9 @@ extern "C" int dvbt_tx_create(const dvbt_tx_params *p, dvbt_tx **out)
   TXCHK(h->T.build_fft(d.N));
   TXCHK(h->T.build_inner(1.0f));
 
-  // outer coder tables: the PRBS of one dispersal group and the RS encoder's feedback rows enc[fb][i] = fb g_(15 - i)
-  std::vector<uint8_t> div = rs_division_table(), enc(256 * 16);
-  for (int b = 0; b < 256; b++) for (int i = 0; i < 16; i++) enc[b * 16 + i] = div[b * 16 + 15 - i];
+  // outer coder tables: the PRBS of one dispersal group and the RS encoder's feedback rows
   TXCHK(tx_upload(energy_prbs(), h->prbs));
-  TXCHK(tx_upload(enc, h->enc_tab));
+  TXCHK(tx_upload(rs_encoder_rows(), h->enc_tab));
 
   // carriers, pilot values, TPS
   TxClasses cl;
@@ -144,23 +168,15 @@ extern "C" int dvbt_tx_create(const dvbt_tx_params *p, dvbt_tx **out)
   TXCHK(tx_upload(cl.pay, h->pay)); TXCHK(tx_upload(cl.pil, h->pil));
   const std::vector<float> pref = pilot_ref_table(d);
   TXCHK(tx_upload(pref, h->pref));
-  const std::vector<int> tpsc = tps_table(d);
-  std::vector<uint16_t> t16(tpsc.begin(), tpsc.end());
-  std::vector<float> tb(tpsc.size()), tsg(4 * 68);
-  for (size_t i = 0; i < tpsc.size(); i++) tb[i] = (float)(2 * (0.5 - (pref[tpsc[i]] < 0.f ? 1 : 0)));      // w_k from the sign of the pilot reference
-  const int w0 = pref[0] < 0.f ? 1 : 0;
-  for (int f = 0; f < 4; f++) {                          // sign of symbol s in frame f: DBPSK over the bits 1..s of the frame's TPS word
-    uint8_t t[68];
-    tx_tps_word(d, p->include_cell_id, p->cell_id, f, w0, t);
-    float sg = 1.f;
-    for (int s = 0; s < 68; s++) { if (s > 0 && t[s]) sg = -sg; tsg[f * 68 + s] = sg; }
-  }
-  TXCHK(tx_upload(t16, h->tps)); TXCHK(tx_upload(tb, h->tps_base)); TXCHK(tx_upload(tsg, h->tps_sign));
+  TxTps tp;
+  tx_tps_tables(d, d.code_rate, p->include_cell_id, p->cell_id, pref, tp);
+  const std::vector<uint16_t> &t16 = tp.car;
+  TXCHK(tx_upload(tp.car, h->tps)); TXCHK(tx_upload(tp.base, h->tps_base)); TXCHK(tx_upload(tp.sign, h->tps_sign));
 
   // symbol kernel parameters
   TxSymParams &sp = h->sp;
   memset(&sp, 0, sizeof sp);
-  sp.N = d.N; sp.cp = d.cp; sp.payload = d.payload; sp.m = d.m; sp.k = d.k; sp.n = d.n; sp.zl = d.zl; sp.K = d.K; sp.n_tps = (int)tpsc.size();
+  sp.N = d.N; sp.cp = d.cp; sp.payload = d.payload; sp.m = d.m; sp.k = d.k; sp.n = d.n; sp.zl = d.zl; sp.K = d.K; sp.n_tps = (int)t16.size();
   sp.ibits = d.info_bits_per_symbol; sp.scale = p->scale;
   for (int c = 0; c < TX_NCLASS; c++) sp.npil[c] = cl.npil[c];
   for (int j = 0, o = 0; j < d.k; j++) {                 // inner_coder_impl.cc:225-254: x then y of every info bit, kept where the puncture vector says 1

@@ -248,3 +248,122 @@ class RxFlowgraph:
         self.registered = []
         for st in self.stages:
             st.blk.close()
+
+
+class TxFlowgraph:
+    """The modulator of apps/dvbt_tx_demo*.grc driven block by block through the per-block C ABI: energy_dispersal -> reed_solomon_enc ->
+    convolutional_interleaver -> inner_coder -> bit_inner_interleaver -> symbol_inner_interleaver(1) -> dvbt_map -> reference_signals -> fft(N, 0, 1),
+    then the stock blocks behind them here, in torch / numpy: the cyclic prefixer and multiply_const.  vector_to_stream is the byte view of the buffers.
+
+    Parameters of the demo flowgraphs: energy_dispersal nblocks, reed_solomon_enc blocks and convolutional_interleaver blocks are 4, 32, 544 in 8k and
+    1, 8, 136 in 2k; dvbt_map gain 1.  Every call offers a block min(available, forecast(noutput_items)) input items, as RxFlowgraph does; call_items
+    (an int, or a numpy Generator for random sizes) sets noutput_items in units of each block's output multiple.  mode "host" / "device" as RxFlowgraph."""
+
+    def __init__(self, constellation, code_rate, mode_t, guard=0, mode="device", call_items=4, scale=None, include_cell_id=0, cell_id=0):
+        self.mode = mode
+        self.torch = None
+        if mode == "device":
+            import torch
+            self.torch = torch
+            self.stream = torch.cuda.Stream()
+        d = self.dims = b.get_dims(constellation, code_rate, mode_t, guard)
+        self.scale = b.TX_SCALE if scale is None else scale
+        self.call_items = call_items
+        N, P = d.fft_length, d.payload_length
+        nb = 4 if mode_t == b.T8k else 1
+        self.nb = nb
+        mk = b.Block
+        self.blocks = [
+            mk("energy_dispersal", nb),
+            mk("reed_solomon_enc", 2, 8, 0x11d, 255, 239, 8, 51, 8 * nb),
+            mk("convolutional_interleaver", 136 * nb, 12, 17),
+            mk("inner_coder", 1, P, constellation, b.NH, code_rate),
+            mk("bit_inner_interleaver", P, constellation, b.NH, mode_t),
+            mk("symbol_inner_interleaver", P, mode_t, 1),
+            mk("map", P, constellation, b.NH, mode_t, 1.0),
+            mk("reference_signals", 8, P, N, constellation, b.NH, code_rate, code_rate, guard, mode_t, include_cell_id, cell_id),
+            mk("fft", N, 0, 1),
+        ]
+        self.in_item = [1, 1504 * nb, 1632 * nb, 1, P, P, P, 8 * P, 8 * N]
+        self.out_item = [1504 * nb, 1632 * nb, 1, P, P, P, 8 * P, 8 * N, 8 * N]
+        self.out_mult = [1, 1, 1632 * nb, 4, 1, 1, 1, 1, 1]           # convolutional_interleaver: a sync_interpolator; inner_coder: set_output_multiple(4)
+
+    def _alloc(self, nbytes):
+        if self.mode == "device":
+            return self.torch.empty(nbytes + 64, dtype=self.torch.uint8, device="cuda")
+        return np.empty(nbytes + 64, dtype=np.uint8)
+
+    def _per_call(self, k):
+        c = self.call_items
+        n = int(c.integers(1, 9)) if isinstance(c, np.random.Generator) else int(c)
+        return n * self.out_mult[k]
+
+    def _step(self, k):
+        blk, st = self.blocks[k], self.st[k]
+        avail = st["w"] - st["r"]
+        nout = min(self._per_call(k), st["cap"] - st["produced"])
+        nout -= nout % self.out_mult[k]
+        if nout <= 0 or avail <= 0:
+            return False
+        nin = min(avail, blk.forecast(nout))
+        if nin <= 0:
+            return False
+        src = self.src if k == 0 else self.st[k - 1]["out"]
+        in_off, out_off = st["r"] * self.in_item[k], st["produced"] * self.out_item[k]
+        if self.mode == "device":
+            produced, consumed, _ = blk.work_device(nout, nin, src.data_ptr() + in_off, st["out"].data_ptr() + out_off, (), self.stream.cuda_stream)
+        else:
+            produced, consumed, _ = blk.work(nout, nin, src[in_off:], st["out"][out_off:])
+        st["calls"] += 1
+        if produced == 0 and consumed == 0:
+            return False
+        st["r"] += consumed
+        st["produced"] += produced
+        if k + 1 < len(self.blocks):
+            self.st[k + 1]["w"] = st["produced"]
+        return True
+
+    def run(self, ts, to_host=True):
+        """ts: bytes / uint8 array of 188-byte packets.  Returns (baseband complex64, the IFFT input complex64[nsym, N]) of the symbols the chain
+        produced; one flowgraph run per TxFlowgraph (the blocks keep their stream state).  to_host=False (device mode): the two as torch tensors on
+        the device, not waited for."""
+        d = self.dims
+        N, cp, P = d.fft_length, d.cp_length, d.payload_length
+        ts = np.ascontiguousarray(np.frombuffer(bytes(ts), np.uint8) if isinstance(ts, (bytes, bytearray)) else ts, dtype=np.uint8).reshape(-1)
+        items = len(ts) // (1504 * self.nb) + 1
+        coded = items * 1632 * self.nb
+        nsym = coded * 8 * d.cr_n // (d.cr_k * d.m) // P + 8
+        caps = [items, items, coded, nsym, nsym, nsym, nsym, nsym, nsym]
+        self.st = [{"r": 0, "w": 0, "produced": 0, "calls": 0, "cap": caps[k], "out": self._alloc(caps[k] * self.out_item[k])} for k in range(9)]
+        if self.mode == "device":
+            self.src = self.torch.from_numpy(ts.copy()).cuda()
+            self.stream.wait_stream(self.torch.cuda.current_stream())
+        else:
+            self.src = ts
+        self.st[0]["w"] = len(ts)
+        progress = True
+        while progress:
+            progress = False
+            for k in range(len(self.blocks)):
+                while self._step(k):
+                    progress = True
+        n = self.st[8]["produced"]
+        car, td = self.st[7]["out"], self.st[8]["out"]
+        if self.mode == "device":
+            torch = self.torch
+            with torch.cuda.stream(self.stream):
+                t = td[:n * 8 * N].view(torch.complex64).view(n, N)
+                bb = (torch.cat([t[:, N - cp:], t], dim=1) * self.scale).reshape(-1)         # cyclic prefixer + multiply_const
+                cv = car[:n * 8 * N].view(torch.complex64).view(n, N)
+                if not to_host:
+                    return bb, cv
+                out = bb.cpu().numpy(), cv.cpu().numpy()
+            self.stream.synchronize()
+            return out
+        t = td[:n * 8 * N].view(np.complex64).reshape(n, N)
+        bb = (np.concatenate([t[:, N - cp:], t], axis=1) * np.complex64(self.scale)).reshape(-1)
+        return bb, car[:n * 8 * N].view(np.complex64).reshape(n, N).copy()
+
+    def close(self):
+        for blk in self.blocks:
+            blk.close()

@@ -128,6 +128,35 @@ DVBT_AMD_BLOCK(energy_descramble, dvbt_energy_descramble_params, (int nblocks), 
 // (rational_resampler_xxx_0 + blocks_multiply_const_vxx_0 of apps/dvbt_rx_demo*.grc), one block here
 DVBT_AMD_BLOCK(resampler, dvbt_resampler_params, (int interpolation, int decimation, float scale), (dvbt_resampler_params{interpolation, decimation, scale}))
 
+// ---- the transmit blocks (include/dvbt_hip.h T1-T7)
+// include/dvbt/energy_dispersal.h
+DVBT_AMD_BLOCK(energy_dispersal, dvbt_energy_dispersal_params, (int nsize), (dvbt_energy_dispersal_params{nsize}))
+// include/dvbt/reed_solomon_enc.h
+DVBT_AMD_BLOCK(reed_solomon_enc, dvbt_reed_solomon_enc_params, (int p, int m, int gfpoly, int n, int k, int t, int s, int blocks),
+               (dvbt_reed_solomon_enc_params{p, m, gfpoly, n, k, t, s, blocks}))
+// include/dvbt/convolutional_interleaver.h (a sync_interpolator: general_work returns bytes, n_consumed items of I*blocks bytes)
+DVBT_AMD_BLOCK(convolutional_interleaver, dvbt_convolutional_interleaver_params, (int nsize, int I, int M),
+               (dvbt_convolutional_interleaver_params{nsize, I, M}))
+// include/dvbt/inner_coder.h
+DVBT_AMD_BLOCK(inner_coder, dvbt_inner_coder_params,
+               (int ninput, int noutput, dvbt_constellation_t constellation, dvbt_hierarchy_t hierarchy, dvbt_code_rate_t coderate),
+               (dvbt_inner_coder_params{ninput, noutput, constellation, hierarchy, coderate}))
+// include/dvbt/bit_inner_interleaver.h (hierarchy NH only)
+DVBT_AMD_BLOCK(bit_inner_interleaver, dvbt_bit_inner_interleaver_params,
+               (int nsize, dvbt_constellation_t constellation, dvbt_hierarchy_t hierarchy, dvbt_transmission_mode_t transmission),
+               (dvbt_bit_inner_interleaver_params{nsize, constellation, hierarchy, transmission}))
+// include/dvbt/dvbt_map.h
+DVBT_AMD_BLOCK(map, dvbt_map_params, (int nsize, dvbt_constellation_t constellation, dvbt_hierarchy_t hierarchy, dvbt_transmission_mode_t transmission, float gain),
+               (dvbt_map_params{nsize, constellation, hierarchy, transmission, gain}))
+typedef map dvbt_map;   // reference class name
+// include/dvbt/reference_signals.h
+DVBT_AMD_BLOCK(reference_signals, dvbt_reference_signals_params,
+               (int itemsize, int ninput, int noutput, dvbt_constellation_t constellation, dvbt_hierarchy_t hierarchy, dvbt_code_rate_t code_rate_HP,
+                dvbt_code_rate_t code_rate_LP, dvbt_guard_interval_t guard_interval, dvbt_transmission_mode_t transmission_mode,
+                int include_cell_id, int cell_id),
+               (dvbt_reference_signals_params{itemsize, ninput, noutput, constellation, hierarchy, code_rate_HP, code_rate_LP, guard_interval,
+                                              transmission_mode, include_cell_id, cell_id}))
+
 #undef DVBT_AMD_BLOCK
 
 // gr::dvbt::rx_hip (gr_dvbt_amd/host/gr/include/dvbt/rx_hip.h): the ten receive blocks of apps/dvbt_rx_demo*.grc behind one block, over the

@@ -277,6 +277,122 @@ int  dvbt_resampler_work_device(dvbt_resampler *h, int noutput_items, int ninput
 int  dvbt_resampler_get_taps(const dvbt_resampler *h, float *taps, int cap, int *interpolation, int *decimation);  /* returns the tap count */
 void dvbt_resampler_destroy(dvbt_resampler *h);
 
+/* ================================================================== the transmit blocks, one at a time
+ * The blocks of apps/dvbt_tx_demo*.grc and of the per-block apps (energy_dispersal.grc, rs_encode.grc, dvbt_map.grc, symbol_inner_interleaver.grc,
+ * dvbt_tx.grc), each with the create / forecast / work / work_device / destroy of the receive blocks.  With symbol_inner_interleaver(direction = 1) and
+ * fft(forward = 0) above, every HIP block of the TX chain has an entry; vector_to_stream, the cyclic prefixer and multiply_const are stock GNU Radio.
+ * The stateful blocks (convolutional_interleaver, inner_coder, reference_signals) keep their state in the handle; a refused call (DVBT_ERR_INVALID)
+ * leaves it as it was, and the next good call continues the stream.  Byte outputs of the device entries must be 4-byte aligned, cfloat outputs
+ * 16-byte aligned (vector stores); byte inputs may sit anywhere.  Only energy_dispersal synchronises in work_device: it reads its SYNC window back. */
+
+/* ------------------------------------------------------------------ T1 energy_dispersal
+ * replaces energy_dispersal::make(nblocks) (include/dvbt/energy_dispersal.h); forecast and general_work lib/energy_dispersal_impl.cc:86-141.
+ * u8 stream -> items of nblocks*8*188 bytes.  forecast: 8*189*nblocks*noutput_items bytes (one spare byte per packet for the SYNC search).
+ * Every call searches its first 188 bytes for 0x47: none there -> 0 items, n_consumed = 188; found at `index` -> the items behind it,
+ * n_consumed = index + nblocks*1504*items.  The PRBS restarts with every group of 8 packets; sync bytes are written as 0xB8 (first packet of a
+ * group) and 0x47 (the others) whatever the input holds (the reference only prints "Malformed MPEG-TS").  Defined here, not reproduced: a call
+ * that sees fewer bytes than its output needs produces what fits (the reference reads past its window); with fewer than 188 bytes and no sync
+ * it consumes nothing, with a sync but not one item behind it it consumes the bytes in front of the sync.
+ * work_device copies the 188-byte window back to the host and synchronises `stream` once per call before it enqueues (the search decides what
+ * is consumed), like energy_descramble. */
+typedef struct { int nblocks; } dvbt_energy_dispersal_params;
+typedef struct dvbt_energy_dispersal dvbt_energy_dispersal;
+int  dvbt_energy_dispersal_create(const dvbt_energy_dispersal_params *p, dvbt_energy_dispersal **out);
+int  dvbt_energy_dispersal_forecast(const dvbt_energy_dispersal *h, int noutput_items, int *ninput_required);
+int  dvbt_energy_dispersal_work(dvbt_energy_dispersal *h, int noutput_items, int ninput_items, const void *in, void *out, dvbt_sideband *sb);
+int  dvbt_energy_dispersal_work_device(dvbt_energy_dispersal *h, int noutput_items, int ninput_items, const void *in_device, void *out_device,
+                                       dvbt_sideband *sb, void *stream);
+void dvbt_energy_dispersal_destroy(dvbt_energy_dispersal *h);
+
+/* ------------------------------------------------------------------ T2 reed_solomon_enc
+ * replaces reed_solomon_enc::make(p, m, gfpoly, n, k, t, s, blocks) (include/dvbt/reed_solomon_enc.h); general_work
+ * lib/reed_solomon_enc_impl.cc:66-99 and reed_solomon::rs_encode lib/reed_solomon.cc:216-244.  items of blocks*(k-s) -> blocks*(n-s) bytes.
+ * Only the DVB parameter set (2,8,0x11d,255,239,8,51) is accepted, as by reed_solomon_dec.  Input and output 4-byte aligned (device). */
+typedef struct { int p, m, gfpoly, n, k, t, s, blocks; } dvbt_reed_solomon_enc_params;
+typedef struct dvbt_reed_solomon_enc dvbt_reed_solomon_enc;
+int  dvbt_reed_solomon_enc_create(const dvbt_reed_solomon_enc_params *p, dvbt_reed_solomon_enc **out);
+int  dvbt_reed_solomon_enc_forecast(const dvbt_reed_solomon_enc *h, int noutput_items, int *ninput_required);
+int  dvbt_reed_solomon_enc_work(dvbt_reed_solomon_enc *h, int noutput_items, int ninput_items, const void *in, void *out, dvbt_sideband *sb);
+int  dvbt_reed_solomon_enc_work_device(dvbt_reed_solomon_enc *h, int noutput_items, int ninput_items, const void *in_device, void *out_device,
+                                       dvbt_sideband *sb, void *stream);
+void dvbt_reed_solomon_enc_destroy(dvbt_reed_solomon_enc *h);
+
+/* ------------------------------------------------------------------ T3 convolutional_interleaver
+ * replaces convolutional_interleaver::make(nsize(blocks), I, M) (include/dvbt/convolutional_interleaver.h); work
+ * lib/convolutional_interleaver_impl.cc:73-82.  A sync_interpolator: items of I*blocks bytes -> u8 stream.  noutput_items must be a multiple of
+ * I*blocks (else DVBT_ERR_INVALID); returns bytes, n_consumed = items.  out[t] = x[t - I*M*(t mod I)] over the whole stream, x[< 0] = 0: branch j
+ * is the reference's FIFO of M*j bytes, initially zero.  The handle keeps the last (I-1)*M*I input bytes on the device.  Any I >= 1, M >= 0 with
+ * I*blocks a multiple of 4. */
+typedef struct { int blocks, I, M; } dvbt_convolutional_interleaver_params;
+typedef struct dvbt_convolutional_interleaver dvbt_convolutional_interleaver;
+int  dvbt_convolutional_interleaver_create(const dvbt_convolutional_interleaver_params *p, dvbt_convolutional_interleaver **out);
+int  dvbt_convolutional_interleaver_forecast(const dvbt_convolutional_interleaver *h, int noutput_items, int *ninput_required);
+int  dvbt_convolutional_interleaver_work(dvbt_convolutional_interleaver *h, int noutput_items, int ninput_items, const void *in, void *out, dvbt_sideband *sb);
+int  dvbt_convolutional_interleaver_work_device(dvbt_convolutional_interleaver *h, int noutput_items, int ninput_items, const void *in_device, void *out_device,
+                                                dvbt_sideband *sb, void *stream);
+void dvbt_convolutional_interleaver_destroy(dvbt_convolutional_interleaver *h);
+
+/* ------------------------------------------------------------------ T4 inner_coder
+ * replaces inner_coder::make(ninput, noutput, constellation, hierarchy, code_rate) (include/dvbt/inner_coder.h); the mother code and puncturing
+ * lib/inner_coder_impl.cc:33-121, forecast and general_work :206-266.  u8 stream -> items of noutput bytes, one m-bit symbol per byte (MSB first).
+ * forecast = n_consumed = noutput_items*noutput*k*m/(ninput*8*n) bytes.  noutput_items must be a multiple of 4 (set_output_multiple(4), :172;
+ * else DVBT_ERR_INVALID); a call with fewer input bytes produces the largest multiple of 4 items they cover.  noutput % 1512 != 0 is refused (the
+ * reference asserts it).  Defined here: ninput must be 1 -- the reference's input items are bytes whatever ninput is (:138) while its consume_each
+ * divides by ninput.  hierarchy only selects m's table row; the code rate is code_rate (HP).  The encoder's register (the last 6 info bits) is
+ * carried on the device from call to call, starting at zero. */
+typedef struct { int ninput, noutput, constellation, hierarchy, code_rate; } dvbt_inner_coder_params;
+typedef struct dvbt_inner_coder dvbt_inner_coder;
+int  dvbt_inner_coder_create(const dvbt_inner_coder_params *p, dvbt_inner_coder **out);
+int  dvbt_inner_coder_forecast(const dvbt_inner_coder *h, int noutput_items, int *ninput_required);
+int  dvbt_inner_coder_work(dvbt_inner_coder *h, int noutput_items, int ninput_items, const void *in, void *out, dvbt_sideband *sb);
+int  dvbt_inner_coder_work_device(dvbt_inner_coder *h, int noutput_items, int ninput_items, const void *in_device, void *out_device,
+                                  dvbt_sideband *sb, void *stream);
+void dvbt_inner_coder_destroy(dvbt_inner_coder *h);
+
+/* ------------------------------------------------------------------ T5 bit_inner_interleaver
+ * replaces bit_inner_interleaver::make(nsize, constellation, hierarchy, transmission) (include/dvbt/bit_inner_interleaver.h); the
+ * non-hierarchical branch of general_work lib/bit_inner_interleaver_impl.cc:120-184.  items of nsize bytes (m bits each) -> nsize bytes.
+ * nsize must be a multiple of 252 (whole 126-word blocks, 4-byte output words; the payloads 1512 and 6048 are).  hierarchy != NH is refused
+ * with DVBT_ERR_INVALID: the reference's hierarchical branch writes d_b[k][v*i/2] beyond its d_b[v][126] matrix, and for 16-QAM writes no
+ * low-priority bit at all -- undefined behaviour, not reproducible. */
+typedef struct { int nsize, constellation, hierarchy, transmission_mode; } dvbt_bit_inner_interleaver_params;
+typedef struct dvbt_bit_inner_interleaver dvbt_bit_inner_interleaver;
+int  dvbt_bit_inner_interleaver_create(const dvbt_bit_inner_interleaver_params *p, dvbt_bit_inner_interleaver **out);
+int  dvbt_bit_inner_interleaver_forecast(const dvbt_bit_inner_interleaver *h, int noutput_items, int *ninput_required);
+int  dvbt_bit_inner_interleaver_work(dvbt_bit_inner_interleaver *h, int noutput_items, int ninput_items, const void *in, void *out, dvbt_sideband *sb);
+int  dvbt_bit_inner_interleaver_work_device(dvbt_bit_inner_interleaver *h, int noutput_items, int ninput_items, const void *in_device, void *out_device,
+                                            dvbt_sideband *sb, void *stream);
+void dvbt_bit_inner_interleaver_destroy(dvbt_bit_inner_interleaver *h);
+
+/* ------------------------------------------------------------------ T6 dvbt_map
+ * replaces dvbt_map::make(nsize, constellation, hierarchy, transmission, gain) (include/dvbt/dvbt_map.h); lib/dvbt_map_impl.cc:44-171.
+ * items of nsize labels -> nsize cfloat: make_constellation_points scaled by gain * norm, with the hierarchy's alpha (ALPHA1/2/4 accepted).
+ * nsize must be even (two points per 16-byte store); labels are taken modulo 64. */
+typedef struct { int nsize, constellation, hierarchy, transmission_mode; float gain; } dvbt_map_params;
+typedef struct dvbt_map dvbt_map;
+int  dvbt_map_create(const dvbt_map_params *p, dvbt_map **out);
+int  dvbt_map_forecast(const dvbt_map *h, int noutput_items, int *ninput_required);
+int  dvbt_map_work(dvbt_map *h, int noutput_items, int ninput_items, const void *in, void *out, dvbt_sideband *sb);
+int  dvbt_map_work_device(dvbt_map *h, int noutput_items, int ninput_items, const void *in_device, void *out_device,
+                          dvbt_sideband *sb, void *stream);
+void dvbt_map_destroy(dvbt_map *h);
+
+/* ------------------------------------------------------------------ T7 reference_signals
+ * replaces reference_signals::make(itemsize, ninput, noutput, constellation, hierarchy, code_rate_HP, code_rate_LP, guard_interval,
+ * transmission_mode, include_cell_id, cell_id) (include/dvbt/reference_signals.h); pilot_gen::update_output lib/reference_signals_impl.cc:1127-1186
+ * and general_work :1289-1314.  items of ninput cfloat (the payload) -> items of noutput cfloat (the FFT length): zeros left and right, payload in
+ * carrier order, scattered and continual pilots, TPS (the word re-formatted every symbol).  itemsize must be 8, ninput the payload length and
+ * noutput the FFT length of the mode.  symbol_index and frame_index start at 0 and are carried in the handle. */
+typedef struct { int itemsize, ninput, noutput, constellation, hierarchy, code_rate_hp, code_rate_lp,
+                 guard_interval, transmission_mode, include_cell_id, cell_id; } dvbt_reference_signals_params;
+typedef struct dvbt_reference_signals dvbt_reference_signals;
+int  dvbt_reference_signals_create(const dvbt_reference_signals_params *p, dvbt_reference_signals **out);
+int  dvbt_reference_signals_forecast(const dvbt_reference_signals *h, int noutput_items, int *ninput_required);
+int  dvbt_reference_signals_work(dvbt_reference_signals *h, int noutput_items, int ninput_items, const void *in, void *out, dvbt_sideband *sb);
+int  dvbt_reference_signals_work_device(dvbt_reference_signals *h, int noutput_items, int ninput_items, const void *in_device, void *out_device,
+                                        dvbt_sideband *sb, void *stream);
+void dvbt_reference_signals_destroy(dvbt_reference_signals *h);
+
 /* ------------------------------------------------------------------ segment API: the whole chain, device resident
  * One segment = a contiguous run of baseband samples (complex64 at the OFDM elementary rate,
  * i.e. the input of ofdm_sym_acquisition in apps/dvbt_rx_demo*.grc).  The segment is processed
