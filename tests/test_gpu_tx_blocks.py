@@ -5,9 +5,14 @@ entries, whole and split over calls; the chain against the fused modulator (gr_d
 within 1e-5 of the peak; and one chain's baseband decoded by the receiver back to the packets.
 """
 import ctypes as C
+import os
+import sys
 
 import numpy as np
 import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import txref  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -409,3 +414,236 @@ def test_refused_calls_leave_state(g):
     assert (o1 == o2).all()
     a.close()
     bref.close()
+
+
+# ================================================================ the block entries at the sizes the ABI accepts
+def _rs_ref(po, ts):
+    L = po.lib()
+    rs = po.RS()
+    L.o_rs_init(C.byref(rs))
+    ref = np.zeros((len(ts), 204), np.uint8)
+    cw = np.zeros(255, np.uint8)
+    par = np.zeros(16, np.uint8)
+    for w in range(len(ts)):
+        cw[51:239] = ts[w]
+        L.o_rs_encode(C.byref(rs), _p(cw), _p(par))
+        ref[w, :188], ref[w, 188:] = ts[w], par
+    return ref
+
+
+@pytest.mark.parametrize("npk", [1, 127, 128, 129, 255, 256, 1000])
+def test_reed_solomon_enc_packet_counts(po, g, npk):
+    """one, part of, exactly and more than one 128-lane workgroup of txb_rs_enc_kernel, with and without a tail workgroup"""
+    ts = np.random.RandomState(npk).randint(0, 256, (npk, 188)).astype(np.uint8)
+    ref = _rs_ref(po, ts)
+    blocks = 8 if npk % 8 == 0 else 1
+    items = npk // blocks
+    blk = g.Block("reed_solomon_enc", 2, 8, 0x11d, 255, 239, 8, 51, blocks)
+    out = np.zeros_like(ref)
+    assert blk.work(items, items, ts, out)[:2] == (items, items)
+    assert (out == ref).all()
+    r, cons, o = _work_device(blk, items, items, ts, ref.size)
+    assert (r, cons) == (items, items) and (o == ref.reshape(-1)).all()
+    blk.close()
+
+
+@pytest.mark.parametrize("nblocks", [2, 3, 8, 17, 4096])
+def test_energy_dispersal_sizes_prefixes_and_splits(po, g, nblocks):
+    """garbage of 0, 1, 187 and 188 bytes (no 0x47) in front of the first sync byte; the stream over calls of 1 or 2 items, host and device
+    entries alternating, driven as a scheduler would: every call gets what the previous ones did not consume"""
+    item = 1504 * nblocks
+    nitems = 1 if nblocks == 4096 else 4
+    ts = po.make_ts(8 * nblocks * nitems, 30 + nblocks)
+    ref = _dispersal_ref(po, ts)
+    rng = np.random.RandomState(nblocks)
+    for prefix in (0, 1, 187, 188):
+        garbage = rng.randint(0, 256, prefix).astype(np.uint8)
+        garbage[garbage == 0x47] = 0x48
+        x = np.concatenate([garbage, ts])
+        blk = g.Block("energy_dispersal", nblocks)
+        out = np.zeros(nitems * item, np.uint8)
+        pos = done = calls = 0
+        while done < nitems:
+            n = min(int(rng.randint(1, 3)), nitems - done)
+            if calls % 2 == 0:
+                r, cons, _ = blk.work(n, len(x) - pos, x[pos:], out[done * item:])
+            else:
+                r, cons, o = _work_device(blk, n, len(x) - pos, x[pos:], n * item)
+                out[done * item:(done + r) * item] = o[:r * item]
+            assert 0 <= r <= n
+            pos += cons
+            done += r
+            calls += 1
+            assert calls < 3 * nitems + 4, "the block stopped consuming"
+        assert pos == len(x), (prefix, pos)
+        assert (out == ref).all(), prefix
+        blk.close()
+
+
+_RATE_KN = {0: (1, 2), 1: (2, 3), 2: (3, 4), 3: (5, 6), 4: (7, 8)}
+
+
+@pytest.mark.skipif(torch is None, reason="needs torch")
+@pytest.mark.parametrize("noutput", [6048, 3 * 1512, 64 * 1512])
+@pytest.mark.parametrize("const", [0, 1, 2])
+@pytest.mark.parametrize("cr", [0, 1, 2, 3, 4])
+def test_inner_coder_output_sizes(g, noutput, const, cr):
+    m = (2, 4, 6)[const]
+    k, n = _RATE_KN[cr]
+    nin4 = 4 * noutput * k * m // (8 * n)
+    assert nin4 * 8 * n == 4 * noutput * k * m
+    calls = (4, 8) if noutput > 6048 else (4, 8, 4, 12)
+    total = sum(calls)
+    x = np.random.RandomState(1000 * const + 10 * cr + noutput % 97).randint(0, 256, total // 4 * nin4).astype(np.uint8)
+    ref = _inner_code(x, m, cr)
+    assert len(ref) == total * noutput
+    blk = g.Block("inner_coder", 1, noutput, const, 0, cr)
+    assert blk.forecast(4) == nin4
+    out = np.zeros(total * noutput, np.uint8)
+    dx, dout = _dev(x), torch.zeros(total * noutput + 64, dtype=torch.uint8, device="cuda")
+    rpos = wpos = 0
+    for i, nitems in enumerate(calls):
+        if i % 2 == 0:
+            r, cons, _ = blk.work(nitems, len(x) - rpos, x[rpos:], out[wpos * noutput:])
+        else:
+            r, cons, _ = blk.work_device(nitems, len(x) - rpos, dx.data_ptr() + rpos, dout.data_ptr() + wpos * noutput)
+            torch.cuda.synchronize()
+            out[wpos * noutput:(wpos + r) * noutput] = dout[wpos * noutput:(wpos + r) * noutput].cpu().numpy()
+        assert (r, cons) == (nitems, nitems // 4 * nin4)
+        rpos += cons
+        wpos += r
+    assert rpos == len(x)
+    assert (out == ref).all()
+    blk.close()
+
+
+@pytest.mark.parametrize("nsize", [252, 504, 1512, 6048, 49392])
+@pytest.mark.parametrize("const", [0, 1, 2])
+def test_bit_inner_interleaver_sizes(po, g, nsize, const):
+    c = po.cfg(const, po.C1_2, po.T2k)
+    items = 2 if nsize > 6048 else 3
+    x = np.random.RandomState(nsize + const).randint(0, c.csize, (items, nsize)).astype(np.uint8)
+    ref = np.zeros_like(x)
+    po.lib().o_bit_interleave(C.byref(c), _p(x), _p(ref), C.c_size_t(x.size))   # whole 126-word blocks, any number of them
+    blk = g.Block("bit_inner_interleaver", nsize, const, 0, po.T2k)
+    out = np.zeros_like(x)
+    assert blk.work(items, items, x, out)[:2] == (items, items) and (out == ref).all()
+    r, cons, o = _work_device(blk, items, items, x, x.size)
+    assert (r, cons) == (items, items) and (o == ref.reshape(-1)).all()
+    blk.close()
+
+
+@pytest.mark.parametrize("const", [0, 1, 2])
+@pytest.mark.parametrize("hier", [0, 1, 2, 3])
+def test_map_every_label_gain_and_size(po, g, const, hier):
+    c = po.cfg(const, po.C1_2, po.T2k, hierarchy=hier)
+    for gain in (1.0, 0.5, float(np.pi / 7)):
+        pts = np.zeros(c.csize, np.complex64)
+        po.lib().o_constellation(C.byref(c), C.c_float(gain), _p(pts))
+        for nsize in (2, c.payload):
+            rng = np.random.RandomState(nsize + const)
+            nl = max(64, 3 * nsize)
+            lab = rng.randint(0, 256, nl).astype(np.uint8)
+            lab[:64] = np.arange(64)
+            lab &= c.csize - 1                                            # labels of the constellation (the reference indexes its table with them)
+            items = nl // nsize
+            lab = lab[:items * nsize].reshape(items, nsize)
+            blk = g.Block("map", nsize, const, hier, po.T2k, gain)
+            out = np.zeros(lab.shape, np.complex64)
+            assert blk.work(items, items, lab, out)[:2] == (items, items)
+            assert out.view(np.uint64).tobytes() == pts[lab].view(np.uint64).tobytes(), (gain, nsize)
+            r, cons, o = _work_device(blk, items, items, lab, out.nbytes)
+            assert (r, cons) == (items, items) and o.tobytes() == out.tobytes()
+            blk.close()
+
+
+# (const, hier, code rate HP, code rate LP, guard, mode, include_cell_id, cell_id): every value of each parameter at least once, LP != HP three times
+REFSIG = [(0, 0, 0, 0, 0, 0, 0, 0), (1, 1, 1, 3, 1, 1, 1, 0x12), (2, 2, 2, 2, 2, 0, 1, 0xff), (2, 3, 3, 0, 3, 1, 0, 0x5a), (1, 0, 4, 4, 1, 0, 0, 0),
+          (0, 2, 4, 1, 3, 0, 1, 0x81)]
+
+
+@pytest.mark.parametrize("const,hier,cr,cr_lp,guard,mode,cid_on,cid", REFSIG)
+def test_reference_signals_covering_set(po, g, const, hier, cr, cr_lp, guard, mode, cid_on, cid):
+    """the fused modulator's frames (TPS with LP = HP) on every carrier but the TPS ones, and the whole frame where LP = HP; the TPS word decoded
+    from the carriers of every frame: the fields at the bit positions of ETSI EN 300 744 4.6.2 and the BCH(67,53) parity"""
+    d = g.get_dims(const, cr, mode, guard, hier)
+    N, P, zl = d.fft_length, d.payload_length, d.zeros_on_left
+    nsym = 68 * 4 + 9
+    npk = -(-nsym * d.info_bits_per_symbol // 1632)
+    tx = g.Tx(const, cr, mode, guard=guard, hierarchy=hier, include_cell_id=cid_on, cell_id=cid, max_packets=npk, keep_carriers=True)
+    tx.run(_ts(npk, 13))
+    car = tx.carriers()[:nsym]
+    tx.close()
+    assert car.shape == (nsym, N)
+    args = (8, P, N, const, hier, cr, cr_lp, guard, mode, cid_on, cid)
+    blk0 = g.Block("reference_signals", *args)
+    o0 = np.zeros((5, N), np.complex64)
+    blk0.work(5, 5, np.zeros((5, P), np.complex64), o0)                 # symbols 0..4: pilots and TPS alone, one of every class
+    blk0.close()
+    cls = lambda s: 4 if s % 68 == 0 else (s % 68) % 4
+    mask = {}
+    for s in range(5):
+        m_ = np.flatnonzero(o0[s] == 0)
+        mask[cls(s)] = m_[(m_ >= zl) & (m_ < zl + d.Kmax + 1)]
+        assert len(mask[cls(s)]) == P
+    pay = np.stack([car[s, mask[cls(s)]] for s in range(nsym)])
+    blk = g.Block("reference_signals", *args)
+    out = np.zeros((nsym, N), np.complex64)
+    rng = np.random.RandomState(mode + 2 * guard)
+    pos, host = 0, True
+    while pos < nsym:
+        n = min(int(rng.randint(1, 90)), nsym - pos)
+        if host:
+            assert blk.work(n, n, pay[pos:], out[pos:])[:2] == (n, n)
+        else:
+            r, cons, o = _work_device(blk, n, n, pay[pos:pos + n], n * N * 8)
+            assert (r, cons) == (n, n)
+            out[pos:pos + n] = o.view(np.complex64).reshape(n, N)
+        host = not host
+        pos += n
+    blk.close()
+    c = po.cfg(const, cr, mode, guard=guard, hierarchy=hier, include_cell_id=cid_on, cell_id=cid)
+    tcar, wk = txref.tps_carriers(po, c)
+    other = np.ones(N, bool)
+    other[zl + tcar] = False
+    assert out[:, other].view(np.uint64).tobytes() == car[:, other].view(np.uint64).tobytes()
+    if cr_lp == cr:
+        assert out.view(np.uint64).tobytes() == car.view(np.uint64).tobytes()
+    F = txref.tps_field
+    for f in range(4):
+        t = txref.decode_tps(out[68 * f:68 * (f + 1)], zl, tcar, wk)
+        assert t[0] == 0                                                  # the first symbol holds the DBPSK initialisation 2 (1/2 - w_k)
+        assert F(t, 1, 16) == (0x35ee if f % 2 == 0 else 0xca11)           # 4.6.2.2: the sync word in frames 1 and 3, inverted in 2 and 4
+        assert F(t, 17, 22) == (0b011111 if cid_on else 0b010111)          # 4.6.2.3: 31 or 23 TPS bits in use
+        assert F(t, 23, 24) == f                                           # 4.6.2.4
+        assert F(t, 25, 26) == const and F(t, 27, 29) == hier              # 4.6.2.5, 4.6.2.6
+        assert F(t, 30, 32) == cr and F(t, 33, 35) == cr_lp                # 4.6.2.7
+        assert F(t, 36, 37) == guard and F(t, 38, 39) == mode              # 4.6.2.8, 4.6.2.9
+        # 4.6.2.10 sends the cell id's high byte in frames 1 and 3; the reference writes its low byte into every frame
+        # (format_tps_data, set_tps_bits(47, 40, cell_id)), and so does the library
+        assert F(t, 40, 47) == cid & 0xff and F(t, 48, 53) == 0
+        assert txref.bch_remainder(t[1:]) == 0                             # 4.6.3
+
+
+@pytest.mark.parametrize("const,cr,mode,guard,cid_on,cid", [(0, 1, 1, 0, 0, 0), (1, 3, 1, 1, 0, 0), (2, 2, 0, 3, 0, 0), (1, 1, 0, 2, 1, 0x33)])
+@pytest.mark.parametrize("fg_mode", ["host", "device"])
+def test_tx_flowgraph_more_configurations(g, const, cr, mode, guard, cid_on, cid, fg_mode):
+    """test_tx_flowgraph_equals_fused_modulator at 8k QPSK, 8k QAM16, GI 1/4 and with a cell id"""
+    from gr_dvbt_amd.flowgraph import TxFlowgraph
+    d = g.get_dims(const, cr, mode, guard)
+    npk = -(-(68 * 4 + 20) * d.info_bits_per_symbol // 1632)
+    npk = -(-npk // 32) * 32
+    ts = _ts(npk, 4)
+    tx = g.Tx(const, cr, mode, guard=guard, include_cell_id=cid_on, cell_id=cid, max_packets=npk, keep_carriers=True)
+    iq_ref = tx.run(ts)
+    car_ref = tx.carriers()
+    tx.close()
+    fg = TxFlowgraph(const, cr, mode, guard=guard, mode=fg_mode, call_items=np.random.default_rng(const * 10 + cr + guard),
+                     include_cell_id=cid_on, cell_id=cid)
+    bb, car = fg.run(ts)
+    fg.close()
+    n = car.shape[0]
+    assert n >= 68 * 4, n
+    assert (car.view(np.uint64) == car_ref[:n].view(np.uint64)).all()
+    assert len(bb) == n * (d.fft_length + d.cp_length)
+    assert np.abs(bb - iq_ref[:len(bb)]).max() <= 1e-5 * np.abs(iq_ref).max()
