@@ -37,9 +37,12 @@ class RxFlowgraph:
     bit_inner_deinterleaver -> [vector_to_stream] -> viterbi_decoder -> convolutional_deinterleaver -> reed_solomon_dec ->
     energy_descramble, with the parameters of the demo flowgraphs."""
 
-    def __init__(self, constellation, code_rate, mode_t, n_samples, mode="device", call_symbols=4, snr_db=30.0, bsize=768, register_buffers=False):
+    def __init__(self, constellation, code_rate, mode_t, n_samples, mode="device", call_symbols=4, snr_db=30.0, bsize=768, register_buffers=False,
+                 guard=b.G1_32, hierarchy=b.NH, code_rate_lp=None):
         """register_buffers (host mode): page-lock the source and every block's output buffer once (dvbt_host_register), as a GNU Radio shell would its
-        flowgraph buffers: the host-pointer entries then DMA straight from / to them instead of staging every item through pinned memory of the handle"""
+        flowgraph buffers: the host-pointer entries then DMA straight from / to them instead of staging every item through pinned memory of the handle.
+        guard, hierarchy, code_rate_lp: the make() arguments of the blocks that take them (code_rate_lp defaults to code_rate); a hierarchical
+        flowgraph decodes the high-priority stream (bit_inner_deinterleaver's output 0)"""
         self.mode = mode
         self.registered = []
         self.register_buffers = register_buffers and mode == "host"
@@ -48,8 +51,9 @@ class RxFlowgraph:
             import torch
             self.torch = torch
             self.stream = torch.cuda.Stream()
-        d = self.dims = b.get_dims(constellation, code_rate, mode_t)
+        d = self.dims = b.get_dims(constellation, code_rate, mode_t, guard, hierarchy)
         N, cp, P = d.fft_length, d.cp_length, d.payload_length
+        lp = code_rate if code_rate_lp is None else code_rate_lp
         self.call_symbols = call_symbols
         nsym = n_samples // (N + cp) + 2
         self.vit_out_mult = bsize * d.cr_k // 8
@@ -60,11 +64,11 @@ class RxFlowgraph:
         self.stages = [
             S(mk("ofdm_sym_acquisition", 1, N, d.Kmax + 1, cp, snr_db), 8, N * 8, n_samples, nsym),
             S(mk("fft", N, 1, 1), N * 8, N * 8, nsym, nsym),
-            S(mk("demod_reference_signals", 8, N, P, constellation, b.NH, code_rate, code_rate, b.G1_32, mode_t, 0, 0), N * 8, P * 8, nsym, nsym),
-            S(mk("demap", P, constellation, b.NH, mode_t, 1.0), P * 8, P, nsym, nsym),
+            S(mk("demod_reference_signals", 8, N, P, constellation, hierarchy, code_rate, lp, guard, mode_t, 0, 0), N * 8, P * 8, nsym, nsym),
+            S(mk("demap", P, constellation, hierarchy, mode_t, 1.0), P * 8, P, nsym, nsym),
             S(mk("symbol_inner_interleaver", P, mode_t, 0), P, P, nsym, nsym),
-            S(mk("bit_inner_deinterleaver", P, constellation, b.NH, mode_t), P, P, nsym, nsym),
-            S(mk("viterbi_decoder", constellation, b.NH, code_rate, bsize, 0, -1), 1, 1, nsym * P, nbytes),
+            S(mk("bit_inner_deinterleaver", P, constellation, hierarchy, mode_t), P, P, nsym, nsym),
+            S(mk("viterbi_decoder", constellation, hierarchy, code_rate, bsize, 0, -1), 1, 1, nsym * P, nbytes),
             S(mk("convolutional_deinterleaver", 136, 12, 17), 1, 1632, nbytes, nbytes // 1632 + 2),
             S(mk("reed_solomon_dec", 2, 8, 0x11d, 255, 239, 8, 51, 8, 0), 1632, 1504, nbytes // 1632 + 2, nbytes // 1632 + 2),
             S(mk("energy_descramble", 8), 1504, 1, nbytes // 1632 + 2, nbytes),

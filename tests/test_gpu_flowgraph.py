@@ -90,3 +90,69 @@ def test_registered_host_buffers(po, tmp_path):
     ts = np.fromfile(fout, np.uint8)
     n = min(len(ts), len(ref))
     assert n > 0.9 * len(ref) and (ts[:n] == ref[:n]).all()
+
+
+FG_SWEEP = [  # (mode_t, guard, constellation, code rate, driver mode, call_symbols)
+    (g.T2k, g.G1_16, g.QPSK, g.C2_3, "device", 1),
+    (g.T8k, g.G1_16, g.QAM16, g.C3_4, "host", 4),
+    (g.T2k, g.G1_8, g.QAM64, g.C5_6, "device", 33),
+    (g.T8k, g.G1_8, g.QPSK, g.C5_6, "device", 4),
+    (g.T2k, g.G1_4, g.QAM16, g.C3_4, "host", 33),
+    (g.T8k, g.G1_4, g.QAM64, g.C2_3, "device", 1),
+]
+FG_HIER = [  # (mode_t, guard, constellation, hierarchy, HP rate, LP rate, driver mode, call_symbols)
+    (g.T2k, g.G1_16, g.QAM16, g.ALPHA2, g.C1_2, g.C3_4, "device", 4),
+    (g.T8k, g.G1_8, g.QAM64, g.ALPHA4, g.C2_3, g.C1_2, "host", 33),
+]
+
+
+@pytest.mark.parametrize("mode_t,guard,const,cr,mode,call_symbols", FG_SWEEP,
+                         ids=[f"{'28'[a[0]]}k-g{a[1]}-c{a[2]}-r{a[3]}-{a[4]}-{a[5]}" for a in FG_SWEEP])
+def test_block_by_block_every_guard_constellation_rate(po, mode_t, guard, const, cr, mode, call_symbols):
+    """the drop-in path at guards 1/16, 1/8, 1/4, QPSK and rates 2/3, 3/4, 5/6 (the blocks get the guard from RxFlowgraph): the oracle's TS from the
+    first byte"""
+    c = po.cfg(const, cr, mode_t, guard=guard)
+    iq = po.stream_slice(c, 3 if mode_t == g.T2k else 2, 9)
+    ref = po.rx(c, iq, want=("ts",))["ts"]
+    fg = RxFlowgraph(const, cr, mode_t, len(iq), mode=mode, call_symbols=call_symbols, guard=guard)
+    ts = fg.run(iq)
+    calls = [st.calls for st in fg.stages]
+    fg.close()
+    assert min(calls) > 0
+    n = min(len(ts), len(ref))
+    assert n > 0.9 * len(ref) and abs(len(ts) - len(ref)) <= 64 * 1504
+    assert (ts[:n] == ref[:n]).all()
+
+
+@pytest.mark.parametrize("mode_t,guard,const,hier,cr,cr_lp,mode,call_symbols", FG_HIER,
+                         ids=[f"{'28'[a[0]]}k-g{a[1]}-c{a[2]}-h{a[3]}-{a[6]}-{a[7]}" for a in FG_HIER])
+def test_block_by_block_hierarchical(po, mode_t, guard, const, hier, cr, cr_lp, mode, call_symbols):
+    """a hierarchical stream through the drop-in path: no TS comes out (the decoder unpacks d_m bits of every byte of the high-priority stream, as
+    gr-dvbt's does: test_gpu_chain.py::test_hierarchical_modes_every_tap), so every stage up to the decoder is held to the oracle over the common
+    prefix -- equalised carriers within the contract's tolerance, demap, symbol and bit de-interleaver (output 0) and Viterbi bytes equal"""
+    c = po.cfg(const, cr, mode_t, guard=guard, hierarchy=hier)
+    pps = po.packets_per_superframe(c)
+    iq = po.tx(c, po.make_ts(2 * pps + pps // 2, 14), lead_in=1000, tail=3 * c.N)
+    o = po.rx(c, iq, want=("eq", "demap", "symdeint", "bitdeint", "vit"))
+    fg = RxFlowgraph(const, cr, mode_t, len(iq), mode=mode, call_symbols=call_symbols, guard=guard, hierarchy=hier, code_rate_lp=cr_lp)
+    fg.run(iq)
+
+    def items(k, dtype, width):
+        st = fg.stages[k]
+        buf = st.out[:st.produced * st.out_item]
+        buf = buf.cpu().numpy() if mode == "device" else np.asarray(buf)
+        return buf.view(dtype).reshape(-1, width)
+    eq = items(2, np.complex64, c.payload)
+    taps = {"demap": items(3, np.uint8, c.payload), "symdeint": items(4, np.uint8, c.payload), "bitdeint": items(5, np.uint8, c.payload),
+            "vit": items(6, np.uint8, 1).reshape(-1)}
+    fg.close()
+    ne = min(len(eq), len(o["eq"]))
+    assert ne > 0.9 * len(o["eq"]) > 100
+    d = eq[:ne] - o["eq"][:ne]
+    assert max(np.abs(d.real).max(), np.abs(d.imag).max()) <= 1e-3 * 2 * c.norm
+    assert taps["bitdeint"].max() == 3                                  # two bits per carrier on the high-priority stream
+    for key, a in taps.items():
+        b = o[key]
+        n = min(len(a), len(b))
+        assert n > 0.9 * len(b) > 0, key
+        assert (a[:n] == b[:n]).all(), key

@@ -4,6 +4,7 @@ step's decode, stitches what arrived and compares it with the transmitted packet
 is N: the same code path with world > 1 (covered with two ranks under gloo in tests/test_dist_gloo.py)."""
 import json
 import os
+import random
 import socket
 import subprocess
 import sys
@@ -15,8 +16,29 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def _free_port():
+    """a port for the child's TCPStore server that stays free until the child binds it, seconds later.  The kernel hands out the ports of
+    net.ipv4.ip_local_port_range to every bind(port 0) and every outgoing connection on the machine, so a port picked there and released can be
+    taken in the meantime (EADDRINUSE in init_process_group).  A port below that range, found free, is only taken by a process that asks for that
+    very number.  Ports from 29400 on (the torch defaults) are left out; a machine whose ephemeral range starts below 20000 gets one from it."""
+    lo = 32768
+    try:
+        with open("/proc/sys/net/ipv4/ip_local_port_range") as f:
+            lo = int(f.read().split()[0])
+    except (OSError, ValueError, IndexError):
+        pass
+    rng = random.Random()
+    candidates = range(20000, min(lo, 29400))
+    for p in rng.sample(candidates, min(200, len(candidates))):
+        s = socket.socket()
+        try:
+            s.bind(("", p))
+        except OSError:
+            continue
+        finally:
+            s.close()
+        return p
     s = socket.socket()
-    s.bind(("127.0.0.1", 0))
+    s.bind(("", 0))
     p = s.getsockname()[1]
     s.close()
     return p
