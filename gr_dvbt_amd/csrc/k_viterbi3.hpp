@@ -25,7 +25,7 @@
 //  * path byte (8 bits): the content of the reference's path byte of the survivor -- the state at the window start
 //    (kept as that state's cell storage index, bits 5:0) and the two oldest inputs of the window (= top two bits of
 //    the state after step 6, stamped there, bits 7:6).  It rides along with the metric through v_pk_max (metric
-//    fields never tie).  In the LDS ring a hop is one v_and_or: origin = byte & 63, merged with the next row address.
+//    fields never tie).  In the LDS ring a hop is one v_bfi: origin = byte & 63, inserted under the next row's offset (v3_hop).
 //  * the tie-break bits are armed THREE STEPS AT A TIME.  Whether a cell holds an upper state at a step depends on one bit of its
 //    index, a different one at every step, and the two cells of a butterfly differ in exactly the bit of the current step.  So the
 //    biases of the next three steps can be written together into bits 6, 7, 8 (the earliest step in the lowest bit; bits 7:6 of
@@ -35,6 +35,14 @@
 //    steps re-arms after steps 3, 6 (with the stamp), 7 and 8 (with the origin of the next window): 4 v_and_or instead of 8.
 // Per step and VGPR (two cells): v_perm (both branch-metric deltas from ONE word of four class deltas), pk_add,
 // pk_sub, exchange, pk_max, and on every second step a v_and_or: 2.75 instructions per cell.
+//
+// The instruction budget, as compiled (tools/vit_window_count.py on the device assembly; tests/test_viterbi_isa_budget.py holds it): a window is 77 VALU instructions for
+// its eight steps, 1 for the path-byte word and 12.5 for its end = 90.5, plus its address arithmetic; a traceback hop is 2 per chain (one row back, one v_bfi).  A block of
+// V3_BLK windows of viterbi3_kernel<24, 72, 1> is straight-line code: windows 0-11 with the previous block's 2 x 23 hops 95.7 per window (106.8 before the ring became one
+// array of the workgroup), windows 12-23 87.9 (94.0 as a loop of six), staging, the chains' start and the output of the traceback ~270 per block: 2,472 instructions per
+// block of 24 windows measured (SQ_INSTS_VALU) against 2,727.  Every stamp is one v_and_or_b32 (the lane constants are kept opaque, v3_init_lane).
+// What the count alone did not buy, the order of the LDS reads did: a hop's read and its use stand three and five steps apart (v3_fwd_window), and a window's
+// step words are loaded one window ahead (v3_fwd_six) -- the wavefront, one of two on its SIMD, no longer waits out the LDS latency 70 times per block.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -155,6 +163,12 @@ __device__ inline void v3_init_lane(int pl, V3Lane &L)
       L.arm_b2[e][r] = b2 | L.bias8[P0][r];
     }
   }
+  // Some of these operands are the same in every lane (bias8[0], bias8[1] and what is built from them alone): left visible, the compiler folds them into literals and a
+  // stamp becomes v_and_b32 + v_or_b32 with one literal each.  Kept opaque they stay in VGPRs and every stamp is one v_and_or_b32 (see vconst)
+  for (int r = 0; r < 2; r++) {
+    for (int P = 0; P < 6; P++) asm("" : "+v"(L.bias8[P][r]));
+    for (int e = 0; e < 3; e++) { asm("" : "+v"(L.kc[e][r])); asm("" : "+v"(L.arm_mid[e][r])); asm("" : "+v"(L.arm_b2[e][r])); asm("" : "+v"(L.arm_org[e][r])); }
+  }
 }
 
 // ST: what happens to the tie-break bits after the step (see the header): 0 nothing (the bits armed earlier serve the next step too);
@@ -193,18 +207,12 @@ template <int P, int ST> __device__ __forceinline__ void v3_step(int (&v)[2], un
   }
 }
 
-// the 8 steps of a window that starts at phase P0 (0, 2, 4); v arrives with the origin stamp in its path bytes
+// (the 8 steps of a window that starts at phase P0 = 0, 2, 4 are written out in v3_fwd_window; v arrives with the origin stamp in its path bytes)
 #if V3_EXP & 64
 #define V3_YIELD() asm volatile("s_nop 3" ::: "memory")
 #else
 #define V3_YIELD()
 #endif
-template <int P0> __device__ __forceinline__ void v3_window(int (&v)[2], const unsigned (&W)[8], const V3Lane &L, int (&raw)[2])
-{
-  v3_step<(P0 + 0) % 6, 0>(v, W[0], L, raw); V3_YIELD(); v3_step<(P0 + 1) % 6, 0>(v, W[1], L, raw); V3_YIELD(); v3_step<(P0 + 2) % 6, 3>(v, W[2], L, raw); V3_YIELD();
-  v3_step<(P0 + 3) % 6, 0>(v, W[3], L, raw); V3_YIELD(); v3_step<(P0 + 4) % 6, 0>(v, W[4], L, raw); V3_YIELD(); v3_step<(P0 + 5) % 6, 1>(v, W[5], L, raw); V3_YIELD();
-  v3_step<(P0 + 6) % 6, 4>(v, W[6], L, raw); V3_YIELD(); v3_step<(P0 + 7) % 6, 2>(v, W[7], L, raw);
-}
 
 // halves of a packed register as sign-extended 32-bit values
 __device__ __forceinline__ int lo16(int x) { return (x << 16) >> 16; }
@@ -233,34 +241,45 @@ template <int PE, bool RENORM> __device__ __forceinline__ int v3_window_end(int 
 }
 
 // Two traceback chains per lane: the calls (windows) pl and 16+pl of one block of a decoder.
+// The ring of path bytes is ONE array of the workgroup, [window][wavefront][decoder][cell z]: a window's row is V3_ROW<NW> = NW * 256 bytes, the wavefront and the decoder sit
+// in bits 9:6 of the byte offset, below the window and above the cell.  A chain's offset into it is then a bit field of one register, and a hop needs no base address.
+template <int NW> constexpr int V3_ROW = NW * 4 * 64;                              // bytes per window of the ring
+template <int NW> constexpr int V3_RMASK = (V3_RINGW * V3_ROW<NW> - 1) & ~63;      // window | wavefront | decoder in a byte offset (NW = 4: 0xffc0, the ring is 64 KB)
 struct V3Trace {
-  int z[2];             // current cell (storage index)
-  int wsh[2];           // ring row of the window whose table is read next (<< 8, counts down past zero: only bits 13:8 are used) | decoder row << 6
-  int wlast[2];         // the window a chain ends in (relative index)
+  int z[2];             // current cell: byte offset into the ring = window row | wavefront | decoder | storage index
+  int wsh[2];           // ring row of the window whose table is read next (x V3_ROW; counts down past zero: only the bits of V3_RMASK are used) | wavefront << 8 | decoder << 6
+  int oph[2];           // phase at the start of the window a chain ends in: 2 * (window mod 3)
   bool ok[2];
-  long long ob[2];      // output byte of the call
+  int oend[2];          // the chunk's end for the calls this chain takes (no call: INT_MIN)
+  int ob[2];            // output byte of the call, relative to the chunk's first byte
 };
 // one hop of both chains: state = path_byte >> 2 in the reference's layout (d_viterbi.c:717) = the low six bits here.
-// wa = ring row of the window to read | decoder row; the v_and_or that extracts the origin also forms the address.
-__device__ __forceinline__ void v3_hop(V3Trace &T, const unsigned char *tab, int rowc)
+// Two VALU instructions per chain: one row back, and the v_bfi that takes window, wavefront and decoder from wsh and the origin (bits 5:0) from the path byte -- the ring's wrap
+// is the mask.  (Written as asm: from the C expression the compiler re-derives the row from the chain's start and masks both sides, four instructions.)
+// The two halves of a hop are separate so that the forward pass can put add-compare-select steps between the read and the use of the path byte.
+__device__ __forceinline__ void v3_hop_read(const V3Trace &T, const unsigned char *tab, unsigned (&t)[2])
+{
+#pragma unroll
+  for (int q = 0; q < 2; q++) t[q] = tab[T.z[q]];                    // z is the whole offset into the ring
+}
+template <int NW> __device__ __forceinline__ void v3_hop_merge(V3Trace &T, const unsigned (&t)[2])
 {
 #pragma unroll
   for (int q = 0; q < 2; q++) {
-    const unsigned t = tab[T.z[q]];                                  // z holds the full LDS index
-    T.wsh[q] -= 256;                                                 // one ring row back; the decoder row rides in bits 7:6, the wrap is the mask below
-    T.z[q] = (T.wsh[q] & 0x3fc0) | ((int)t & ~0x3fc0);               // one v_bfi: ring row and decoder row from wsh, the origin (bits 5:0) from the path byte
+    T.wsh[q] -= V3_ROW<NW>;
+    asm("v_bfi_b32 %0, %1, %2, %3" : "=v"(T.z[q]) : "s"(V3_RMASK<NW>), "v"(T.wsh[q]), "v"(t[q]));
   }
 }
+template <int NW> __device__ __forceinline__ void v3_hop(V3Trace &T, const unsigned char *tab) { unsigned t[2]; v3_hop_read(T, tab, t); v3_hop_merge<NW>(T, t); }
 // the decoded byte of a call: (state at the start of the last window of the chain) << 2 | its two oldest inputs.
-// w = that window (relative index, for its phase)
-__device__ __forceinline__ void v3_trace_out(const V3Trace &T, const unsigned char *tab, int rowc, uint8_t *out, long long out_lo)
+// outb = where the chunk's first byte goes
+__device__ __forceinline__ void v3_trace_out(const V3Trace &T, const unsigned char *tab, uint8_t *outb)
 {
 #pragma unroll
   for (int q = 0; q < 2; q++) {
     const unsigned t = tab[T.z[q]];
-    const int w = T.wlast[q];
-    const int sstart = rotl6(v3_cell_of_z((int)(t & 63u)), 2 * (((w % 3) + 3) % 3));    // phase of window w = (8w) % 6
-    if (T.ok[q]) out[T.ob[q] - out_lo] = (unsigned char)((sstart << 2) | (t >> 6));
+    const int sstart = rotl6(v3_cell_of_z((int)(t & 63u)), T.oph[q]);                   // phase of window w = (8w) % 6
+    if (T.ok[q]) outb[T.ob[q]] = (unsigned char)((sstart << 2) | (t >> 6));
   }
 }
 
@@ -268,22 +287,28 @@ __device__ __forceinline__ void v3_trace_out(const V3Trace &T, const unsigned ch
 // after every second window.  HOPS: two traceback hops of the previous block's calls ride along (their LDS latency
 // hides under the add-compare-select work).
 // Which hops exist is a compile-time fact (HOP0 + 2 V6 (+1) < NTB - 1 with NTB = ntraceback, a template parameter of the
-// kernel): the window stays one straight-line block and the scheduler can spread the dependent LDS reads over it.
-template <int V6, bool HOPS, int HOP0, int NTB> __device__ __forceinline__ void v3_fwd_window(int (&v)[2], const V3Lane &L, const unsigned *wrow, unsigned char *tab,
-                                                                                           unsigned char *bests, int j0, int dd, int pl, V3Trace &T)
+// kernel): the window stays one straight-line block, with the dependent LDS reads spread over it (below).
+__device__ __forceinline__ void v3_load_words(const unsigned *wp_, unsigned (&W)[8])
 {
-  if (HOPS && HOP0 + 2 * V6 < NTB - 1) v3_hop(T, tab, dd * 64);
-  if (HOPS && HOP0 + 2 * V6 + 1 < NTB - 1) v3_hop(T, tab, dd * 64);
+  const uint4 *wp = reinterpret_cast<const uint4 *>(wp_);
+  const uint4 t0 = wp[0], t1 = wp[1];
+  W[0] = t0.x; W[1] = t0.y; W[2] = t0.z; W[3] = t0.w; W[4] = t1.x; W[5] = t1.y; W[6] = t1.z; W[7] = t1.w;
+}
+// tabw = the ring at this lane's word of a row (wavefront, decoder, 4 x lane in row)
+// W = the window's eight step words, already in registers; PREF: the next window's (they follow in wrow) are loaded into Wn at the start of this one, a window ahead of their use
+template <int V6, bool HOPS, int HOP0, int NTB, int NW, bool PREF> __device__ __forceinline__ void v3_fwd_window(int (&v)[2], const V3Lane &L, const unsigned *wrow, unsigned char *tab, unsigned char *tabw,
+                                                                                           unsigned char *bests, int j0, int dd, int pl, V3Trace &T, unsigned (&W)[8], unsigned (&Wn)[8])
+{
+  // a window's two hops are dependent LDS reads: the first is issued here and used behind the window's 3rd step, where the second is issued, which is used behind the last step
+  // (the compiler keeps the source order: written as read + use in one place they end up 1 to 5 instructions apart, and the wavefront waits out the LDS latency 46 times a block)
+  constexpr bool HOPA = HOPS && HOP0 + 2 * V6 < NTB - 1, HOPB = HOPS && HOP0 + 2 * V6 + 1 < NTB - 1;
+  unsigned th[2];
+  if (HOPA) v3_hop_read(T, tab, th);
   const int jr = (j0 + V6) & (V3_RINGW - 1);
-  unsigned W[8];
 #if V3_EXP & 256
   for (int i = 0; i < 8; i++) { W[i] = (unsigned)(j0 * 0x01010101 + i * 0x00020406 + pl); asm volatile("" : "+v"(W[i])); }   // no LDS read in the loop
 #else
-  {
-    const uint4 *wp = reinterpret_cast<const uint4 *>(wrow + V6 * 8);
-    const uint4 t0 = wp[0], t1 = wp[1];
-    W[0] = t0.x; W[1] = t0.y; W[2] = t0.z; W[3] = t0.w; W[4] = t1.x; W[5] = t1.y; W[6] = t1.z; W[7] = t1.w;
-  }
+  if (PREF) v3_load_words(wrow + (V6 + 1) * 8, Wn);
 #endif
   constexpr int P0 = (8 * V6) % 6;
   int raw[2];
@@ -293,19 +318,24 @@ template <int V6, bool HOPS, int HOP0, int NTB> __device__ __forceinline__ void 
 #if V3_EXP & 128
   __builtin_amdgcn_s_sleep(1);
 #endif
-  v3_window<P0>(v, W, L, raw);
+  v3_step<(P0 + 0) % 6, 0>(v, W[0], L, raw); V3_YIELD(); v3_step<(P0 + 1) % 6, 0>(v, W[1], L, raw); V3_YIELD(); v3_step<(P0 + 2) % 6, 3>(v, W[2], L, raw); V3_YIELD();
+  if (HOPA) { v3_hop_merge<NW>(T, th); if (HOPB) v3_hop_read(T, tab, th); }
+  v3_step<(P0 + 3) % 6, 0>(v, W[3], L, raw); V3_YIELD(); v3_step<(P0 + 4) % 6, 0>(v, W[4], L, raw); V3_YIELD(); v3_step<(P0 + 5) % 6, 1>(v, W[5], L, raw); V3_YIELD();
+  v3_step<(P0 + 6) % 6, 4>(v, W[6], L, raw); V3_YIELD(); v3_step<(P0 + 7) % 6, 2>(v, W[7], L, raw);
+  if (HOPB) v3_hop_merge<NW>(T, th);
   // the four path bytes of this lane's cells = one word of the table (storage index z = 4*lane + 2r + h)
-  if (!(V3_EXP & 4)) *reinterpret_cast<unsigned *>(tab + (jr * 4 + dd) * 64 + pl * 4) = __builtin_amdgcn_perm((unsigned)raw[1], (unsigned)raw[0], 0x06040200u);
+  if (!(V3_EXP & 4)) *reinterpret_cast<unsigned *>(tabw + jr * V3_ROW<NW>) = __builtin_amdgcn_perm((unsigned)raw[1], (unsigned)raw[0], 0x06040200u);
   if (V3_EXP & 2) { if (raw[0] == 0x12345) bests[jr] = 1; return; }
   const int s = v3_window_end<(P0 + 2) % 6, (V6 & 1) == 1>(v, L);
   bests[dd * V3_RINGW + jr] = (unsigned char)s;                    // low byte of the key (63 - best state in bits 5:0); all 16 lanes of the row write the same byte
 }
-template <bool HOPS, int HOP0, int NTB> __device__ __forceinline__ void v3_fwd_six(int (&v)[2], const V3Lane &L, const unsigned *wrow, unsigned char *tab,
-                                                                                  unsigned char *bests, int j0, int dd, int pl, V3Trace &T)
+// six windows; Wa arrives with the first window's step words and leaves with those of the window behind the six (MORE: there is one in this block)
+template <bool HOPS, int HOP0, int NTB, int NW, bool MORE> __device__ __forceinline__ void v3_fwd_six(int (&v)[2], const V3Lane &L, const unsigned *wrow, unsigned char *tab, unsigned char *tabw,
+                                                                                  unsigned char *bests, int j0, int dd, int pl, V3Trace &T, unsigned (&Wa)[8], unsigned (&Wb)[8])
 {
-  v3_fwd_window<0, HOPS, HOP0, NTB>(v, L, wrow, tab, bests, j0, dd, pl, T); v3_fwd_window<1, HOPS, HOP0, NTB>(v, L, wrow, tab, bests, j0, dd, pl, T);
-  v3_fwd_window<2, HOPS, HOP0, NTB>(v, L, wrow, tab, bests, j0, dd, pl, T); v3_fwd_window<3, HOPS, HOP0, NTB>(v, L, wrow, tab, bests, j0, dd, pl, T);
-  v3_fwd_window<4, HOPS, HOP0, NTB>(v, L, wrow, tab, bests, j0, dd, pl, T); v3_fwd_window<5, HOPS, HOP0, NTB>(v, L, wrow, tab, bests, j0, dd, pl, T);
+  v3_fwd_window<0, HOPS, HOP0, NTB, NW, true>(v, L, wrow, tab, tabw, bests, j0, dd, pl, T, Wa, Wb); v3_fwd_window<1, HOPS, HOP0, NTB, NW, true>(v, L, wrow, tab, tabw, bests, j0, dd, pl, T, Wb, Wa);
+  v3_fwd_window<2, HOPS, HOP0, NTB, NW, true>(v, L, wrow, tab, tabw, bests, j0, dd, pl, T, Wa, Wb); v3_fwd_window<3, HOPS, HOP0, NTB, NW, true>(v, L, wrow, tab, tabw, bests, j0, dd, pl, T, Wb, Wa);
+  v3_fwd_window<4, HOPS, HOP0, NTB, NW, true>(v, L, wrow, tab, tabw, bests, j0, dd, pl, T, Wa, Wb); v3_fwd_window<5, HOPS, HOP0, NTB, NW, MORE>(v, L, wrow, tab, tabw, bests, j0, dd, pl, T, Wb, Wa);
 }
 
 // A chunk = vp.chunk_bytes decoded bytes; it is decoded by an independent decoder that starts `warm` windows early
@@ -362,7 +392,7 @@ __device__ __forceinline__ int *v3_fix(const V3Aux &ax, long long c) { return ax
 inline size_t v3_snap_words(long long cap) { return (size_t)(cap + 2) * 3 * V3_SLOT; }
 inline size_t v3_ctl_words(long long cap) { return (size_t)V3_CTL_HDR + 2 * (size_t)(cap + 2); }
 
-struct V3Lds { unsigned char *tab; unsigned *wbuf; unsigned char *bests; const unsigned *lut; };
+struct V3Lds { unsigned char *tab; unsigned *wbuf; unsigned char *bests; const unsigned *lut; int wv; };   // tab: the workgroup's ring; wbuf, bests: the wavefront's; wv: the wavefront
 // the label-class deltas of a step as a function of (keep flags, next two received bits); every wavefront writes the same 16 words
 __device__ __forceinline__ void v3_init_lut(unsigned *lut, int lane)
 {
@@ -381,7 +411,7 @@ __device__ __forceinline__ void v3_init_lut(unsigned *lut, int lane)
 // MODE 0: the plain chunk decoder.  MODE 1: the same, and it leaves own[] / pred[] (own, predn: this lane's two words of the slots; inject: the state chunk 0 is handed at its
 // first window instead of what its warm-up produced).  MODE 2: from the state in v, no warm-up (WARM is ignored); endv = the state at the next chunk's first window.
 // WARM: the warm-up in windows as a compile-time constant (the default instantiation: V3_WARM), or 0: taken from vp.warm (any multiple of V3_BLK up to V3_WARM_MAX).
-template <int NTB, int WARM, int MODE>
+template <int NTB, int WARM, int MODE, int NW>
 __device__ __forceinline__ void v3_decode(const uint8_t *__restrict__ in, uint8_t *__restrict__ out, long long total_steps, long long total_out, const VitParams &vp,
                                           long long in_base, long long out_lo, long long b0, bool dec_active, const V3Lds &S, const V3Lane &L, int (&v)[2], int (&endv)[2],
                                           int *own, int *predn, const int *inject, int *carry, int carry_rel)
@@ -395,6 +425,8 @@ __device__ __forceinline__ void v3_decode(const uint8_t *__restrict__ in, uint8_
   constexpr int V3_CBS = V3_BLK * 8;                                               // stride between the decoders' bit streams
   static_assert(V3_CBW <= V3_CBS, "bit stream does not fit the step-word row");
   const int lane = threadIdx.x & 63, dd = lane >> 4, pl = lane & 15;
+  const int rowl = S.wv * 256 + dd * 64;                           // wavefront | decoder in a ring offset
+  unsigned char *const tabw = tab + rowl + pl * 4;
   const int B = vp.chunk_bytes, m = vp.m;
   constexpr int ntb = NTB;                                         // == vp.ntb (the host picks the instantiation)
   const long long b1 = (b0 + B < total_out) ? b0 + B : total_out;
@@ -404,16 +436,46 @@ __device__ __forceinline__ void v3_decode(const uint8_t *__restrict__ in, uint8_
   const long long n_in_bytes = (total_steps * 2 / vp.plen * vp.n + vp.m - 1) / vp.m;   // input bytes that exist
   const int nload = ((384 + 2 * m - 2) / m + 3 + 15) / 16;         // lanes whose 16 bytes a block can need (13, 7, 5)
 
-  // ---- staging, first half: where block jb starts in the input (row-uniform) and the load of its bytes
-  int ph0 = 0, bo0 = 0, off = 0; uint4 q = make_uint4(0, 0, 0, 0);
+  // what the traceback compares and addresses per block, as 32-bit offsets from the chunk's first byte (the 64-bit arithmetic is done once, here)
+  uint8_t *const outb = out + (b0 - out_lo);
+  const int ob_end = !dec_active ? INT_MIN : (int)(b1 - b0 > INT_MIN / 2 ? b1 - b0 : INT_MIN / 2);      // a call is written when ob_lo <= its byte < ob_end[chain]
+  const int ob_lo = MODE != 1 || out_lo <= b0 ? 0 : (int)(out_lo - b0 < INT_MAX / 2 ? out_lo - b0 : INT_MAX / 2);
+  const long long tb0 = 8 * (w0 - 1) - 2;                          // real step index of step 0 of block 0 (may be < 0)
+  constexpr int BLKBITS = 2 * 8 * V3_BLK;                          // depunctured bits per block
+  const int inc_q = BLKBITS / vp.plen, inc_ph = BLKBITS - inc_q * vp.plen;   // a block's advance in puncture periods (once per decoder)
+  const unsigned magic16_m = (65536u + (unsigned)m - 1) / (unsigned)m;       // x / m for x < 65536 / m
+
+  // The blocks of this wavefront's four decoders whose 8 * V3_BLK steps are all real steps of the stream are jb = u_first .. u_last (a block reaches before the stream's start only
+  // in the warm-up of the stream's first chunk, past its end only in its last chunks, and an idle decoder has none): everywhere else staging needs no clamp, and the test is scalar
+  int u_first, u_last;
+  {
+    const long long r = total_steps - 8 * V3_BLK - tb0;
+    int first = tb0 >= 0 ? 0 : (int)((-tb0 + 7) >> 3 < J ? (-tb0 + 7) >> 3 : J), last = !dec_active || r < 0 ? -1 : (int)(r >> 3 < J ? r >> 3 : J);
+    u_first = max(max(__builtin_amdgcn_readlane(first, 0), __builtin_amdgcn_readlane(first, 16)), max(__builtin_amdgcn_readlane(first, 32), __builtin_amdgcn_readlane(first, 48)));
+    u_last = min(min(__builtin_amdgcn_readlane(last, 0), __builtin_amdgcn_readlane(last, 16)), min(__builtin_amdgcn_readlane(last, 32), __builtin_amdgcn_readlane(last, 48)));
+  }
+  // ---- staging, first half: where block jb starts in the input (row-uniform) and the load of its bytes.  The blocks are staged in order: behind a block whose step 0 is a real
+  // step the position advances by BLKBITS depunctured bits -- ph0, the byte and bo0 are carried with small integers; the 64-bit locate runs for a decoder's first block, and for
+  // the blocks of a decoder that starts before the stream does (the clamp below), in which case the whole wavefront takes it.
+  int ph0 = 0, bo0 = 0, off = 0; long long byte0 = 0; uint4 q = make_uint4(0, 0, 0, 0);
   auto stage_load = [&](int jb) {
-    const long long tb = 8 * (w0 - 1) + (long long)jb * 8 - 2;     // real step index of block step 0 (may be < 0)
-    const unsigned long long pbit = 2ull * (unsigned long long)(tb > 0 ? tb : 0);
-    const unsigned long long pq = __umul64hi(pbit, vp.magic_plen);
-    ph0 = (int)(pbit - pq * (unsigned)vp.plen);
-    const unsigned long long rb = pq * (unsigned)vp.n + ((vp.prefix_nib >> (4 * ph0)) & 15ull);
-    const unsigned long long by = __umul64hi(rb, vp.magic_m);
-    const long long byte0 = (long long)by; bo0 = (int)(rb - by * (unsigned)m);
+    const long long tb = tb0 + (long long)jb * 8;                  // real step index of block step 0 (may be < 0)
+    if (jb > 0 && jb - V3_BLK >= u_first) {                         // (the block before starts at a real step in all four decoders)
+      const int pf0 = (int)((vp.prefix_nib >> (4 * ph0)) & 15ull);
+      ph0 += inc_ph;
+      const int wrap = ph0 >= vp.plen ? 1 : 0;
+      ph0 -= wrap ? vp.plen : 0;
+      const int r = bo0 + (inc_q + wrap) * vp.n + (int)((vp.prefix_nib >> (4 * ph0)) & 15ull) - pf0;   // received bits from the old byte's first bit (0 <= r < 1024)
+      const int dby = (int)(((unsigned)r * magic16_m) >> 16);
+      bo0 = r - dby * m; byte0 += dby;
+    } else {
+      const unsigned long long pbit = 2ull * (unsigned long long)(tb > 0 ? tb : 0);
+      const unsigned long long pq = __umul64hi(pbit, vp.magic_plen);
+      ph0 = (int)(pbit - pq * (unsigned)vp.plen);
+      const unsigned long long rb = pq * (unsigned)vp.n + ((vp.prefix_nib >> (4 * ph0)) & 15ull);
+      const unsigned long long by = __umul64hi(rb, vp.magic_m);
+      byte0 = (long long)by; bo0 = (int)(rb - by * (unsigned)m);
+    }
     off = (int)(((unsigned long long)(uintptr_t)in + (unsigned long long)(byte0 - in_base)) & 3ull);
     const long long src = byte0 - off + pl * 16;                   // 4-byte aligned address
     q = make_uint4(0, 0, 0, 0);
@@ -445,17 +507,21 @@ __device__ __forceinline__ void v3_decode(const uint8_t *__restrict__ in, uint8_
     }
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
     constexpr int SPL = V3_BLK * 8 / 16;                           // steps per lane
-    const long long tb = 8 * (w0 - 1) + (long long)jb * 8 - 2;
-    const long long tbr = tb > 0 ? tb : 0;
+    const long long tb = tb0 + (long long)jb * 8;
     const int ub0 = pl * SPL;
-    const long long t = tb + ub0;
-    int lo = 0;                                                    // leading steps before the stream start
-    if (t < 0) lo = (-t < SPL) ? (int)(-t) : SPL;
-    const long long rem = total_steps - t;
-    int hi = !dec_active ? 0 : rem <= 0 ? 0 : rem < SPL ? (int)rem : SPL;
-    if (hi < lo) hi = lo;
-    int x = ph0 + 2 * (int)((t + lo) - tbr);                        // depunctured-bit offset of the first real step from the row base
-    if (x < 0) x = 0;
+    // a block that lies inside the stream, of a decoder that exists: every step is real.  Otherwise (a decoder's blocks around the stream's start and end) the wavefront clamps
+    int lo = 0, hi = SPL;                                          // leading steps before the stream start; end of the real steps
+    int x = ph0 + 2 * ub0;                                         // depunctured-bit offset of the first real step from the row base
+    if (jb < u_first || jb > u_last) {
+      const long long tbr = tb > 0 ? tb : 0;
+      const long long t = tb + ub0;
+      if (t < 0) lo = (-t < SPL) ? (int)(-t) : SPL;
+      const long long rem = total_steps - t;
+      hi = !dec_active ? 0 : rem <= 0 ? 0 : rem < SPL ? (int)rem : SPL;
+      if (hi < lo) hi = lo;
+      x = ph0 + 2 * (int)((t + lo) - tbr);
+      if (x < 0) x = 0;
+    }
     const int dq = (int)(((unsigned)x * vp.magic16_plen) >> 16);
     const int ph = x - dq * vp.plen;
     const int pos = off * m + bo0 + dq * vp.n + (int)((vp.prefix_nib >> (4 * ph)) & 15ull) - (int)((vp.prefix_nib >> (4 * ph0)) & 15ull);
@@ -467,24 +533,27 @@ __device__ __forceinline__ void v3_decode(const uint8_t *__restrict__ in, uint8_
     for (int i = 0; i < SPL; i++) {
       const unsigned k2 = (kmask >> (2 * i)) & 3u;                  // keep flags of the step's two symbols
       const unsigned idx = (k2 << 2) | (win >> 30);
-      win <<= (k2 - (k2 >> 1));                                    // consume one received bit per kept symbol
+      win <<= __popc(k2);                                          // consume one received bit per kept symbol
       wbuf[dd * (V3_BLK * 8) + ub0 + i] = lut[idx];
     }
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
   };
   // ---- traceback chains of the block that starts at window jp
+  // (a block starts at a multiple of 3 windows, so the phases a chain meets depend on the lane alone)
   V3Trace T;
+  int tph[2];                                                      // phase after the window a chain starts in: (8 jj + 8) % 6 = 2 * ((jj + 1) % 3)
+#pragma unroll
+  for (int c = 0; c < 2; c++) { T.oend[c] = c * 16 + pl < V3_BLK ? ob_end : INT_MIN; tph[c] = 2 * ((c * 16 + pl + 1) % 3); T.oph[c] = 2 * ((c * 16 + pl + 3 * ntb - (ntb - 1)) % 3); }
+  static_assert(V3_BLK % 3 == 0, "phases per lane");
   auto trace_init = [&](int jp) {
 #pragma unroll
     for (int c = 0; c < 2; c++) {
-      int jj = jp + c * 16 + pl;
-      T.ob[c] = b0 + (jj - (warm + ntb - 1));
-      T.ok[c] = (c * 16 + pl < V3_BLK) && dec_active && jj >= warm + ntb - 1 && T.ob[c] < b1 && (MODE != 1 || T.ob[c] >= out_lo);
-      if (!T.ok[c]) jj = jp;                                       // any window inside the ring: result unused
+      const int jj = jp + c * 16 + pl;
+      T.ob[c] = jj - (warm + ntb - 1);
+      T.ok[c] = T.ob[c] >= ob_lo && T.ob[c] < T.oend[c];           // (a chain that is not ok runs all the same, over whatever the ring holds: every read is masked into the ring)
       const int sb = 63 - (bests[dd * V3_RINGW + (jj & (V3_RINGW - 1))] & 63);
-      T.wsh[c] = ((jj << 8) & 0x3f00) | (dd * 64);
-      T.z[c] = v3_z_of_cell(((sb | (sb << 6)) >> ((8 * jj + 8) % 6)) & 63) | T.wsh[c];   // cell = rotr6(state, phase after the window)
-      T.wlast[c] = jj - (ntb - 1);
+      T.wsh[c] = jj * V3_ROW<NW> + rowl;
+      T.z[c] = v3_z_of_cell(((sb | (sb << 6)) >> tph[c]) & 63) | (T.wsh[c] & V3_RMASK<NW>);   // cell = rotr6(state, phase after the window)
     }
   };
 
@@ -505,28 +574,38 @@ __device__ __forceinline__ void v3_decode(const uint8_t *__restrict__ in, uint8_
     const bool tr = jb > 0 && !(V3_EXP & 1);
     if (tr) trace_init(jb - V3_BLK);
     const unsigned *wrow = wbuf + dd * (V3_BLK * 8);
+    unsigned Wa[8], Wb[8];                                         // the step words of the current and of the next window
+    v3_load_words(wrow, Wa);
     if (tr) {
-      v3_fwd_six<true, 0, NTB>(v, L, wrow, tab, bests, jb, dd, pl, T);
-      v3_fwd_six<true, 12, NTB>(v, L, wrow + 48, tab, bests, jb + 6, dd, pl, T);
-      v3_trace_out(T, tab, dd * 64, out, out_lo);
+      v3_fwd_six<true, 0, NTB, NW, true>(v, L, wrow, tab, tabw, bests, jb, dd, pl, T, Wa, Wb);
+      v3_fwd_six<true, 12, NTB, NW, true>(v, L, wrow + 48, tab, tabw, bests, jb + 6, dd, pl, T, Wa, Wb);
+      v3_trace_out(T, tab, outb);
     } else {
-      v3_fwd_six<false, 0, NTB>(v, L, wrow, tab, bests, jb, dd, pl, T);
-      v3_fwd_six<false, 0, NTB>(v, L, wrow + 48, tab, bests, jb + 6, dd, pl, T);
+      v3_fwd_six<false, 0, NTB, NW, true>(v, L, wrow, tab, tabw, bests, jb, dd, pl, T, Wa, Wb);
+      v3_fwd_six<false, 0, NTB, NW, true>(v, L, wrow + 48, tab, tabw, bests, jb + 6, dd, pl, T, Wa, Wb);
     }
-    for (int wi = 12; wi < V3_BLK; wi += 6) v3_fwd_six<false, 0, NTB>(v, L, wrow + wi * 8, tab, bests, jb + wi, dd, pl, T);
+    static_assert(V3_BLK == 24, "the second half of the block is written out: two groups of six windows, straight-line like the first half");
+    v3_fwd_six<false, 0, NTB, NW, true>(v, L, wrow + 96, tab, tabw, bests, jb + 12, dd, pl, T, Wa, Wb);
+    v3_fwd_six<false, 0, NTB, NW, false>(v, L, wrow + 144, tab, tabw, bests, jb + 18, dd, pl, T, Wa, Wb);
   }
   // the last block's calls
   __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
   trace_init(J - V3_BLK);
-  for (int h = 0; h < ntb - 1; h++) v3_hop(T, tab, dd * 64);
-  v3_trace_out(T, tab, dd * 64, out, out_lo);
+  for (int h = 0; h < ntb - 1; h++) v3_hop<NW>(T, tab);
+  v3_trace_out(T, tab, outb);
 }
 
-#define V3_LDS_DECL(NW) \
-  __shared__ __attribute__((aligned(16))) unsigned char tab_[NW][V3_RINGW * 4 * 64];   /* path bytes: [window][decoder][cell z]  (the ppresult ring) */ \
-  __shared__ __attribute__((aligned(16))) unsigned wbuf_[NW][4 * V3_BLK * 8];          /* step words: [decoder][step in block] */ \
-  __shared__ unsigned char bests_[NW][4 * V3_RINGW];                                    /* best state per window */ \
-  __shared__ unsigned lut[16];                                                          /* (keep flags, next two received bits) -> the step word */
+// One object, the ring first: it is the kernel's only LDS variable, so the ring starts at LDS offset 0 and a ring offset IS the ds address (a hop adds no base).  Nothing depends
+// on that for correctness: wherever the object lies, its address is a constant that folds into the ds instructions' offset field.
+template <int NW> struct V3Shared {
+  alignas(16) unsigned char tab[V3_RINGW * V3_ROW<NW>];     // path bytes: [window][wavefront][decoder][cell z]  (the ppresult ring)
+  alignas(16) unsigned wbuf[NW][4 * V3_BLK * 8];            // step words: [wavefront][decoder][step in block]
+  unsigned char bests[NW][4 * V3_RINGW];                    // best state per window
+  unsigned lut[16];                                         // (keep flags, next two received bits) -> the step word
+};
+static_assert(sizeof(V3Shared<4>) <= 81920 && V3_RMASK<4> == 0xffc0 && V3_RMASK<1> == 0x3fc0, "two four-wave workgroups per CU beside the symbol kernel's 76 KB");
+#define V3_LDS_DECL(NW) __shared__ V3Shared<NW> sh_;
+#define V3_LDS(NW, wv) V3Lds{sh_.tab, sh_.wbuf[wv], sh_.bests[wv], sh_.lut, wv}
 
 // MODE 0 / 1 (see v3_decode).  MODE 0: out_lo is also the index of chunk 0's first byte (the block API's former layout); MODE 1: ax.grid0 is, out_lo the first byte that is written.
 template <int NTB, int WARM = V3_WARM, int MODE = 0> __global__ __launch_bounds__(64 * V3_WGW) void viterbi3_kernel(const uint8_t *__restrict__ in, uint8_t *__restrict__ out, const RxState *st,
@@ -534,7 +613,7 @@ template <int NTB, int WARM = V3_WARM, int MODE = 0> __global__ __launch_bounds_
 {
   V3_LDS_DECL(V3_WGW)
   const int wv = V3_WGW > 1 ? (int)(threadIdx.x >> 6) : 0;
-  const V3Lds S = {tab_[wv], wbuf_[wv], bests_[wv], lut};
+  const V3Lds S = V3_LDS(V3_WGW, wv);
   const int lane = threadIdx.x & 63, dd = lane >> 4, pl = lane & 15;
   const long long total_steps = st ? st->n_vit_steps : steps_fixed;
   const long long total_out = total_steps / 8 - vp.ntb;
@@ -547,7 +626,7 @@ template <int NTB, int WARM = V3_WARM, int MODE = 0> __global__ __launch_bounds_
   if (grid0 + chunk0 * B >= total_out) return;                    // whole wavefront idle
   const long long c = chunk0 + dd, b0 = grid0 + c * B;            // this lane's decoder
   const bool dec_active = b0 < total_out;
-  v3_init_lut(lut, lane);
+  v3_init_lut(sh_.lut, lane);
 #if V3_EXP & 16
   const unsigned long long dbg_t0 = wall_clock64();
 #endif
@@ -559,7 +638,7 @@ template <int NTB, int WARM = V3_WARM, int MODE = 0> __global__ __launch_bounds_
     if (c == 0 && ax.carry_in) inject = ax.carry_in + 2 * pl;
     if (ax.carry_out && b0 + B >= total_out) carry = ax.carry_out + 2 * pl;      // the launch's last chunk
   }
-  v3_decode<NTB, WARM, MODE>(in, out, total_steps, total_out, vp, in_base, out_lo, b0, dec_active, S, L, v, endv, own, predn, inject, carry, ax.carry_rel);
+  v3_decode<NTB, WARM, MODE, V3_WGW>(in, out, total_steps, total_out, vp, in_base, out_lo, b0, dec_active, S, L, v, endv, own, predn, inject, carry, ax.carry_rel);
 #if V3_EXP & 16
   if (lane == 0) {
     unsigned id, xcc;
@@ -614,7 +693,7 @@ __device__ __forceinline__ bool v3_row_equal(const int (&a)[2], const int (&b)[2
 }
 
 // The parallel repair pass: one decoder (row) per listed chunk, from pred[c], over that chunk alone.  `rows` decoder rows work through the list, this wavefront's first is row0.
-template <int NTB> __device__ __forceinline__ void v3_repair_rows(const uint8_t *__restrict__ in, uint8_t *__restrict__ out, long long total_steps, const VitParams &vp, const V3Aux &ax,
+template <int NTB, int NW> __device__ __forceinline__ void v3_repair_rows(const uint8_t *__restrict__ in, uint8_t *__restrict__ out, long long total_steps, const VitParams &vp, const V3Aux &ax,
                                                                   long long in_base, long long out_lo, const V3Lds &S, const V3Lane &L, long long rows, long long row0, int n)
 {
   const int lane = threadIdx.x & 63, dd = lane >> 4, pl = lane & 15;
@@ -628,7 +707,7 @@ template <int NTB> __device__ __forceinline__ void v3_repair_rows(const uint8_t 
     int v[2], endv[2] = {0, 0};
     { const int *p = v3_pred(ax, c) + 2 * pl; v[0] = p[0]; v[1] = p[1]; }
     int *carry = (act && ax.carry_out && b0 + B >= total_out) ? ax.carry_out + 2 * pl : nullptr;
-    v3_decode<NTB, 0, 2>(in, out, total_steps, total_out, vp, in_base, out_lo, b0, act && b0 < total_out, S, L, v, endv, v3_own(ax, c) + 2 * pl, nullptr, nullptr, carry, ax.carry_rel);
+    v3_decode<NTB, 0, 2, NW>(in, out, total_steps, total_out, vp, in_base, out_lo, b0, act && b0 < total_out, S, L, v, endv, v3_own(ax, c) + 2 * pl, nullptr, nullptr, carry, ax.carry_rel);
     int pn[2] = {endv[0], endv[1]};
     if (act && c + 1 < nch) { const int *p = v3_pred(ax, c + 1) + 2 * pl; pn[0] = p[0]; pn[1] = p[1]; }
     if (!v3_row_equal(endv, pn, dd) || ((ax.debug & 1) && act && c + 1 < nch)) {   // the repaired decoder does not arrive where the unproven one did: the sequential pass goes on from here
@@ -646,16 +725,16 @@ template <int NTB> __global__ __launch_bounds__(64 * V3_WGW) void viterbi_repair
   const int wv = V3_WGW > 1 ? (int)(threadIdx.x >> 6) : 0;
   const long long rows = (long long)gridDim.x * V3_WGW * 4, row0 = ((long long)blockIdx.x * V3_WGW + wv) * 4;
   if (row0 >= n) return;
-  const V3Lds S = {tab_[wv], wbuf_[wv], bests_[wv], lut};
-  v3_init_lut(lut, threadIdx.x & 63);
+  const V3Lds S = V3_LDS(V3_WGW, wv);
+  v3_init_lut(sh_.lut, threadIdx.x & 63);
   V3Lane L; v3_init_lane(threadIdx.x & 15, L);
-  v3_repair_rows<NTB>(in, out, st ? st->n_vit_steps : steps_fixed, vp, ax, in_base, out_lo, S, L, rows, row0, n);
+  v3_repair_rows<NTB, V3_WGW>(in, out, st ? st->n_vit_steps : steps_fixed, vp, ax, in_base, out_lo, S, L, rows, row0, n);
 }
 
 // The sequential pass: ONE decoder walks the flagged chunks in stream order.  From fix[c] it decodes chunk c; where the state it reaches at chunk c + 1 is own[c + 1] the bytes behind
 // are the streaming decoder's already, otherwise it goes on through chunk c + 1.  force (a test hook, dvbt_rx_params.viterbi_verify = 3: the parallel pass is not launched): every
 // chunk whose own[] is not pred[] is taken, from pred[].  One wavefront, its first row.
-template <int NTB> __device__ __forceinline__ void v3_seq_walk(const uint8_t *__restrict__ in, uint8_t *__restrict__ out, long long total_steps, const VitParams &vp, const V3Aux &ax,
+template <int NTB, int NW> __device__ __forceinline__ void v3_seq_walk(const uint8_t *__restrict__ in, uint8_t *__restrict__ out, long long total_steps, const VitParams &vp, const V3Aux &ax,
                                                                long long in_base, long long out_lo, const V3Lds &S, const V3Lane &L, int force)
 {
   const int lane = threadIdx.x & 63, dd = lane >> 4, pl = lane & 15;
@@ -688,7 +767,7 @@ template <int NTB> __device__ __forceinline__ void v3_seq_walk(const uint8_t *__
       int st0[2] = {v[0], v[1]}, endv[2] = {0, 0};
       if (act) { int *p = v3_pred(ax, c) + 2 * pl; p[0] = v[0]; p[1] = v[1]; }
       int *carry = (act && ax.carry_out && b0 + B >= total_out) ? ax.carry_out + 2 * pl : nullptr;
-      v3_decode<NTB, 0, 2>(in, out, total_steps, total_out, vp, in_base, out_lo, b0, act, S, L, st0, endv, v3_own(ax, c) + 2 * pl, nullptr, nullptr, carry, ax.carry_rel);
+      v3_decode<NTB, 0, 2, NW>(in, out, total_steps, total_out, vp, in_base, out_lo, b0, act, S, L, st0, endv, v3_own(ax, c) + 2 * pl, nullptr, nullptr, carry, ax.carry_rel);
       __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
       done++;
       if (c + 1 >= nch) { pos = nch; break; }
@@ -705,10 +784,10 @@ template <int NTB> __global__ __launch_bounds__(64) void viterbi_repair_seq_kern
                                                       long long steps_fixed, VitParams vp, V3Aux ax, long long in_base, long long out_lo, int force)
 {
   V3_LDS_DECL(1)
-  const V3Lds S = {tab_[0], wbuf_[0], bests_[0], lut};
-  v3_init_lut(lut, threadIdx.x & 63);
+  const V3Lds S = V3_LDS(1, 0);
+  v3_init_lut(sh_.lut, threadIdx.x & 63);
   V3Lane L; v3_init_lane(threadIdx.x & 15, L);
-  v3_seq_walk<NTB>(in, out, st ? st->n_vit_steps : steps_fixed, vp, ax, in_base, out_lo, S, L, force);
+  v3_seq_walk<NTB, 1>(in, out, st ? st->n_vit_steps : steps_fixed, vp, ax, in_base, out_lo, S, L, force);
 }
 
 // Check, parallel repair (16 decoder rows) and sequential pass in ONE launch of one workgroup, for launches of few chunks (V3_FIX_SMALL): the lock periods of a walk, the single
@@ -729,12 +808,12 @@ template <int NTB> __global__ __launch_bounds__(64 * V3_WGW) void viterbi_fix_ke
   }
   __threadfence(); __syncthreads();
   const int n = *(volatile int *)(ax.ctl + V3_CTL_MISMATCH);
-  const V3Lds S = {tab_[wv], wbuf_[wv], bests_[wv], lut};
-  v3_init_lut(lut, threadIdx.x & 63);
+  const V3Lds S = V3_LDS(V3_WGW, wv);
+  v3_init_lut(sh_.lut, threadIdx.x & 63);
   V3Lane L; v3_init_lane(threadIdx.x & 15, L);
-  if (!force && n > 0) v3_repair_rows<NTB>(in, out, total_steps, vp, ax, in_base, out_lo, S, L, 4 * V3_WGW, 4 * wv, n);
+  if (!force && n > 0) v3_repair_rows<NTB, V3_WGW>(in, out, total_steps, vp, ax, in_base, out_lo, S, L, 4 * V3_WGW, 4 * wv, n);
   __threadfence(); __syncthreads();
-  if (wv == 0) v3_seq_walk<NTB>(in, out, total_steps, vp, ax, in_base, out_lo, S, L, force);
+  if (wv == 0) v3_seq_walk<NTB, V3_WGW>(in, out, total_steps, vp, ax, in_base, out_lo, S, L, force);
 }
 
 }  // namespace dvbt
