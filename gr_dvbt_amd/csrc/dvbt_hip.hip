@@ -1542,6 +1542,72 @@ extern "C" int dvbt_debug_peak_detect(const float *lam_host, const float *avg_ho
   return DVBT_OK;
 }
 
+// test hook: viterbi_soft4_kernel alone on host-supplied soft values, at a chunk size, step count and grid the caller chooses (a segment reaches the large chunk
+// sizes and the second pass of the task loop only with tens of megabytes through the decoder).  VitParams as dvbt_rx_create makes them; the state block says
+// first_out = 0, n_vit_steps = total_steps, n_vit_in = n_soft / m.  The whole output buffer is 0xA5 before the launch and comes back whole.  Whatever s4_plan
+// could not have produced is refused before anything is allocated or launched
+extern "C" int dvbt_debug_soft_viterbi(int constellation, int code_rate, const int8_t *soft_host, int64_t n_soft, int64_t total_steps, int B, int nsteps, int grid,
+                                       uint8_t *out_host, size_t out_cap)
+{
+  if (!soft_host || !out_host) return fail(DVBT_ERR_INVALID, "null argument");
+  const Dims d = make_dims(constellation, 0, code_rate, 0, 0);
+  if (!d.valid) return fail(DVBT_ERR_INVALID, "bad DVB-T parameters");
+  if (n_soft < 0 || n_soft % d.m != 0 || n_soft > (1ll << 30)) return fail(DVBT_ERR_INVALID, "n_soft must be a multiple of the constellation's m in [0, 2^30]");
+  if (total_steps < 0 || total_steps > (1ll << 30)) return fail(DVBT_ERR_INVALID, "total_steps must lie in [0, 2^30]");
+  if (B < 64 || B > S4_BMAX) return fail(DVBT_ERR_INVALID, "B must lie in [64, 304]");
+  const int look = 8 * d.ntb > S4_LOOK ? 8 * d.ntb : S4_LOOK;
+  if (nsteps <= 0 || nsteps % S4_BLK != 0 || nsteps > S4_MAXSTEPS || nsteps < S4_WARM + 8 * B + look)
+    return fail(DVBT_ERR_INVALID, "nsteps must be a multiple of 48 in [256 + 8 B + max(8 ntraceback, 128), S4_MAXSTEPS]");
+  if (grid < 1 || grid > S4_GRID) return fail(DVBT_ERR_INVALID, "grid must lie in [1, 2048]");
+  if (out_cap == 0 || out_cap > (1ull << 30) || (long long)out_cap < total_steps / 8) return fail(DVBT_ERR_INVALID, "out_cap must hold total_steps / 8 bytes");
+  int r = need_device(); if (r) return r;
+  const VitParams vp = make_vit_params(d, 768, 768);
+  RxState st; memset(&st, 0, sizeof st);
+  st.first_out = 0; st.n_vit_steps = total_steps; st.n_vit_in = n_soft / d.m;
+  int8_t *dsoft = nullptr; uint8_t *dout = nullptr; RxState *dst = nullptr; unsigned *scratch = nullptr;
+  auto done = [&](int code) { (void)hipFree(dsoft); (void)hipFree(dout); (void)hipFree(dst); (void)hipFree(scratch); return code; };
+#define DBGHIP(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { g_err = std::string(#x) + ": " + hipGetErrorString(e_); return done(DVBT_ERR_HIP); } } while (0)
+  DBGHIP(hipMalloc((void **)&dsoft, (size_t)n_soft + 64)); DBGHIP(hipMalloc((void **)&dout, out_cap)); DBGHIP(hipMalloc((void **)&dst, sizeof(RxState)));
+  DBGHIP(hipMalloc((void **)&scratch, sizeof(unsigned) * (size_t)grid * S4_WAVES * S4_SLOT_WORDS));
+  if (n_soft) DBGHIP(hipMemcpy(dsoft, soft_host, (size_t)n_soft, hipMemcpyHostToDevice));
+  DBGHIP(hipMemcpy(dst, &st, sizeof st, hipMemcpyHostToDevice));
+  DBGHIP(hipMemset(dout, 0xA5, out_cap));
+  hipLaunchKernelGGL(viterbi_soft4_kernel, dim3((unsigned)grid), dim3(64 * S4_WAVES), 0, nullptr, (const int8_t *)dsoft, dout, (const RxState *)dst, vp, scratch, B, nsteps);
+  DBGHIP(hipGetLastError());
+  DBGHIP(hipMemcpy(out_host, dout, out_cap, hipMemcpyDeviceToHost));
+  return done(DVBT_OK);
+}
+
+// test hook: soft_tab_kernel, then soft_demap_kernel, on nsym host-supplied symbols of equalised carriers (cfloat[P]) and channel state (float[P]) with a symbol
+// parity each; the `points` table and inv_step2 are the ones enqueue passes.  out_host: int8[nsym][P m], the soft values behind both inner de-interleavers
+extern "C" int dvbt_debug_soft_demap(int constellation, int mode, const void *eq_host, const float *csi_host, const int32_t *parity_host, int nsym, int8_t *out_host)
+{
+  if (!eq_host || !csi_host || !parity_host || !out_host || nsym <= 0 || nsym > 4096) return fail(DVBT_ERR_INVALID, "null argument, or nsym outside [1, 4096]");
+  const Dims d = make_dims(constellation, 0, 0, 0, mode);
+  if (!d.valid) return fail(DVBT_ERR_INVALID, "bad DVB-T parameters");
+  int r = need_device(); if (r) return r;
+  Tables T; T.d = d;
+  if ((r = T.build_inner(1.0f))) return r;
+  const size_t P = d.payload, n = (size_t)nsym * P;
+  RxState st; memset(&st, 0, sizeof st);
+  st.first_out = 0; st.n_out_symbols = nsym;
+  float2 *deq = nullptr; float *dcsi = nullptr; int *dpar = nullptr; RxState *dst = nullptr; uint16_t *tab = nullptr; int8_t *dout = nullptr;
+  auto done = [&](int code) { (void)hipFree(deq); (void)hipFree(dcsi); (void)hipFree(dpar); (void)hipFree(dst); (void)hipFree(tab); (void)hipFree(dout); return code; };
+  DBGHIP(hipMalloc((void **)&deq, sizeof(float2) * n)); DBGHIP(hipMalloc((void **)&dcsi, sizeof(float) * n)); DBGHIP(hipMalloc((void **)&dpar, sizeof(int) * nsym));
+  DBGHIP(hipMalloc((void **)&dst, sizeof(RxState))); DBGHIP(hipMalloc((void **)&tab, sizeof(uint16_t) * 2 * P * d.m)); DBGHIP(hipMalloc((void **)&dout, n * d.m + 64));
+  DBGHIP(hipMemcpy(deq, eq_host, sizeof(float2) * n, hipMemcpyHostToDevice)); DBGHIP(hipMemcpy(dcsi, csi_host, sizeof(float) * n, hipMemcpyHostToDevice));
+  DBGHIP(hipMemcpy(dpar, parity_host, sizeof(int) * nsym, hipMemcpyHostToDevice)); DBGHIP(hipMemcpy(dst, &st, sizeof st, hipMemcpyHostToDevice));
+  const InnerParams ip = T.inner_params(d.payload);
+  hipLaunchKernelGGL(soft_tab_kernel, dim3(64), dim3(256), 0, nullptr, ip, (const uint16_t *)T.H, (const uint16_t *)T.Hinv, tab);
+  const float step = 2.0f * d.norm;
+  hipLaunchKernelGGL(soft_demap_kernel, dim3((unsigned)nsym), dim3(256), (size_t)d.payload * d.m, nullptr, (const float2 *)deq, (const float *)dcsi, (const RxState *)dst, ip,
+                     (const float2 *)T.points, 1.0f / (step * step), (const int *)dpar, (const uint16_t *)tab, dout);
+  DBGHIP(hipGetLastError());
+  DBGHIP(hipMemcpy(out_host, dout, n * d.m, hipMemcpyDeviceToHost));
+#undef DBGHIP
+  return done(DVBT_OK);
+}
+
 #include "dvbt_stream.inc"
 #include "dvbt_rccl.inc"
 #include "dvbt_blocks.inc"

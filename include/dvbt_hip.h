@@ -792,6 +792,15 @@ int64_t dvbt_debug_descr_follow(const uint8_t *rs, size_t nitems, const int64_t 
  * error-flag slot, sent from the stream's sample buffer).  tests/test_gpu_rccl.py::test_exchange_step_world_2_over_the_loopback_transport */
 int dvbt_rccl_comm_create_loopback(void **group, int rank, int world, int device, dvbt_rccl_comm **out);
 int dvbt_rccl_debug_fail_steps(dvbt_rccl_comm *c, int n);
+/* the soft-input decoder's kernel alone (csrc/k_soft4.hpp) on n_soft host soft values (int8, the decoder's input order; a multiple of the constellation's m): chunk size B,
+ * nsteps steps per decoder and `grid` workgroups as given instead of planned.  out_host[0 .. out_cap) was 0xA5 on the device before the launch; the kernel writes
+ * total_steps / 8 - ntraceback bytes.  DVBT_ERR_INVALID, nothing launched, for what the planner cannot produce: B outside [64, 304], nsteps not a multiple of 48 in
+ * [256 + 8 B + max(8 ntraceback, 128), 2928], grid outside [1, 2048], out_cap < total_steps / 8.  tests/test_gpu_soft_kernels.py */
+int dvbt_debug_soft_viterbi(int constellation, int code_rate, const int8_t *soft_host, int64_t n_soft, int64_t total_steps, int B, int nsteps, int grid,
+                            uint8_t *out_host, size_t out_cap);
+/* the soft demapper's two kernels (csrc/k_soft.hpp: the scatter table of both inner de-interleavers, then the demapper) on nsym host symbols: eq cfloat[nsym][P],
+ * csi float[nsym][P], parity[s] = symbol index & 1; out_host int8[nsym][P m], the soft values in the decoder's input order */
+int dvbt_debug_soft_demap(int constellation, int transmission_mode, const void *eq_host, const float *csi_host, const int32_t *parity_host, int nsym, int8_t *out_host);
 
 #ifdef __cplusplus
 }

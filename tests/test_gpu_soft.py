@@ -176,8 +176,10 @@ def _model_check(po, const, cr, mode, nsf, snr, echoes=(), seed=9, optional=Fals
     return rep
 
 
-@pytest.mark.parametrize("const,cr,mode,nsf,snr", [(g.QAM16, g.C1_2, g.T2k, 4, 10.0), (g.QAM64, g.C7_8, g.T8k, 2, 20.0), (g.QPSK, g.C2_3, g.T8k, 2, 30.0), (g.QAM64, g.C2_3, g.T2k, 4, 17.0)],
-                         ids=["2k QAM16 1/2 at 10 dB (hard path dead)", "8k QAM64 7/8 at 20 dB (hard path dead)", "8k QPSK 2/3 clean", "2k QAM64 2/3 at 17 dB (hard path dead)"])
+@pytest.mark.parametrize("const,cr,mode,nsf,snr", [(g.QAM16, g.C1_2, g.T2k, 4, 10.0), (g.QAM64, g.C7_8, g.T8k, 2, 20.0), (g.QPSK, g.C2_3, g.T8k, 2, 30.0), (g.QAM64, g.C2_3, g.T2k, 4, 17.0),
+                                                   (g.QAM64, g.C5_6, g.T2k, 4, 19.0), (g.QAM16, g.C3_4, g.T2k, 4, 13.0)],
+                         ids=["2k QAM16 1/2 at 10 dB (hard path dead)", "8k QAM64 7/8 at 20 dB (hard path dead)", "8k QPSK 2/3 clean", "2k QAM64 2/3 at 17 dB (hard path dead)",
+                              "2k QAM64 5/6 at 19 dB (hard path dead)", "2k QAM16 3/4 at 13 dB (hard path dead)"])
 def test_soft_values_and_decoded_bytes_equal_the_model(po, const, cr, mode, nsf, snr):
     rep = _model_check(po, const, cr, mode, nsf, snr)
     if snr < 25:
