@@ -38,11 +38,17 @@
 //
 // The instruction budget, as compiled (tools/vit_window_count.py on the device assembly; tests/test_viterbi_isa_budget.py holds it): a window is 77 VALU instructions for
 // its eight steps, 1 for the path-byte word and 12.5 for its end = 90.5, plus its address arithmetic; a traceback hop is 2 per chain (one row back, one v_bfi).  A block of
-// V3_BLK windows of viterbi3_kernel<24, 72, 1> is straight-line code: windows 0-11 with the previous block's 2 x 23 hops 95.7 per window (106.8 before the ring became one
-// array of the workgroup), windows 12-23 87.9 (94.0 as a loop of six), staging, the chains' start and the output of the traceback ~270 per block: 2,472 instructions per
-// block of 24 windows measured (SQ_INSTS_VALU) against 2,727.  Every stamp is one v_and_or_b32 (the lane constants are kept opaque, v3_init_lane).
+// V3_BLK windows of viterbi3_kernel<24, 72, 1> is straight-line code: windows 0-11 with the previous block's 2 x 23 hops, the start of its chains' output and the calls' bytes
+// 97.6 per window (106.8 before the ring became one array of the workgroup; 95.7 while the calls' bytes were assembled behind the block), the other blocks of twelve 91.5 and
+// 87.9 (94.0 as a loop of six), staging and the chains' start ~240 per block (~270 with the output before round 8): 2,458 instructions per block of 24 windows measured
+// (SQ_INSTS_VALU; 2,472 in round 7, 2,727 before it).  Every stamp is one v_and_or_b32 (the lane constants are kept opaque, v3_init_lane).
 // What the count alone did not buy, the order of the LDS reads did: a hop's read and its use stand three and five steps apart (v3_fwd_window), and a window's
-// step words are loaded one window ahead (v3_fwd_six) -- the wavefront, one of two on its SIMD, no longer waits out the LDS latency 70 times per block.
+// step words are loaded one window ahead (v3_fwd_six) -- the wavefront, one of two on its SIMD, no longer waits out the LDS latency 70 times per block.  The same holds around
+// the windows since round 8: staging computes a lane's twelve table indices first, issues the twelve look-ups back to back behind one wait and stores the words as three
+// ds_write_b128 (stage_words); the best states the chains start from are read at the top of the iteration and used behind staging (bests_read / trace_init); the chains' last
+// path bytes are read together in the hop slot behind the last hop and the calls' bytes leave where that hop would be merged, under an exec mask without a branch
+// (v3_trace_read / v3_trace_store): as compiled, two s_waitcnt lgkmcnt(0) between the loop header and the first window (the compacted bits, the first window's step words; the batch of look-ups
+// is met by three partial waits, one per wide store) instead of fifteen, and none on the spot behind the last hop instead of two (tests/test_viterbi_isa_staging.py).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -248,8 +254,8 @@ template <int NW> constexpr int V3_RMASK = (V3_RINGW * V3_ROW<NW> - 1) & ~63;   
 struct V3Trace {
   int z[2];             // current cell: byte offset into the ring = window row | wavefront | decoder | storage index
   int wsh[2];           // ring row of the window whose table is read next (x V3_ROW; counts down past zero: only the bits of V3_RMASK are used) | wavefront << 8 | decoder << 6
-  int oph[2];           // phase at the start of the window a chain ends in: 2 * (window mod 3)
-  bool ok[2];
+  int osh[2];           // (6 - phase at the start of the window a chain ends in) mod 6: the rotation of v3_trace_store, a constant of the lane
+  unsigned long long ok[2];   // the lanes of the wavefront whose chain q ends in a call of the chunk (v3_trace_store's exec mask)
   int oend[2];          // the chunk's end for the calls this chain takes (no call: INT_MIN)
   int ob[2];            // output byte of the call, relative to the chunk's first byte
 };
@@ -271,17 +277,34 @@ template <int NW> __device__ __forceinline__ void v3_hop_merge(V3Trace &T, const
   }
 }
 template <int NW> __device__ __forceinline__ void v3_hop(V3Trace &T, const unsigned char *tab) { unsigned t[2]; v3_hop_read(T, tab, t); v3_hop_merge<NW>(T, t); }
-// the decoded byte of a call: (state at the start of the last window of the chain) << 2 | its two oldest inputs.
-// outb = where the chunk's first byte goes
-__device__ __forceinline__ void v3_trace_out(const V3Trace &T, const unsigned char *tab, uint8_t *outb)
+// the decoded byte of a call: (state at the start of the last window of the chain) << 2 | its two oldest inputs.  The read of the chain's last path byte and its use are separate
+// (v3_hop_read / v3_hop_merge likewise): the forward pass issues both chains' reads together behind the last hop and assembles the bytes a window or more later.
+__device__ __forceinline__ void v3_trace_read(const V3Trace &T, const unsigned char *tab, unsigned (&t)[2])
+{
+#pragma unroll
+  for (int q = 0; q < 2; q++) t[q] = tab[T.z[q]];
+}
+// outb = where the chunk's first byte goes.  The cell of storage index z is rotr6(z ^ 12 * (bit 4 of z), 2) (v3_cell_of_z) and the window starts at phase oph = (8w) % 6, so the
+// state << 2 is the doubled six bits shifted by osh = (6 - oph) % 6 -- seven instructions per chain, none of them under the store's exec mask
+template <bool MASKED> __device__ __forceinline__ void v3_trace_store(const V3Trace &T, const unsigned (&t)[2], uint8_t *outb)
 {
 #pragma unroll
   for (int q = 0; q < 2; q++) {
-    const unsigned t = tab[T.z[q]];
-    const int sstart = rotl6(v3_cell_of_z((int)(t & 63u)), T.oph[q]);                   // phase of window w = (8w) % 6
-    if (T.ok[q]) outb[T.ob[q]] = (unsigned char)((sstart << 2) | (t >> 6));
+    const unsigned zz = (t[q] ^ (((t[q] >> 4) & 1u) * 12u)) & 63u;
+    unsigned by = (((zz | (zz << 6)) >> T.osh[q]) & 0xfcu) | (t[q] >> 6);
+    if (MASKED) {
+      // the store under the lanes' ok as exec mask, without a branch: around a conditional store the compiler keeps an s_cbranch_execz, and the twelve windows would no
+      // longer be one basic block for the scheduler (and for tools/vit_window_count.py).  What this relies on: T.ok[q] is a ballot taken with all 64 lanes live, in wave-uniform
+      // control flow (trace_init), and so is this place -- exec is all ones on entry and the group puts back what it found; the group is the only user of exec here (the compiler
+      // sees one opaque instruction, nothing can be scheduled into it).  The compiler does not count the store in its vmcnt bookkeeping: an uncounted store in flight can only make
+      // a later s_waitcnt vmcnt(N) wait longer, never shorter, and nothing reads the byte back.  The "memory" clobber keeps the store in source order against the kernel's other
+      // memory operations; it is a scheduling barrier at the two places per block where a store stands (the end of window 11 for ntraceback 24).
+      unsigned long long sv;
+      asm volatile("s_and_saveexec_b64 %0, %1\n\tglobal_store_byte %2, %3, off\n\ts_mov_b64 exec, %0" : "=&s"(sv) : "s"(T.ok[q]), "v"(outb + T.ob[q]), "v"(by) : "memory", "scc");
+    } else if ((T.ok[q] >> (threadIdx.x & 63)) & 1) outb[T.ob[q]] = (unsigned char)by;
   }
 }
+__device__ __forceinline__ void v3_trace_out(const V3Trace &T, const unsigned char *tab, uint8_t *outb) { unsigned t[2]; v3_trace_read(T, tab, t); v3_trace_store<false>(T, t, outb); }
 
 // window j0 + V6 of a decoder (j0 % 6 == 0): it starts at phase (8 V6) % 6 = 0,2,4,0,2,4; the minimum is subtracted
 // after every second window.  HOPS: two traceback hops of the previous block's calls ride along (their LDS latency
@@ -296,14 +319,18 @@ __device__ __forceinline__ void v3_load_words(const unsigned *wp_, unsigned (&W)
 }
 // tabw = the ring at this lane's word of a row (wavefront, decoder, 4 x lane in row)
 // W = the window's eight step words, already in registers; PREF: the next window's (they follow in wrow) are loaded into Wn at the start of this one, a window ahead of their use
+// The read of the chains' last path byte takes the slot of the hop that would follow the last one (FINA / FINB), and the calls' bytes are assembled and written where that hop
+// would be merged, three or five steps later (outb: v3_trace_store)
 template <int V6, bool HOPS, int HOP0, int NTB, int NW, bool PREF> __device__ __forceinline__ void v3_fwd_window(int (&v)[2], const V3Lane &L, const unsigned *wrow, unsigned char *tab, unsigned char *tabw,
-                                                                                           unsigned char *bests, int j0, int dd, int pl, V3Trace &T, unsigned (&W)[8], unsigned (&Wn)[8])
+                                                                                           unsigned char *bests, int j0, int dd, int pl, V3Trace &T, unsigned (&W)[8], unsigned (&Wn)[8], uint8_t *outb)
 {
   // a window's two hops are dependent LDS reads: the first is issued here and used behind the window's 3rd step, where the second is issued, which is used behind the last step
   // (the compiler keeps the source order: written as read + use in one place they end up 1 to 5 instructions apart, and the wavefront waits out the LDS latency 46 times a block)
   constexpr bool HOPA = HOPS && HOP0 + 2 * V6 < NTB - 1, HOPB = HOPS && HOP0 + 2 * V6 + 1 < NTB - 1;
-  unsigned th[2];
+  constexpr bool FINA = HOPS && HOP0 + 2 * V6 == NTB - 1, FINB = HOPS && HOP0 + 2 * V6 + 1 == NTB - 1;
+  unsigned th[2], tout[2];
   if (HOPA) v3_hop_read(T, tab, th);
+  if (FINA) v3_trace_read(T, tab, tout);
   const int jr = (j0 + V6) & (V3_RINGW - 1);
 #if V3_EXP & 256
   for (int i = 0; i < 8; i++) { W[i] = (unsigned)(j0 * 0x01010101 + i * 0x00020406 + pl); asm volatile("" : "+v"(W[i])); }   // no LDS read in the loop
@@ -320,9 +347,12 @@ template <int V6, bool HOPS, int HOP0, int NTB, int NW, bool PREF> __device__ __
 #endif
   v3_step<(P0 + 0) % 6, 0>(v, W[0], L, raw); V3_YIELD(); v3_step<(P0 + 1) % 6, 0>(v, W[1], L, raw); V3_YIELD(); v3_step<(P0 + 2) % 6, 3>(v, W[2], L, raw); V3_YIELD();
   if (HOPA) { v3_hop_merge<NW>(T, th); if (HOPB) v3_hop_read(T, tab, th); }
+  if (FINB) v3_trace_read(T, tab, tout);
+  if (FINA) v3_trace_store<true>(T, tout, outb);
   v3_step<(P0 + 3) % 6, 0>(v, W[3], L, raw); V3_YIELD(); v3_step<(P0 + 4) % 6, 0>(v, W[4], L, raw); V3_YIELD(); v3_step<(P0 + 5) % 6, 1>(v, W[5], L, raw); V3_YIELD();
   v3_step<(P0 + 6) % 6, 4>(v, W[6], L, raw); V3_YIELD(); v3_step<(P0 + 7) % 6, 2>(v, W[7], L, raw);
   if (HOPB) v3_hop_merge<NW>(T, th);
+  if (FINB) v3_trace_store<true>(T, tout, outb);
   // the four path bytes of this lane's cells = one word of the table (storage index z = 4*lane + 2r + h)
   if (!(V3_EXP & 4)) *reinterpret_cast<unsigned *>(tabw + jr * V3_ROW<NW>) = __builtin_amdgcn_perm((unsigned)raw[1], (unsigned)raw[0], 0x06040200u);
   if (V3_EXP & 2) { if (raw[0] == 0x12345) bests[jr] = 1; return; }
@@ -331,11 +361,11 @@ template <int V6, bool HOPS, int HOP0, int NTB, int NW, bool PREF> __device__ __
 }
 // six windows; Wa arrives with the first window's step words and leaves with those of the window behind the six (MORE: there is one in this block)
 template <bool HOPS, int HOP0, int NTB, int NW, bool MORE> __device__ __forceinline__ void v3_fwd_six(int (&v)[2], const V3Lane &L, const unsigned *wrow, unsigned char *tab, unsigned char *tabw,
-                                                                                  unsigned char *bests, int j0, int dd, int pl, V3Trace &T, unsigned (&Wa)[8], unsigned (&Wb)[8])
+                                                                                  unsigned char *bests, int j0, int dd, int pl, V3Trace &T, unsigned (&Wa)[8], unsigned (&Wb)[8], uint8_t *outb)
 {
-  v3_fwd_window<0, HOPS, HOP0, NTB, NW, true>(v, L, wrow, tab, tabw, bests, j0, dd, pl, T, Wa, Wb); v3_fwd_window<1, HOPS, HOP0, NTB, NW, true>(v, L, wrow, tab, tabw, bests, j0, dd, pl, T, Wb, Wa);
-  v3_fwd_window<2, HOPS, HOP0, NTB, NW, true>(v, L, wrow, tab, tabw, bests, j0, dd, pl, T, Wa, Wb); v3_fwd_window<3, HOPS, HOP0, NTB, NW, true>(v, L, wrow, tab, tabw, bests, j0, dd, pl, T, Wb, Wa);
-  v3_fwd_window<4, HOPS, HOP0, NTB, NW, true>(v, L, wrow, tab, tabw, bests, j0, dd, pl, T, Wa, Wb); v3_fwd_window<5, HOPS, HOP0, NTB, NW, MORE>(v, L, wrow, tab, tabw, bests, j0, dd, pl, T, Wb, Wa);
+  v3_fwd_window<0, HOPS, HOP0, NTB, NW, true>(v, L, wrow, tab, tabw, bests, j0, dd, pl, T, Wa, Wb, outb); v3_fwd_window<1, HOPS, HOP0, NTB, NW, true>(v, L, wrow, tab, tabw, bests, j0, dd, pl, T, Wb, Wa, outb);
+  v3_fwd_window<2, HOPS, HOP0, NTB, NW, true>(v, L, wrow, tab, tabw, bests, j0, dd, pl, T, Wa, Wb, outb); v3_fwd_window<3, HOPS, HOP0, NTB, NW, true>(v, L, wrow, tab, tabw, bests, j0, dd, pl, T, Wb, Wa, outb);
+  v3_fwd_window<4, HOPS, HOP0, NTB, NW, true>(v, L, wrow, tab, tabw, bests, j0, dd, pl, T, Wa, Wb, outb); v3_fwd_window<5, HOPS, HOP0, NTB, NW, MORE>(v, L, wrow, tab, tabw, bests, j0, dd, pl, T, Wb, Wa, outb);
 }
 
 // A chunk = vp.chunk_bytes decoded bytes; it is decoded by an independent decoder that starts `warm` windows early
@@ -457,22 +487,25 @@ __device__ __forceinline__ void v3_decode(const uint8_t *__restrict__ in, uint8_
   // ---- staging, first half: where block jb starts in the input (row-uniform) and the load of its bytes.  The blocks are staged in order: behind a block whose step 0 is a real
   // step the position advances by BLKBITS depunctured bits -- ph0, the byte and bo0 are carried with small integers; the 64-bit locate runs for a decoder's first block, and for
   // the blocks of a decoder that starts before the stream does (the clamp below), in which case the whole wavefront takes it.
-  int ph0 = 0, bo0 = 0, off = 0; long long byte0 = 0; uint4 q = make_uint4(0, 0, 0, 0);
+  // pfx(ph) = received bits of a period before its phase ph (VitParams.prefix): the kept symbols below ph -- one v_bfe + v_bcnt where the nibble table takes a 64-bit shift
+  auto pfx = [&](int ph) { return (int)__popc(vp.punct_mask & ((1u << ph) - 1u)); };
+  int ph0 = 0, pf0 = 0, bo0 = 0, off = 0; long long byte0 = 0; uint4 q = make_uint4(0, 0, 0, 0);   // pf0 = pfx(ph0), carried with it
   auto stage_load = [&](int jb) {
     const long long tb = tb0 + (long long)jb * 8;                  // real step index of block step 0 (may be < 0)
     if (jb > 0 && jb - V3_BLK >= u_first) {                         // (the block before starts at a real step in all four decoders)
-      const int pf0 = (int)((vp.prefix_nib >> (4 * ph0)) & 15ull);
+      const int pf_old = pf0;
       ph0 += inc_ph;
       const int wrap = ph0 >= vp.plen ? 1 : 0;
       ph0 -= wrap ? vp.plen : 0;
-      const int r = bo0 + (inc_q + wrap) * vp.n + (int)((vp.prefix_nib >> (4 * ph0)) & 15ull) - pf0;   // received bits from the old byte's first bit (0 <= r < 1024)
+      pf0 = pfx(ph0);
+      const int r = bo0 + (inc_q + wrap) * vp.n + pf0 - pf_old;       // received bits from the old byte's first bit (0 <= r < 1024)
       const int dby = (int)(((unsigned)r * magic16_m) >> 16);
       bo0 = r - dby * m; byte0 += dby;
     } else {
       const unsigned long long pbit = 2ull * (unsigned long long)(tb > 0 ? tb : 0);
       const unsigned long long pq = __umul64hi(pbit, vp.magic_plen);
-      ph0 = (int)(pbit - pq * (unsigned)vp.plen);
-      const unsigned long long rb = pq * (unsigned)vp.n + ((vp.prefix_nib >> (4 * ph0)) & 15ull);
+      ph0 = (int)(pbit - pq * (unsigned)vp.plen); pf0 = pfx(ph0);
+      const unsigned long long rb = pq * (unsigned)vp.n + (unsigned)pf0;
       const unsigned long long by = __umul64hi(rb, vp.magic_m);
       byte0 = (long long)by; bo0 = (int)(rb - by * (unsigned)m);
     }
@@ -524,38 +557,58 @@ __device__ __forceinline__ void v3_decode(const uint8_t *__restrict__ in, uint8_
     }
     const int dq = (int)(((unsigned)x * vp.magic16_plen) >> 16);
     const int ph = x - dq * vp.plen;
-    const int pos = off * m + bo0 + dq * vp.n + (int)((vp.prefix_nib >> (4 * ph)) & 15ull) - (int)((vp.prefix_nib >> (4 * ph0)) & 15ull);
+    const int pos = off * m + bo0 + dq * vp.n + pfx(ph) - pf0;
     const unsigned kmask = ((unsigned)(vp.punct_rep >> ph) << (2 * lo)) & (((1u << (2 * hi)) - 1u) & ~((1u << (2 * lo)) - 1u));
     const unsigned *cb = cbits + dd * V3_CBS;
     const unsigned cw0 = cb[pos >> 5], cw1 = cb[(pos >> 5) + 1];
     unsigned win = (unsigned)(((((unsigned long long)cw0) << 32) | cw1) >> (32 - (pos & 31)));
+    // the twelve table indices first (one VALU chain on win), then the twelve look-ups back to back behind ONE wait, then the lane's 48 bytes as three 16-byte stores.  Written as
+    // look-up + store per step, the compiler keeps that order (the table and the step words are members of one LDS object) and the wavefront waits out twelve LDS round trips in a row
+    unsigned idx[SPL], sw[SPL];
 #pragma unroll
     for (int i = 0; i < SPL; i++) {
       const unsigned k2 = (kmask >> (2 * i)) & 3u;                  // keep flags of the step's two symbols
-      const unsigned idx = (k2 << 2) | (win >> 30);
+      idx[i] = (k2 << 2) | (win >> 30);
       win <<= __popc(k2);                                          // consume one received bit per kept symbol
-      wbuf[dd * (V3_BLK * 8) + ub0 + i] = lut[idx];
     }
+#pragma unroll
+    for (int i = 0; i < SPL; i++) sw[i] = lut[idx[i]];
+    static_assert(SPL % 4 == 0, "a lane's step words are whole 16-byte groups (its offset dd * 768 + pl * 48 bytes is 16-byte aligned)");
+    uint4 *const wdst = reinterpret_cast<uint4 *>(wbuf + dd * (V3_BLK * 8) + ub0);
+#pragma unroll
+    for (int i = 0; i < SPL / 4; i++) wdst[i] = make_uint4(sw[4 * i], sw[4 * i + 1], sw[4 * i + 2], sw[4 * i + 3]);
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
   };
   // ---- traceback chains of the block that starts at window jp
   // (a block starts at a multiple of 3 windows, so the phases a chain meets depend on the lane alone)
+  // The bit shuffles between a state and a cell's storage index depend, beside the path byte, on the lane alone: z(cell) = rotl6(cell, 2) ^ 12 * (cell bit 2) (v3_z_of_cell) and
+  // cell = rotr6(state, phase), so z = R ^ 12 * (R bit 4) with R = rotl6(state, 2 - phase) -- one shift by a constant of the lane (tsh, osh: computed once per kernel)
   V3Trace T;
-  int tph[2];                                                      // phase after the window a chain starts in: (8 jj + 8) % 6 = 2 * ((jj + 1) % 3)
+  int tsh[2];                                                      // (phase after the window a chain starts in + 4) % 6, that phase = (8 jj + 8) % 6 = 2 * ((jj + 1) % 3)
 #pragma unroll
-  for (int c = 0; c < 2; c++) { T.oend[c] = c * 16 + pl < V3_BLK ? ob_end : INT_MIN; tph[c] = 2 * ((c * 16 + pl + 1) % 3); T.oph[c] = 2 * ((c * 16 + pl + 3 * ntb - (ntb - 1)) % 3); }
+  for (int c = 0; c < 2; c++) {
+    T.oend[c] = c * 16 + pl < V3_BLK ? ob_end : INT_MIN; tsh[c] = (2 * ((c * 16 + pl + 1) % 3) + 4) % 6; T.osh[c] = (6 - 2 * ((c * 16 + pl + 3 * ntb - (ntb - 1)) % 3)) % 6;
+  }
   static_assert(V3_BLK % 3 == 0, "phases per lane");
-  auto trace_init = [&](int jp) {
+  // the best states the chains of the block at window jp start from.  The block is complete when it ends: the reads are issued at the top of the next iteration, ahead of
+  // staging, and used behind it (trace_init) -- their round trip hides under the staging arithmetic
+  auto bests_read = [&](int jp, unsigned (&bb)[2]) {
+#pragma unroll
+    for (int c = 0; c < 2; c++) bb[c] = bests[dd * V3_RINGW + ((jp + c * 16 + pl) & (V3_RINGW - 1))];
+  };
+  auto trace_init = [&](int jp, const unsigned (&bb)[2]) {
 #pragma unroll
     for (int c = 0; c < 2; c++) {
       const int jj = jp + c * 16 + pl;
       T.ob[c] = jj - (warm + ntb - 1);
-      T.ok[c] = T.ob[c] >= ob_lo && T.ob[c] < T.oend[c];           // (a chain that is not ok runs all the same, over whatever the ring holds: every read is masked into the ring)
-      const int sb = 63 - (bests[dd * V3_RINGW + (jj & (V3_RINGW - 1))] & 63);
+      T.ok[c] = __builtin_amdgcn_ballot_w64(T.ob[c] >= ob_lo && T.ob[c] < T.oend[c]);          // (a chain that is not ok runs all the same, over whatever the ring holds: every read is masked into the ring)
       T.wsh[c] = jj * V3_ROW<NW> + rowl;
-      T.z[c] = v3_z_of_cell(((sb | (sb << 6)) >> tph[c]) & 63) | (T.wsh[c] & V3_RMASK<NW>);   // cell = rotr6(state, phase after the window)
+      // bb = 63 - best state = ~state in six bits: R = rotl6(bb, .) ^ 63, and 63 ^ 12 * (1 - bit) = 51 ^ 12 * bit
+      const unsigned R = (bb[c] | (bb[c] << 6)) >> tsh[c];
+      T.z[c] = (int)((R ^ 51u ^ (((R >> 4) & 1u) * 12u)) & 63u) | (T.wsh[c] & V3_RMASK<NW>);
     }
   };
+  unsigned bb[2];
 
   stage_load(0);
   for (int jb = 0; jb < J; jb += V3_BLK) {
@@ -569,28 +622,30 @@ __device__ __forceinline__ void v3_decode(const uint8_t *__restrict__ in, uint8_
       if (jb == B) { endv[0] = v[0]; endv[1] = v[1]; }
       if (carry && dec_active && jb == carry_rel) { carry[0] = v[0]; carry[1] = v[1]; }
     }
+    bests_read(jb - V3_BLK, bb);                                   // (block 0: whatever the ring holds, unused)
     if (!(V3_EXP & 8) || jb == 0) stage_words(jb);
     if (jb + V3_BLK < J && !(V3_EXP & 8)) stage_load(jb + V3_BLK);                  // the bytes of the next block travel during this block's forward pass
     const bool tr = jb > 0 && !(V3_EXP & 1);
-    if (tr) trace_init(jb - V3_BLK);
+    if (tr) trace_init(jb - V3_BLK, bb);
     const unsigned *wrow = wbuf + dd * (V3_BLK * 8);
     unsigned Wa[8], Wb[8];                                         // the step words of the current and of the next window
     v3_load_words(wrow, Wa);
     if (tr) {
-      v3_fwd_six<true, 0, NTB, NW, true>(v, L, wrow, tab, tabw, bests, jb, dd, pl, T, Wa, Wb);
-      v3_fwd_six<true, 12, NTB, NW, true>(v, L, wrow + 48, tab, tabw, bests, jb + 6, dd, pl, T, Wa, Wb);
-      v3_trace_out(T, tab, outb);
+      v3_fwd_six<true, 0, NTB, NW, true>(v, L, wrow, tab, tabw, bests, jb, dd, pl, T, Wa, Wb, outb);
+      v3_fwd_six<true, 12, NTB, NW, true>(v, L, wrow + 48, tab, tabw, bests, jb + 6, dd, pl, T, Wa, Wb, outb);
     } else {
-      v3_fwd_six<false, 0, NTB, NW, true>(v, L, wrow, tab, tabw, bests, jb, dd, pl, T, Wa, Wb);
-      v3_fwd_six<false, 0, NTB, NW, true>(v, L, wrow + 48, tab, tabw, bests, jb + 6, dd, pl, T, Wa, Wb);
+      v3_fwd_six<false, 0, NTB, NW, true>(v, L, wrow, tab, tabw, bests, jb, dd, pl, T, Wa, Wb, outb);
+      v3_fwd_six<false, 0, NTB, NW, true>(v, L, wrow + 48, tab, tabw, bests, jb + 6, dd, pl, T, Wa, Wb, outb);
     }
     static_assert(V3_BLK == 24, "the second half of the block is written out: two groups of six windows, straight-line like the first half");
-    v3_fwd_six<false, 0, NTB, NW, true>(v, L, wrow + 96, tab, tabw, bests, jb + 12, dd, pl, T, Wa, Wb);
-    v3_fwd_six<false, 0, NTB, NW, false>(v, L, wrow + 144, tab, tabw, bests, jb + 18, dd, pl, T, Wa, Wb);
+    static_assert(NTB - 1 < 24, "the chains' last read takes a hop slot of the first twelve windows");
+    v3_fwd_six<false, 0, NTB, NW, true>(v, L, wrow + 96, tab, tabw, bests, jb + 12, dd, pl, T, Wa, Wb, outb);
+    v3_fwd_six<false, 0, NTB, NW, false>(v, L, wrow + 144, tab, tabw, bests, jb + 18, dd, pl, T, Wa, Wb, outb);
   }
   // the last block's calls
   __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-  trace_init(J - V3_BLK);
+  bests_read(J - V3_BLK, bb);
+  trace_init(J - V3_BLK, bb);
   for (int h = 0; h < ntb - 1; h++) v3_hop<NW>(T, tab);
   v3_trace_out(T, tab, outb);
 }
