@@ -420,7 +420,7 @@ extern "C" int dvbt_rx_create(const dvbt_rx_params *p, dvbt_rx **out)
   h->prm = *p; h->d = d; h->T.d = d;
   // capacity of the chain proper, in samples at the OFDM elementary rate
   size_t chain_max = p->max_samples;
-  if (p->resample_interp > 0 || p->resample_decim > 0) {
+  if (p->resample_interp != 0 || p->resample_decim != 0) {   // 0,0 alone means no resampler: a negative pair is refused by build(), not taken for none
     int r2 = h->rsd.build(p->resample_interp, p->resample_decim); if (r2) { delete h; return r2; }
     chain_max = (size_t)(((unsigned long long)p->max_samples * h->rsd.ri + h->rsd.rd - 1) / h->rsd.rd);
   }

@@ -170,3 +170,80 @@ def coded_symbols(po, c, nbytes, ber, seed, m=None):
     for j in range(m):
         sym |= kept[j:nsym * m:m] << (m - 1 - j)
     return data, sym
+
+
+# ---------------------------------------------------------------- rational resampler + multiply_const (k_resample.hpp), float64
+RS_MAX_BRANCH_FLOATS = 64 * 48     # k_resample.hpp: floats of the branch table a workgroup stages (ri * nt must fit)
+RS_TILE_IN = 768                   # k_resample.hpp: input samples a workgroup of 256 outputs stages
+
+
+def resampler_design64(interp, decim):
+    """rational_resampler(interp, decim, taps=None, fractional_bw=None) of the GNU Radio 3.7 series, as the header comment of resampler_taps
+    (dvbt_tables.hpp) names it, in float64 throughout: interp / decim reduced by their gcd; fractional_bw 0.4; design_filter = firdes.low_pass(gain
+    ri, fs ri, mid, width, Kaiser beta 7) with width = 0.1 and mid = 0.45 for a rate >= 1, both times the rate below; compute_ntaps =
+    int((beta / 0.1102 + 8.7) fs / (22 width)) made odd; low_pass = sin(n w0) / (n pi) under the Kaiser window, w0 = 2 pi mid / fs, normalised to
+    the gain at DC.  Returns (taps, ri, rd, nt): the prototype, the reduced ratio and the taps per polyphase branch, ceil(len(taps) / ri)."""
+    g = int(np.gcd(interp, decim))
+    ri, rd = interp // g, decim // g
+    fractional_bw, beta, halfband = 0.4, 7.0, 0.5
+    rate = ri / rd
+    if rate >= 1.0:
+        width = halfband - fractional_bw
+        mid = halfband - width / 2.0
+    else:
+        width = rate * (halfband - fractional_bw)
+        mid = rate * halfband - width / 2.0
+    fs = float(ri)
+    ntaps = int((beta / 0.1102 + 8.7) * fs / (22.0 * width))
+    ntaps += 1 - (ntaps & 1)
+    n = np.arange(ntaps, dtype=np.float64) - (ntaps - 1) // 2
+    taps = 2.0 * mid / fs * np.sinc(2.0 * mid / fs * n) * np.kaiser(ntaps, beta)
+    taps *= ri / taps.sum()
+    return taps, ri, rd, (ntaps + ri - 1) // ri
+
+
+def resampler_supported(ri, rd, nt):
+    """the support rule of ResamplerDesign::build (dvbt_hip.hip): the branch table and the input tile of one workgroup fit their LDS arrays"""
+    return ri * nt <= RS_MAX_BRANCH_FLOATS and 256 * rd // ri + nt + 2 <= RS_TILE_IN
+
+
+def resample64(x, taps, ri, rd, scale):
+    """out[M] = scale * sum_k branch[(M rd) mod ri][k] * x[floor(M rd / ri) - k], branch[b][k] = taps[b + k ri] (0 past the end), x = 0 outside
+    [0, len), M = 0 .. ceil(len ri / rd) - 1, in complex128.  Returns (out, A_re, A_im): A_re[M] = |scale| sum_k |branch[..][k]| |Re x[..]|, the
+    sum of the magnitudes of what out[M].real adds up (the scale of its rounding error), A_im likewise.
+    Every branch at every input position as one matrix product over the windows x[n - nt + 1 .. n], of which each output picks its own."""
+    x = np.asarray(x).astype(np.complex128)
+    taps = np.asarray(taps, np.float64)
+    nt = (len(taps) + ri - 1) // ri
+    br = np.zeros(ri * nt)
+    br[:len(taps)] = taps
+    br = br.reshape(nt, ri).T                                  # br[b][k] = taps[b + k ri]
+    nout = (len(x) * ri + rd - 1) // rd
+    M = np.arange(nout, dtype=np.int64)
+    n_of, b_of = M * rd // ri, M * rd % ri                     # n_of < len(x)
+    flipped = np.ascontiguousarray(br[:, ::-1].T)              # window column j holds x[n - (nt - 1 - j)]
+
+    def every_branch(v, t):
+        w = np.ascontiguousarray(np.lib.stride_tricks.sliding_window_view(np.concatenate([np.zeros(nt - 1), v]), nt))
+        return (w @ t)[n_of, b_of]
+    out = every_branch(x.real, flipped) + 1j * every_branch(x.imag, flipped)
+    a_re, a_im = every_branch(np.abs(x.real), np.abs(flipped)), every_branch(np.abs(x.imag), np.abs(flipped))
+    return out * scale, a_re * abs(scale), a_im * abs(scale)
+
+
+def resample_bound(a, nt):
+    """how far a float32 evaluation of resample64 may lie from it, per output and component: nt products and nt - 1 additions in any order, fused or
+    not, each rounding by at most 2^-24 of a partial sum that the magnitude sum a bounds (first order: nt 2^-24 a), one more rounding for the scale,
+    one of margin for the higher-order terms; 2^-149 for a result flushed to zero"""
+    return (nt + 2) * 2.0 ** -24 * a + 2.0 ** -149
+
+
+def resampler_call_count(ri, rd, produced, consumed, nout, nin):
+    """what a work() call must produce, from the block's contract alone: output M can be produced once input floor(M rd / ri) has been offered.
+    `produced` outputs exist and `consumed` inputs were taken by earlier calls, so this call offers the inputs below consumed + nin; the outputs
+    M >= produced whose newest input floor(M rd / ri) lies below that are those with M rd < (consumed + nin) ri"""
+    if nout <= 0 or nin <= 0:
+        return 0
+    offered = consumed + nin
+    ready = (offered * ri - 1) // rd + 1 - produced            # M = produced .. (offered ri - 1) // rd
+    return max(0, min(nout, ready))
