@@ -8,20 +8,19 @@
 
 namespace {
 
-struct PinBuf {           // growable pinned host staging
-  void *p = nullptr; size_t cap = 0;
-  int reserve(size_t n) { if (n <= cap) return DVBT_OK; if (p) (void)hipHostFree(p); p = nullptr; cap = 0; HIPCHK(hipHostMalloc(&p, n + 64)); cap = n; return DVBT_OK; }
-  ~PinBuf() { if (p) (void)hipHostFree(p); }
+struct PinBuf {           // growable pinned host staging (mem owns, p views: as DevBuf)
+  PinMem<uint8_t> mem; void *p = nullptr; size_t cap = 0;
+  int reserve(size_t n) { if (n <= cap) return DVBT_OK; p = nullptr; cap = 0; HIPCHK(mem.alloc(n + 64)); p = mem; cap = n; return DVBT_OK; }
 };
 // The host-pointer entries (dvbt_<blk>_work) move their items through PINNED staging buffers of the handle: memcpy + asynchronous H2D in, asynchronous D2H +
 // memcpy out behind the call's one synchronisation.  A copy straight from / to the caller's pageable buffer makes the runtime pin and unpin those pages on
 // every call (GNU Radio's buffers move through a circular mapping: never the same address twice in a row): 8-20 GB/s effective against ~50 for pinned memory,
 // and the copies of the ten blocks' threads serialise inside the runtime.
 struct BlockCtx {
-  hipStream_t s = nullptr; DevBuf din, dout, aux; PinBuf pin_in, pin_out;
+  Stream s; DevBuf din, dout, aux; PinBuf pin_in, pin_out;   // (s first: released after the buffers its copies use)
   struct Pending { void *host; size_t off, bytes; };
   std::vector<Pending> pending; size_t pin_in_used = 0, pin_out_used = 0;
-  int init() { int r = need_device(); if (r) return r; HIPCHK(hipStreamCreate(&s)); return DVBT_OK; }
+  int init() { int r = need_device(); if (r) return r; HIPCHK(s.create()); return DVBT_OK; }
   // a caller's buffer that is page-locked already (dvbt_host_register, or hipHostMalloc'd by the host) needs no staging: the DMA engines read / write it directly
   static bool is_pinned(const void *host)
   {
@@ -68,7 +67,6 @@ struct BlockCtx {
   // history + new input made contiguous in din for a _work_device call: device-to-device on the caller's stream
   int put_dev(DevBuf &b, const void *dev, size_t bytes, size_t offset, hipStream_t st)
   { int r = b.reserve_keep(offset + bytes, offset, st); if (r) return r; if (bytes) HIPCHK(hipMemcpyAsync((char *)b.p + offset, dev, bytes, hipMemcpyDeviceToDevice, st)); return DVBT_OK; }
-  ~BlockCtx() { if (s) (void)hipStreamDestroy(s); }
 };
 // NULL = the device's default stream: blocks chained without an explicit stream are ordered on it
 inline hipStream_t pick(void *stream, const BlockCtx &) { return (hipStream_t)stream; }
@@ -93,10 +91,9 @@ inline void sb_begin(dvbt_sideband *sb) { if (sb) { sb->n_out_tags = 0; sb->n_co
 
 }  // namespace
 
-#define BLK_CREATE_PROLOGUE(T) if (!p || !out) return fail(DVBT_ERR_INVALID, "null argument"); T *h = new T(); { int r_ = h->c.init(); if (r_) { delete h; return r_; } }
-#define BLK_FAIL(code, msg) do { delete h; return fail(code, msg); } while (0)
-#define BLK_CHK(x) do { int r_ = (x); if (r_) { delete h; return r_; } } while (0)
 #define WCHK(x) do { int r_ = (x); if (r_) return r_; } while (0)
+// the handle lives in `hold` until the create function hands it out (*out = hold.release()): every early return releases what has been built
+#define BLK_CREATE_PROLOGUE(T) if (!p || !out) return fail(DVBT_ERR_INVALID, "null argument"); std::unique_ptr<T> hold(new T()); T *const h = hold.get(); WCHK(h->c.init())
 
 // ============================================================================ A2 fft
 struct dvbt_fft { dvbt_fft_params p; BlockCtx c; Tables T; };
@@ -106,10 +103,10 @@ extern "C" int dvbt_fft_create(const dvbt_fft_params *p, dvbt_fft **out)
   h->p = *p;
   int N = p->fft_size;
   // forward: the RX flowgraphs' fft_vxx(forward, shift=True); forward = 0: the TX flowgraphs' fft_vxx(reverse, shift=True) (k_tx.hpp)
-  if (!p->shift || N < 64 || N > 8192 || (N & (N - 1))) BLK_FAIL(DVBT_ERR_INVALID, "only shifted, power-of-two sizes 64..8192 (the configuration of the RX and TX flowgraphs)");
-  BLK_CHK(h->T.build_fft(N));
-  BLK_CHK(set_lds(p->forward ? (const void *)fft_items_kernel : (const void *)ifft_items_kernel, (size_t)(N + N / 32 + N / 128 + 129) * 8));
-  *out = h; return DVBT_OK;
+  if (!p->shift || N < 64 || N > 8192 || (N & (N - 1))) return fail(DVBT_ERR_INVALID, "only shifted, power-of-two sizes 64..8192 (the configuration of the RX and TX flowgraphs)");
+  WCHK(h->T.build_fft(N));
+  WCHK(set_lds(p->forward ? (const void *)fft_items_kernel : (const void *)ifft_items_kernel, (size_t)(N + N / 32 + N / 128 + 129) * 8));
+  *out = hold.release(); return DVBT_OK;
 }
 extern "C" int dvbt_fft_forecast(const dvbt_fft *, int n, int *req) { if (req) *req = n; return DVBT_OK; }
 static void fft_run(dvbt_fft *h, int n, const void *din, void *dout, hipStream_t s)
@@ -152,10 +149,10 @@ extern "C" int dvbt_demap_create(const dvbt_demap_params *p, dvbt_demap **out)
   BLK_CREATE_PROLOGUE(dvbt_demap);
   h->p = *p;
   h->T.d = make_dims(p->constellation, p->hierarchy, 0, 0, p->transmission_mode);
-  if (!h->T.d.valid || p->nsize <= 0 || p->nsize > 49152) BLK_FAIL(DVBT_ERR_INVALID, "bad demap parameters");
-  BLK_CHK(h->T.build_inner(p->gain));
-  BLK_CHK(set_lds((const void *)inner_kernel<1>, inner_lds_bytes((size_t)p->nsize)));
-  *out = h; return DVBT_OK;
+  if (!h->T.d.valid || p->nsize <= 0 || p->nsize > 49152) return fail(DVBT_ERR_INVALID, "bad demap parameters");
+  WCHK(h->T.build_inner(p->gain));
+  WCHK(set_lds((const void *)inner_kernel<1>, inner_lds_bytes((size_t)p->nsize)));
+  *out = hold.release(); return DVBT_OK;
 }
 extern "C" int dvbt_demap_forecast(const dvbt_demap *, int n, int *req) { if (req) *req = n; return DVBT_OK; }
 static void demap_run(dvbt_demap *h, int n, const void *din, void *dout, hipStream_t s)
@@ -196,9 +193,9 @@ extern "C" int dvbt_symbol_inner_interleaver_create(const dvbt_symbol_inner_inte
   BLK_CREATE_PROLOGUE(dvbt_symbol_inner_interleaver);
   h->p = *p;
   h->T.d = make_dims(1, 0, 0, 0, p->transmission_mode);
-  if (!h->T.d.valid || p->nsize != h->T.d.payload) BLK_FAIL(DVBT_ERR_INVALID, "nsize must equal the payload length of the transmission mode (reference assert, symbol_inner_interleaver_impl.cc:125)");
-  BLK_CHK(h->T.build_inner(1.0f));
-  *out = h; return DVBT_OK;
+  if (!h->T.d.valid || p->nsize != h->T.d.payload) return fail(DVBT_ERR_INVALID, "nsize must equal the payload length of the transmission mode (reference assert, symbol_inner_interleaver_impl.cc:125)");
+  WCHK(h->T.build_inner(1.0f));
+  *out = hold.release(); return DVBT_OK;
 }
 extern "C" int dvbt_symbol_inner_interleaver_forecast(const dvbt_symbol_inner_interleaver *, int n, int *req) { if (req) *req = n; return DVBT_OK; }
 // the items' symbol indices (tags on RX, a counter on TX) into h->idx; the table travels to the device ahead of the kernel
@@ -261,9 +258,9 @@ extern "C" int dvbt_bit_inner_deinterleaver_create(const dvbt_bit_inner_deinterl
   BLK_CREATE_PROLOGUE(dvbt_bit_inner_deinterleaver);
   h->p = *p;
   h->d = make_dims(p->constellation, p->hierarchy, 0, 0, p->transmission_mode);
-  if (!h->d.valid || p->nsize <= 0 || p->nsize % 126 || p->nsize > 49152) BLK_FAIL(DVBT_ERR_INVALID, "nsize must be a positive multiple of 126");
-  if (p->hierarchy != DVBT_NH && h->d.m == 2) BLK_FAIL(DVBT_ERR_INVALID, "hierarchical QPSK does not exist (the reference's constructor divides by d_v - 2 = 0)");
-  *out = h; return DVBT_OK;
+  if (!h->d.valid || p->nsize <= 0 || p->nsize % 126 || p->nsize > 49152) return fail(DVBT_ERR_INVALID, "nsize must be a positive multiple of 126");
+  if (p->hierarchy != DVBT_NH && h->d.m == 2) return fail(DVBT_ERR_INVALID, "hierarchical QPSK does not exist (the reference's constructor divides by d_v - 2 = 0)");
+  *out = hold.release(); return DVBT_OK;
 }
 extern "C" int dvbt_bit_inner_deinterleaver_forecast(const dvbt_bit_inner_deinterleaver *, int n, int *req) { if (req) *req = n; return DVBT_OK; }
 static void bit_run(dvbt_bit_inner_deinterleaver *h, int n, const void *din, void *dout, hipStream_t s, void *dout_lp = nullptr)
@@ -331,8 +328,7 @@ struct dvbt_viterbi_decoder {
   dvbt_viterbi_decoder_params p; BlockCtx c; Dims d; VitParams vp;
   size_t hist = 0; long long in_total = 0, steps = 0; int d_init = 0;      // hist: bytes of consumed input kept at the front of din
   static constexpr size_t kTail = 8192;
-  VitProof proof; int *carry = nullptr; int cur = 0; bool have_carry = false; long long grid0 = 0;   // carry: 2 x 32 words (ping-pong), [cur] = the state at byte grid0
-  ~dvbt_viterbi_decoder() { if (carry) (void)hipFree(carry); }
+  VitProof proof; DevMem<int> carry; int cur = 0; bool have_carry = false; long long grid0 = 0;   // carry: 2 x 32 words (ping-pong), [cur] = the state at byte grid0
 };
 extern "C" int dvbt_viterbi_decoder_create(const dvbt_viterbi_decoder_params *p, dvbt_viterbi_decoder **out)
 {
@@ -340,11 +336,11 @@ extern "C" int dvbt_viterbi_decoder_create(const dvbt_viterbi_decoder_params *p,
   h->p = *p;
   h->d = make_dims(p->constellation, p->hierarchy, p->code_rate, 0, 0);
   if (!h->d.valid || p->bsize <= 0 || (2 * h->d.k * p->bsize) % 16 || (p->bsize * h->d.n) % h->d.m || (p->bsize * h->d.k) % 8)
-    BLK_FAIL(DVBT_ERR_INVALID, "bsize must make bsize*n/m and bsize*k/8 integral and 2*k*bsize a multiple of 16");
+    return fail(DVBT_ERR_INVALID, "bsize must make bsize*n/m and bsize*k/8 integral and 2*k*bsize a multiple of 16");
   h->vp = make_vit_params(h->d, p->bsize, 11 * V3_BLK);          // chunks of 264 bytes: a whole number of blocks of windows (the proof's condition)
-  if (hipMalloc((void **)&h->carry, 2 * V3_SLOT * sizeof(int)) != hipSuccess) BLK_FAIL(DVBT_ERR_HIP, "hipMalloc (viterbi_decoder carry)");
-  BLK_CHK(h->proof.reserve(256));
-  *out = h; return DVBT_OK;
+  if (h->carry.alloc(2 * V3_SLOT) != hipSuccess) return fail(DVBT_ERR_HIP, "hipMalloc (viterbi_decoder carry)");
+  WCHK(h->proof.reserve(256));
+  *out = hold.release(); return DVBT_OK;
 }
 extern "C" int dvbt_viterbi_decoder_forecast(const dvbt_viterbi_decoder *h, int n, int *req)
 { if (!h || !req) return DVBT_ERR_INVALID; *req = n * 8 * h->d.n / (h->d.k * h->d.m); return DVBT_OK; }   // viterbi_decoder_impl.cc:181-189
@@ -440,8 +436,8 @@ extern "C" int dvbt_convolutional_deinterleaver_create(const dvbt_convolutional_
 {
   BLK_CREATE_PROLOGUE(dvbt_convolutional_deinterleaver);
   h->p = *p;
-  if (p->I != 12 || p->M != 17 || p->blocks != 136) BLK_FAIL(DVBT_ERR_INVALID, "only the DVB-T outer interleaver I=12, M=17, blocks=136 (every RX flowgraph; assert at convolutional_deinterleaver_impl.cc:68)");
-  *out = h; return DVBT_OK;
+  if (p->I != 12 || p->M != 17 || p->blocks != 136) return fail(DVBT_ERR_INVALID, "only the DVB-T outer interleaver I=12, M=17, blocks=136 (every RX flowgraph; assert at convolutional_deinterleaver_impl.cc:68)");
+  *out = hold.release(); return DVBT_OK;
 }
 extern "C" int dvbt_convolutional_deinterleaver_forecast(const dvbt_convolutional_deinterleaver *h, int n, int *req)
 { if (!h || !req) return DVBT_ERR_INVALID; *req = n * h->p.I * h->p.blocks; return DVBT_OK; }
@@ -488,16 +484,16 @@ extern "C" int dvbt_convolutional_deinterleaver_work_device(dvbt_convolutional_d
 extern "C" void dvbt_convolutional_deinterleaver_destroy(dvbt_convolutional_deinterleaver *h) { delete h; }
 
 // ============================================================================ A9 reed_solomon_dec
-struct dvbt_reed_solomon_dec { dvbt_reed_solomon_dec_params p; BlockCtx c; Tables T; int *cnt = nullptr; ~dvbt_reed_solomon_dec() { if (cnt) (void)hipFree(cnt); } };
+struct dvbt_reed_solomon_dec { dvbt_reed_solomon_dec_params p; BlockCtx c; Tables T; DevMem<int> cnt; };
 extern "C" int dvbt_reed_solomon_dec_create(const dvbt_reed_solomon_dec_params *p, dvbt_reed_solomon_dec **out)
 {
   BLK_CREATE_PROLOGUE(dvbt_reed_solomon_dec);
   h->p = *p;
   if (p->p != 2 || p->m != 8 || p->gfpoly != 0x11d || p->n != 255 || p->k != 239 || p->t != 8 || p->s != 51 || p->blocks <= 0)
-    BLK_FAIL(DVBT_ERR_INVALID, "only RS(255,239,t=8) over GF(2^8)/0x11d shortened by 51 (the DVB-T outer code)");
-  BLK_CHK(h->T.build_rs());
-  if (hipMalloc((void **)&h->cnt, 8) != hipSuccess || hipMemset(h->cnt, 0, 8) != hipSuccess) BLK_FAIL(DVBT_ERR_HIP, "hipMalloc");
-  *out = h; return DVBT_OK;
+    return fail(DVBT_ERR_INVALID, "only RS(255,239,t=8) over GF(2^8)/0x11d shortened by 51 (the DVB-T outer code)");
+  WCHK(h->T.build_rs());
+  if (h->cnt.alloc(2) != hipSuccess || hipMemset(h->cnt, 0, 8) != hipSuccess) return fail(DVBT_ERR_HIP, "hipMalloc");
+  *out = hold.release(); return DVBT_OK;
 }
 extern "C" int dvbt_reed_solomon_dec_forecast(const dvbt_reed_solomon_dec *, int n, int *req) { if (req) *req = n; return DVBT_OK; }
 static void rs_run(dvbt_reed_solomon_dec *h, long long words, const void *din, void *dout, hipStream_t s)
@@ -529,13 +525,13 @@ extern "C" int dvbt_reed_solomon_dec_work_device(dvbt_reed_solomon_dec *h, int n
 extern "C" void dvbt_reed_solomon_dec_destroy(dvbt_reed_solomon_dec *h) { delete h; }
 
 // ============================================================================ next row: energy_descramble
-struct dvbt_energy_descramble { dvbt_energy_descramble_params p; BlockCtx c; Tables T; int d_index = 0; RxState *dstate = nullptr; unsigned ring = 0; ~dvbt_energy_descramble() { if (dstate) (void)hipFree(dstate); } };
+struct dvbt_energy_descramble { dvbt_energy_descramble_params p; BlockCtx c; Tables T; int d_index = 0; DevMem<RxState> dstate; unsigned ring = 0; };
 extern "C" int dvbt_energy_descramble_create(const dvbt_energy_descramble_params *p, dvbt_energy_descramble **out)
 {
   BLK_CREATE_PROLOGUE(dvbt_energy_descramble);
   h->p = *p;
-  BLK_CHK(h->T.build_rs());
-  *out = h; return DVBT_OK;
+  WCHK(h->T.build_rs());
+  *out = hold.release(); return DVBT_OK;
 }
 extern "C" int dvbt_energy_descramble_forecast(const dvbt_energy_descramble *, int n, int *req) { if (req) *req = 4 * (n / 1504); return DVBT_OK; }   // :101-105
 static int descramble_call(dvbt_energy_descramble *h, int nout, int nin, const void *in, void *out, dvbt_sideband *sb, bool dev, hipStream_t s)
@@ -556,7 +552,7 @@ static int descramble_call(dvbt_energy_descramble *h, int nout, int nin, const v
   const uint8_t *src = (const uint8_t *)in + h->d_index;
   if (!dev) { WCHK(h->c.put(h->c.din, src, nbytes)); WCHK(h->c.dout.reserve(nbytes)); }
   if (!h->dstate) {
-    HIPCHK(hipMalloc((void **)&h->dstate, sizeof(RxState) * 64));
+    HIPCHK(h->dstate.alloc(64));
   }
   RxState st; memset(&st, 0, sizeof st); st.n_ts_bytes = (long long)nbytes;
   RxState *slot = h->dstate + (h->ring++ & 63);                   // a slot per call in flight
@@ -585,8 +581,8 @@ extern "C" int dvbt_resampler_create(const dvbt_resampler_params *p, dvbt_resamp
 {
   BLK_CREATE_PROLOGUE(dvbt_resampler);
   h->p = *p;
-  BLK_CHK(h->D.build(p->interpolation, p->decimation));
-  *out = h; return DVBT_OK;
+  WCHK(h->D.build(p->interpolation, p->decimation));
+  *out = hold.release(); return DVBT_OK;
 }
 extern "C" int dvbt_resampler_forecast(const dvbt_resampler *h, int n, int *req)
 { // rational_resampler_base::forecast: max(1, noutput * decimation / interpolation + history() - 1)
@@ -651,9 +647,8 @@ extern "C" void dvbt_resampler_destroy(dvbt_resampler *h) { delete h; }
 // ============================================================================ A3 demod_reference_signals
 struct dvbt_demod_reference_signals {
   dvbt_demod_reference_signals_params p; BlockCtx c; Tables T; FrontParams fp;
-  DevBuf eq, tpsval, info, maj, symidx, flags, syncf; TpsState *ts = nullptr; float2 *prev_tps = nullptr; bool have_prev = false, locked = false;
+  DevBuf eq, tpsval, info, maj, symidx, flags, syncf; DevMem<TpsState> ts; DevMem<float2> prev_tps; bool have_prev = false, locked = false;
   std::vector<int> h_flags, h_symidx; std::vector<unsigned char> h_sync;
-  ~dvbt_demod_reference_signals() { if (ts) (void)hipFree(ts); if (prev_tps) (void)hipFree(prev_tps); }
 };
 extern "C" int dvbt_demod_reference_signals_create(const dvbt_demod_reference_signals_params *p, dvbt_demod_reference_signals **out)
 {
@@ -661,12 +656,12 @@ extern "C" int dvbt_demod_reference_signals_create(const dvbt_demod_reference_si
   h->p = *p;
   h->T.d = make_dims(p->constellation, p->hierarchy, p->code_rate_hp, p->guard_interval, p->transmission_mode);
   const Dims &d = h->T.d;
-  if (!d.valid || p->itemsize != 8 || p->ninput != d.N || p->noutput != d.payload) BLK_FAIL(DVBT_ERR_INVALID, "itemsize must be 8 (gr_complex), ninput the FFT length, noutput the payload length");
-  BLK_CHK(h->T.build_front());
+  if (!d.valid || p->itemsize != 8 || p->ninput != d.N || p->noutput != d.payload) return fail(DVBT_ERR_INVALID, "itemsize must be 8 (gr_complex), ninput the FFT length, noutput the payload length");
+  WCHK(h->T.build_front());
   h->fp = make_front_params(d, 30.0f);
-  if (hipMalloc((void **)&h->ts, sizeof(TpsState)) != hipSuccess || hipMalloc((void **)&h->prev_tps, sizeof(float2) * d.n_tps) != hipSuccess) BLK_FAIL(DVBT_ERR_HIP, "hipMalloc");
-  if (hipMemset(h->ts, 0, sizeof(TpsState)) != hipSuccess || hipMemset(h->prev_tps, 0, sizeof(float2) * d.n_tps) != hipSuccess) BLK_FAIL(DVBT_ERR_HIP, "hipMemset");
-  *out = h; return DVBT_OK;
+  if (h->ts.alloc(1) != hipSuccess || h->prev_tps.alloc(d.n_tps) != hipSuccess) return fail(DVBT_ERR_HIP, "hipMalloc");
+  if (hipMemset(h->ts, 0, sizeof(TpsState)) != hipSuccess || hipMemset(h->prev_tps, 0, sizeof(float2) * d.n_tps) != hipSuccess) return fail(DVBT_ERR_HIP, "hipMemset");
+  *out = hold.release(); return DVBT_OK;
 }
 extern "C" int dvbt_demod_reference_signals_forecast(const dvbt_demod_reference_signals *, int n, int *req) { if (req) *req = n + 1; return DVBT_OK; }   // needs the next item too (:88-94)
 static int demod_call(dvbt_demod_reference_signals *h, int nout, int nin, const void *in, void *out, dvbt_sideband *sb, bool dev, hipStream_t s)
@@ -738,23 +733,21 @@ extern "C" void dvbt_demod_reference_signals_destroy(dvbt_demod_reference_signal
 // ============================================================================ A1 ofdm_sym_acquisition
 struct dvbt_ofdm_sym_acquisition {
   dvbt_ofdm_sym_acquisition_params p; BlockCtx c; FrontParams fp; DevBuf g_init, l_init, g_trk, l_trk, meta, outb, centre, drift, drift_flags;
-  RxState *st = nullptr, *st_host = nullptr; AcqState *as = nullptr, *as_host = nullptr; bool acquired = false;
-  ~dvbt_ofdm_sym_acquisition() { if (st) (void)hipFree(st); if (as) (void)hipFree(as); if (st_host) (void)hipHostFree(st_host); if (as_host) (void)hipHostFree(as_host); }
+  DevMem<RxState> st; PinMem<RxState> st_host; DevMem<AcqState> as; PinMem<AcqState> as_host; bool acquired = false;
 };
 extern "C" int dvbt_ofdm_sym_acquisition_create(const dvbt_ofdm_sym_acquisition_params *p, dvbt_ofdm_sym_acquisition **out)
 {
   BLK_CREATE_PROLOGUE(dvbt_ofdm_sym_acquisition);
   h->p = *p;
   int N = p->fft_length, cp = p->cp_length;
-  if (p->blocks != 1 || N < 64 || N > 8192 || (N & (N - 1)) || cp <= 0 || cp > N) BLK_FAIL(DVBT_ERR_INVALID, "blocks must be 1, fft_length a power of two <= 8192");
+  if (p->blocks != 1 || N < 64 || N > 8192 || (N & (N - 1)) || cp <= 0 || cp > N) return fail(DVBT_ERR_INVALID, "blocks must be 1, fft_length a power of two <= 8192");
   Dims d; d.N = N; d.cp = cp;
   h->fp = make_front_params(d, p->snr);
   h->fp.N = N; h->fp.cp = cp;
-  if (hipMalloc((void **)&h->st, sizeof(RxState)) != hipSuccess || hipMalloc((void **)&h->as, sizeof(AcqState)) != hipSuccess ||
-      hipHostMalloc((void **)&h->st_host, sizeof(RxState)) != hipSuccess || hipHostMalloc((void **)&h->as_host, sizeof(AcqState)) != hipSuccess) BLK_FAIL(DVBT_ERR_HIP, "hipMalloc");
-  if (hipMemset(h->st, 0, sizeof(RxState)) != hipSuccess || hipMemset(h->as, 0, sizeof(AcqState)) != hipSuccess) BLK_FAIL(DVBT_ERR_HIP, "hipMemset");
-  BLK_CHK(set_lds((const void *)derot_fft_kernel, (size_t)(N + N / 32 + N / 128 + 128) * 8));
-  *out = h; return DVBT_OK;
+  if (h->st.alloc(1) != hipSuccess || h->as.alloc(1) != hipSuccess || h->st_host.alloc(1) != hipSuccess || h->as_host.alloc(1) != hipSuccess) return fail(DVBT_ERR_HIP, "hipMalloc");
+  if (hipMemset(h->st, 0, sizeof(RxState)) != hipSuccess || hipMemset(h->as, 0, sizeof(AcqState)) != hipSuccess) return fail(DVBT_ERR_HIP, "hipMemset");
+  WCHK(set_lds((const void *)derot_fft_kernel, (size_t)(N + N / 32 + N / 128 + 128) * 8));
+  *out = hold.release(); return DVBT_OK;
 }
 // the tracking window may look 8 (+margin) samples past 2N+cp: ask for 16 more than the reference (:474-481)
 extern "C" int dvbt_ofdm_sym_acquisition_forecast(const dvbt_ofdm_sym_acquisition *h, int n, int *req)

@@ -10,7 +10,9 @@
 #include <map>
 #include <deque>
 #include <algorithm>
+#include <memory>
 #include "../../include/dvbt_hip.h"
+#include "hip_own.hpp"
 #include "dvbt_tables.hpp"
 #include "ts_ring.hpp"
 #include "k_frontend.hpp"
@@ -25,6 +27,7 @@
 #include "k_txblocks.hpp"
 
 using namespace dvbt;
+using hip_own::DevMem; using hip_own::PinMem; using hip_own::Stream; using hip_own::Event;
 
 static thread_local std::string g_err;
 static int fail(int code, const std::string &msg) { g_err = msg; return code; }
@@ -64,40 +67,39 @@ extern "C" int dvbt_get_dims(int constellation, int hierarchy, int code_rate, in
 }
 
 // ------------------------------------------------------------------------------------------ helpers
-template <class T> static int upload(const std::vector<T> &v, T **dptr)
+template <class T> static int upload(const std::vector<T> &v, DevMem<T> &d)
 {
-  HIPCHK(hipMalloc((void **)dptr, v.size() * sizeof(T) + 16));
-  HIPCHK(hipMemcpy(*dptr, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
+  HIPCHK(d.alloc(v.size() + 16));
+  HIPCHK(hipMemcpy(d, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
   return DVBT_OK;
 }
 
-struct DevBuf {          // growable device scratch
-  void *p = nullptr; size_t cap = 0;
-  int reserve(size_t n) { if (n <= cap) return DVBT_OK; if (p) (void)hipFree(p); p = nullptr; cap = 0; HIPCHK(hipMalloc(&p, n + 64)); cap = n; return DVBT_OK; }
+struct DevBuf {          // growable device scratch: `mem` owns it, `p` is what the blocks read it through (one buffer holds whatever type the call needs)
+  DevMem<uint8_t> mem; void *p = nullptr; size_t cap = 0;
+  int reserve(size_t n) { if (n <= cap) return DVBT_OK; p = nullptr; cap = 0; HIPCHK(mem.alloc(n + 64)); p = mem; cap = n; return DVBT_OK; }
   // grow and keep the first `keep` bytes (a block's history at the front of its input buffer).  The history was written by copies queued on
   // the call's stream `st` (the *_work_device entries never synchronise), so the move is queued on the same stream, and the old buffer is
   // released only after that stream has drained (growth happens a handful of times in a handle's life)
   int reserve_keep(size_t n, size_t keep, hipStream_t st)
   {
     if (n <= cap) return DVBT_OK;
-    void *q = nullptr; HIPCHK(hipMalloc(&q, n + 64));
+    DevMem<uint8_t> q; HIPCHK(q.alloc(n + 64));
     if (p && keep) HIPCHK(hipMemcpyAsync(q, p, keep, hipMemcpyDeviceToDevice, st));
-    if (p) { HIPCHK(hipStreamSynchronize(st)); (void)hipFree(p); }
-    p = q; cap = n; return DVBT_OK;
+    if (p) HIPCHK(hipStreamSynchronize(st));
+    mem = std::move(q); p = mem; cap = n; return DVBT_OK;
   }
-  ~DevBuf() { if (p) (void)hipFree(p); }
 };
 
 struct Tables {          // device lookup tables for one configuration
   Dims d;
-  float2 *tw = nullptr; uint16_t *perm = nullptr;
-  int16_t *cpilot = nullptr, *tps = nullptr; float *known = nullptr, *pref = nullptr;
-  uint16_t *pay_c = nullptr, *pay_L = nullptr, *pay_R = nullptr, *tps_L = nullptr, *tps_R = nullptr;
-  uint16_t *pil_k = nullptr, *pay_Li = nullptr, *pay_Ri = nullptr, *tps_Li = nullptr, *tps_Ri = nullptr; uint8_t *pay_d = nullptr, *tps_d = nullptr; int np[4] = {0, 0, 0, 0};
-  uint16_t *tps_bch = nullptr;               // [7][256]: the TPS word's BCH check as a bytewise table (tps_bch_table_host)
-  uint32_t *pay_pack = nullptr;              // [4][payload]: carrier | rank of the left estimation carrier << 13 | distance to it << 23 (one word per payload carrier)
-  uint16_t *H = nullptr, *Hinv = nullptr; float2 *points = nullptr; uint8_t *label_tab = nullptr; int nlev = 0; float inv_step = 0.f, guard = 0.f, hshift = 0.f;
-  uint8_t *mul_alpha = nullptr, *gexp = nullptr, *glog = nullptr, *prbs = nullptr;
+  DevMem<float2> tw; DevMem<uint16_t> perm;
+  DevMem<int16_t> cpilot, tps; DevMem<float> known, pref;
+  DevMem<uint16_t> pay_c, pay_L, pay_R, tps_L, tps_R;
+  DevMem<uint16_t> pil_k, pay_Li, pay_Ri, tps_Li, tps_Ri; DevMem<uint8_t> pay_d, tps_d; int np[4] = {0, 0, 0, 0};
+  DevMem<uint16_t> tps_bch;                  // [7][256]: the TPS word's BCH check as a bytewise table (tps_bch_table_host)
+  DevMem<uint32_t> pay_pack;                 // [4][payload]: carrier | rank of the left estimation carrier << 13 | distance to it << 23 (one word per payload carrier)
+  DevMem<uint16_t> H, Hinv; DevMem<float2> points; DevMem<uint8_t> label_tab; int nlev = 0; float inv_step = 0.f, guard = 0.f, hshift = 0.f;
+  DevMem<uint8_t> mul_alpha, gexp, glog, prbs;
   bool front = false, inner = false, rs = false;
 
   int build_fft(int N)
@@ -105,8 +107,8 @@ struct Tables {          // device lookup tables for one configuration
     std::vector<float> tw_h = fft_twiddles(N);
     std::vector<float2> t2(N);
     for (int i = 0; i < N; i++) t2[i] = make_float2(tw_h[2 * i], tw_h[2 * i + 1]);
-    int r = upload(t2, &tw); if (r) return r;
-    return upload(fft_out_perm(N), &perm);
+    int r = upload(t2, tw); if (r) return r;
+    return upload(fft_out_perm(N), perm);
   }
   int build_front()
   {
@@ -115,7 +117,7 @@ struct Tables {          // device lookup tables for one configuration
     std::vector<float> pr = pilot_ref_table(d), kn(d.n_cp - 1);
     for (int i = 0; i + 1 < d.n_cp; i++) { float df = pr[c[i + 1]] - pr[c[i]]; kn[i] = df * df; }
     int r;
-    if ((r = upload(c16, &cpilot)) || (r = upload(t16, &tps)) || (r = upload(pr, &pref)) || (r = upload(kn, &known))) return r;
+    if ((r = upload(c16, cpilot)) || (r = upload(t16, tps)) || (r = upload(pr, pref)) || (r = upload(kn, known))) return r;
     std::vector<uint16_t> pc, pl, prr, tl, trr, pk((size_t)4 * DEMOD_NP, 0), pli, pri, tli, tri;
     std::vector<uint8_t> pd, td;
     std::vector<uint32_t> pp;
@@ -134,10 +136,10 @@ struct Tables {          // device lookup tables for one configuration
       prr.insert(prr.end(), pt.pay_R.begin(), pt.pay_R.end()); tl.insert(tl.end(), pt.tps_L.begin(), pt.tps_L.end());
       trr.insert(trr.end(), pt.tps_R.begin(), pt.tps_R.end());
     }
-    if ((r = upload(pc, &pay_c)) || (r = upload(pl, &pay_L)) || (r = upload(prr, &pay_R)) || (r = upload(tl, &tps_L)) || (r = upload(trr, &tps_R))) return r;
-    if ((r = upload(pk, &pil_k)) || (r = upload(pli, &pay_Li)) || (r = upload(pri, &pay_Ri)) || (r = upload(pd, &pay_d)) || (r = upload(tli, &tps_Li)) ||
-        (r = upload(tri, &tps_Ri)) || (r = upload(td, &tps_d)) || (r = upload(pp, &pay_pack))) return r;
-    if ((r = upload(tps_bch_table_host(), &tps_bch))) return r;
+    if ((r = upload(pc, pay_c)) || (r = upload(pl, pay_L)) || (r = upload(prr, pay_R)) || (r = upload(tl, tps_L)) || (r = upload(trr, tps_R))) return r;
+    if ((r = upload(pk, pil_k)) || (r = upload(pli, pay_Li)) || (r = upload(pri, pay_Ri)) || (r = upload(pd, pay_d)) || (r = upload(tli, tps_Li)) ||
+        (r = upload(tri, tps_Ri)) || (r = upload(td, tps_d)) || (r = upload(pp, pay_pack))) return r;
+    if ((r = upload(tps_bch_table_host(), tps_bch))) return r;
     front = true;
     return DVBT_OK;
   }
@@ -147,7 +149,7 @@ struct Tables {          // device lookup tables for one configuration
     if (!H) {
       std::vector<uint16_t> h = symbol_H(d), hi(h.size());
       for (size_t q = 0; q < h.size(); q++) hi[h[q]] = (uint16_t)q;
-      if ((r = upload(h, &H)) || (r = upload(hi, &Hinv))) return r;
+      if ((r = upload(h, H)) || (r = upload(hi, Hinv))) return r;
     }
     std::vector<float> p = constellation_points(d, gain);
     std::vector<float2> p2(64, make_float2(0.f, 0.f));
@@ -170,9 +172,7 @@ struct Tables {          // device lookup tables for one configuration
       }
       if (ok) { nlev = n; inv_step = 1.0f / step; guard = 1.0e4f * step; hshift = sh; }
     }
-    if (points) { (void)hipFree(points); points = nullptr; }
-    if (label_tab) { (void)hipFree(label_tab); label_tab = nullptr; }
-    if ((r = upload(p2, &points)) || (r = upload(lab, &label_tab))) return r;
+    if ((r = upload(p2, points)) || (r = upload(lab, label_tab))) return r;
     inner = true;
     return DVBT_OK;
   }
@@ -183,7 +183,7 @@ struct Tables {          // device lookup tables for one configuration
     std::vector<uint8_t> ex(512), lg(256), mul = rs_division_table();
     gf_tables(ex.data(), lg.data());
     int r;
-    if ((r = upload(ex, &gexp)) || (r = upload(lg, &glog)) || (r = upload(mul, &mul_alpha)) || (r = upload(energy_prbs(), &prbs))) return r;
+    if ((r = upload(ex, gexp)) || (r = upload(lg, glog)) || (r = upload(mul, mul_alpha)) || (r = upload(energy_prbs(), prbs))) return r;
     rs = true;
     return DVBT_OK;
   }
@@ -192,29 +192,22 @@ struct Tables {          // device lookup tables for one configuration
     T.pil_k = pil_k; for (int i = 0; i < 4; i++) T.np[i] = np[i];
     T.pay_Li = pay_Li; T.pay_Ri = pay_Ri; T.pay_d = pay_d; T.tps_Li = tps_Li; T.tps_Ri = tps_Ri; T.tps_d = tps_d; T.pay_pack = pay_pack; return T; }
   RsTables rs_tables() const { RsTables T; T.div_tab = mul_alpha; T.gexp = gexp; T.glog = glog; return T; }
-  ~Tables()
-  {
-    void *all[] = {tw, perm, cpilot, tps, known, pref, pay_c, pay_L, pay_R, tps_L, tps_R, pil_k, pay_Li, pay_Ri, pay_d, tps_Li, tps_Ri, tps_d, pay_pack, tps_bch, H, Hinv, points, label_tab, mul_alpha, gexp, glog, prbs};
-    for (void *q : all) if (q) (void)hipFree(q);
-  }
 };
 
 // A7: 4 chunks per wavefront, V3_WGW independent wavefronts per workgroup (k_viterbi3.hpp)
 #define V3_NTB_SWITCH(ntb, CALL) switch (ntb) { case 5: CALL(5); break; case 9: CALL(9); break; case 10: CALL(10); break; case 15: CALL(15); break; default: CALL(24); break; }
 // device buffers of the proof and the repair passes; one launch of the decoder at a time per owner (stream order)
 struct VitProof {
-  int *snap = nullptr, *ctl = nullptr; long long cap = 0;
+  DevMem<int> snap, ctl; long long cap = 0;
   int reserve(long long chunks)
   {
     if (chunks <= cap) return DVBT_OK;
-    if (snap) (void)hipFree(snap); if (ctl) (void)hipFree(ctl);
-    snap = ctl = nullptr; cap = 0;
-    HIPCHK(hipMalloc((void **)&snap, v3_snap_words(chunks) * sizeof(int))); HIPCHK(hipMalloc((void **)&ctl, v3_ctl_words(chunks) * sizeof(int)));
+    cap = 0;
+    HIPCHK(snap.alloc(v3_snap_words(chunks))); HIPCHK(ctl.alloc(v3_ctl_words(chunks)));
     HIPCHK(hipMemset(ctl, 0, v3_ctl_words(chunks) * sizeof(int)));
     cap = chunks; return DVBT_OK;
   }
   V3Aux aux() const { V3Aux a; memset(&a, 0, sizeof a); a.snap = snap; a.ctl = ctl; a.cap = cap; a.carry_rel = -1; return a; }
-  ~VitProof() { if (snap) (void)hipFree(snap); if (ctl) (void)hipFree(ctl); }
 };
 enum { VIT_PLAIN = -1, VIT_REPAIR = 0, VIT_REPAIR_COUNT = 1, VIT_PROOF_ONLY = 2, VIT_FORCE_SEQ = 3, VIT_FORCE_CONFLICT = 4 };   // dvbt_rx_params.viterbi_verify
 constexpr unsigned V3_REPAIR_GRID = 64;   // workgroups of the parallel repair pass: 1024 decoders at once, the rest in rounds (a wavefront without a listed chunk returns at once)
@@ -311,65 +304,71 @@ static const char *kStageNames[] = {"acq", "fft", "demod", "inner", "viterbi", "
 
 // taps and polyphase branches of the stock rational_resampler (dvbt_tables.hpp::resampler_taps) on the device
 struct ResamplerDesign {
-  int ri = 0, rd = 0, nt = 0; std::vector<float> taps; float *br = nullptr;
+  int ri = 0, rd = 0, nt = 0; std::vector<float> taps; DevMem<float> br;
   int build(int interp, int decim)
   {
     if (interp <= 0 || decim <= 0) return fail(DVBT_ERR_INVALID, "bad resampler ratio");
     taps = resampler_taps(interp, decim, ri, rd);
     std::vector<float> b = resampler_branches(taps, ri, nt);
     if ((long long)ri * nt > RS_MAX_BRANCH_FLOATS || 256ll * rd / ri + nt + 2 > RS_TILE_IN) return fail(DVBT_ERR_INVALID, "resampler ratio outside the supported range");
-    HIPCHK(hipMalloc((void **)&br, b.size() * sizeof(float)));
+    HIPCHK(br.alloc(b.size()));
     HIPCHK(hipMemcpy(br, b.data(), b.size() * sizeof(float), hipMemcpyHostToDevice));
     return DVBT_OK;
   }
-  ~ResamplerDesign() { if (br) (void)hipFree(br); }
 };
 
 struct dvbt_rx {
+  // Members are released in reverse order of declaration: the streams and events stand in front of the page-locked blocks, and those in front of the device
+  // buffers that work queued on the streams uses, so the buffers go first and the streams last.  Members of pointer type own nothing: they are views
+  // into an owner (st, meta, trk_flags, sym_ticket, st_host, drift.*: the acquisition context in use, set_ctx).
   dvbt_rx_params prm; Dims d; Tables T; FrontParams fp; VitParams vp;
-  hipStream_t own_stream = nullptr, cur_stream = nullptr;
-  hipStream_t front_stream = nullptr; hipEvent_t front_ev[2] = {nullptr, nullptr};   // dvbt_rx_params.front_priority: the front end's high-priority stream, fork / join
+  Stream front_stream; Event front_ev[2];   // dvbt_rx_params.front_priority: the front end's high-priority stream, fork / join
+  Stream own_stream; hipStream_t cur_stream = nullptr;
+  Event ev[ST_COUNT];                       // dvbt_rx_enable_timing: one per stage boundary
+  Stream aux_stream; Event aux_ev;
+  static constexpr int NCTX = 3;            // acquisition contexts (below)
+  PinMem<RxState> st_host_ctx[NCTX];
   size_t max_samples = 0; int max_calls = 0;
-  float2 *d_iq = nullptr;              // only when input comes from the host
-  ResamplerDesign rsd; float2 *rs_iq = nullptr; size_t chain_max = 0;
-  AcqState *acq_carry = nullptr; bool use_carry = false;     // peak-detector state carried into a restart after a lost lock   // front-of-chain resample + scale (next row 2): its output buffer
-  float2 *g_init = nullptr; float *l_init = nullptr; float2 *g_trk = nullptr; float *l_trk = nullptr;
-  SymMeta *meta = nullptr; RxState *st = nullptr, *st_host = nullptr; TpsState *tps_state = nullptr;
+  DevMem<float2> d_iq;                 // only when input comes from the host
+  ResamplerDesign rsd; DevMem<float2> rs_iq; size_t chain_max = 0;
+  DevMem<AcqState> acq_carry; bool use_carry = false;     // peak-detector state carried into a restart after a lost lock   // front-of-chain resample + scale (next row 2): its output buffer
+  DevMem<float2> g_init; DevMem<float> l_init; DevMem<float2> g_trk; DevMem<float> l_trk;
+  SymMeta *meta = nullptr; RxState *st = nullptr, *st_host = nullptr; DevMem<TpsState> tps_state;
   // two acquisition contexts (state block + per-symbol tracker results): `st` / `meta` point at the one in use.  The lock-period walk searches on in the
   // other one, so that what the last decoded period left behind stays valid for the byte de-interleaver, the report and the taps (segment_periods)
-  static constexpr int NCTX = 3;            // (segment_periods uses two; the streaming entry's walk keeps a found period, decodes the one before it and searches for the next one at once)
-  RxState *st_ctx[NCTX] = {nullptr, nullptr, nullptr}; SymMeta *meta_ctx[NCTX] = {nullptr, nullptr, nullptr}; int ctx = 0;
+  // (NCTX = 3: segment_periods uses two; the streaming entry's walk keeps a found period, decodes the one before it and searches for the next one at once)
+  DevMem<RxState> st_ctx[NCTX]; DevMem<SymMeta> meta_ctx[NCTX]; int ctx = 0;
   // ... and what else an acquisition of one period and the decode of the period before it would share if they ran at the same time -- which they do (segment_periods:
   // the search for period p + 1 on the caller's stream, the decode of period p on aux_stream): the trackers' flag words, the symbol kernel's ticket, the drift
   // model's verdict, the page-locked copy of the state block.  trk_flags / sym_ticket / drift.flags / st_host point at the context in use (set_ctx)
-  int *trk_flags_ctx[NCTX] = {nullptr, nullptr, nullptr}, *sym_ticket_ctx[NCTX] = {nullptr, nullptr, nullptr}, *drift_flags_ctx[NCTX] = {nullptr, nullptr, nullptr}; RxState *st_host_ctx[NCTX] = {nullptr, nullptr, nullptr};
-  hipStream_t aux_stream = nullptr; hipEvent_t aux_ev = nullptr;
-  int *trk_cp_a = nullptr, *trk_cp_b = nullptr, *trk_flags = nullptr; float *trk_eps = nullptr; TpsEdge *tps_edges = nullptr;
-  int *centre = nullptr, *anchor_pos = nullptr;   // predicted CP position per call / coarse estimates every ACQ_ANCHOR calls
-  float2 *acq_tap = nullptr, *fft_out = nullptr, *eq = nullptr, *tpsval = nullptr; SymInfo *info = nullptr; int *maj = nullptr, *sym_index = nullptr;
-  uint8_t *labels = nullptr, *symdeint_tap = nullptr, *bitdeint = nullptr, *vit = nullptr, *deint_tap = nullptr, *rs_out = nullptr, *ts_out = nullptr;
-  uint8_t *bitdeint_lp = nullptr;           // hierarchical modes: the bit de-interleaver's second output
-  uint8_t *bd_log = nullptr; std::vector<dvbt_period_tap> plog; size_t plog_bytes = 0;   // dvbt_rx_enable_taps(h, 2): every lock period's decoder input
+  DevMem<int> trk_flags_ctx[NCTX], sym_ticket_ctx[NCTX], drift_flags_ctx[NCTX];
+  DevMem<int> trk_cp_a, trk_cp_b; int *trk_flags = nullptr; DevMem<float> trk_eps; DevMem<TpsEdge> tps_edges;
+  DevMem<int> centre, anchor_pos;   // predicted CP position per call / coarse estimates every ACQ_ANCHOR calls
+  DevMem<float2> acq_tap, fft_out, eq, tpsval; DevMem<SymInfo> info; DevMem<int> maj, sym_index;
+  DevMem<uint8_t> labels, symdeint_tap, bitdeint, vit, deint_tap, rs_out, ts_out;
+  DevMem<uint8_t> bitdeint_lp;              // hierarchical modes: the bit de-interleaver's second output
+  DevMem<uint8_t> bd_log; std::vector<dvbt_period_tap> plog; size_t plog_bytes = 0;   // dvbt_rx_enable_taps(h, 2): every lock period's decoder input
   VitProof vproof; bool vit_checked = false;   // the Viterbi stage's proof + repair passes (dvbt_rx_params.viterbi_verify): the chunk decoders' states, the passes' counters
-  size_t vit_cap = 0; RsDefer *rs_defer = nullptr; int rs_defer_cap = 0;
-  unsigned long long *rs_sync = nullptr;     // bit w: payload byte 0 of RS word w is 0xB8 (deint_rs_kernel / rs_fix_kernel -> descramble_scan_kernel)
+  size_t vit_cap = 0; DevMem<RsDefer> rs_defer; int rs_defer_cap = 0;
+  DevMem<unsigned long long> rs_sync;        // bit w: payload byte 0 of RS word w is 0xB8 (deint_rs_kernel / rs_fix_kernel -> descramble_scan_kernel)
   unsigned soft_grid = 0;     // workgroups the decision scratch has slots for
-  float *csi = nullptr; int8_t *soft_a = nullptr; uint16_t *soft_tab = nullptr; unsigned *soft_scratch = nullptr;   // soft-decision mode (k_soft.hpp): channel state per carrier, soft values, A5 + A6 gather table, decision slots
+  DevMem<float> csi; DevMem<int8_t> soft_a; DevMem<uint16_t> soft_tab; DevMem<unsigned> soft_scratch;   // soft-decision mode (k_soft.hpp): channel state per carrier, soft values, A5 + A6 gather table, decision slots
   int timing = 0;             // 0 off, 1 events around every stage, 2 around the decoder only (dvbt_rx_enable_timing)
   bool pending = false;
-  hipEvent_t ev[ST_COUNT]; double acc_ms[ST_COUNT] = {0}; long n_timed = 0; bool ev_ready = false, ev_recorded = false;
+  double acc_ms[ST_COUNT] = {0}; long n_timed = 0; bool ev_recorded = false;
   dvbt_rx_report last; bool have_last = false;
   dvbt_rx_cut cut = {0, 0, 0};
-  float2 *tps_prev = nullptr, *tps_prev_snap[2] = {nullptr, nullptr}; TpsState *tps_snap[2] = {nullptr, nullptr};  DescrRun *descr_runs = nullptr; int *descr_nruns = nullptr;
+  DevMem<float2> tps_prev, tps_prev_snap[2]; DevMem<TpsState> tps_snap[2]; DevMem<DescrRun> descr_runs; DevMem<int> descr_nruns;
   int n_periods = 1; size_t seg_offset = 0;
   std::vector<dvbt_lock_period> periods;    // phase A of the last synchronous run
-  DriftBufs drift = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; double *drift_mem = nullptr;   // k_drift.hpp
+  DriftBufs drift = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; DevMem<double> drift_mem; DevMem<float> drift_delta;   // k_drift.hpp: drift's pointers are views into these two (flags: into drift_flags_ctx)
   struct GraphEntry { const void *iq; size_t n; hipStream_t s; long long sym_off; int delay, phase; hipGraphExec_t exec; };
   std::vector<GraphEntry> graphs;           // launch_graph: the captured launch sequences (a handful: a receiver's ring of segments)
   int ncu = 256;
   long long n_small = 0, n_general = 0;     // acquisition-only passes of the lock-period walk through acq_small_kernel / through the general kernels (dvbt_rx_walk_stats)
   int sym_grid = 512;                       // workgroups of symbol8k_kernel (two per CU)
   int *sym_ticket = nullptr;                // its symbol counter
+  ~dvbt_rx();                               // (the captured graphs: the one thing here that no member's type releases)
 };
 
 constexpr long long kVitMaxChunk = 3000;
@@ -382,22 +381,7 @@ static void drop_graphs(dvbt_rx *h)
   for (auto &ge : h->graphs) if (ge.exec) (void)hipGraphExecDestroy(ge.exec);
   h->graphs.clear();
 }
-
-static void rx_free(dvbt_rx *h)
-{
-  void *all[] = {h->bd_log, h->bitdeint_lp, h->st_ctx[0], h->st_ctx[1], h->st_ctx[2], h->meta_ctx[0], h->meta_ctx[1], h->meta_ctx[2], h->tps_prev_snap[0], h->tps_prev_snap[1], h->tps_snap[0], h->tps_snap[1], h->csi, h->soft_a, h->soft_tab, h->soft_scratch, h->rs_defer, h->rs_sync, h->drift_mem, h->drift.delta, h->drift_flags_ctx[0], h->drift_flags_ctx[1], h->drift_flags_ctx[2], h->tps_prev, h->descr_runs, h->descr_nruns, h->centre, h->anchor_pos, h->sym_ticket_ctx[0], h->sym_ticket_ctx[1], h->sym_ticket_ctx[2], h->tps_edges, h->trk_cp_a, h->trk_cp_b, h->trk_flags_ctx[0], h->trk_flags_ctx[1], h->trk_flags_ctx[2], h->trk_eps, h->d_iq, h->rs_iq, h->acq_carry, h->g_init, h->l_init, h->g_trk, h->l_trk, h->tps_state, h->acq_tap, h->fft_out, h->eq, h->tpsval,
-                 h->info, h->maj, h->sym_index, h->labels, h->symdeint_tap, h->bitdeint, h->vit, h->deint_tap, h->rs_out, h->ts_out};
-  for (void *q : all) if (q) (void)hipFree(q);
-  for (auto &ge : h->graphs) if (ge.exec) (void)hipGraphExecDestroy(ge.exec);
-  for (int i = 0; i < dvbt_rx::NCTX; i++) if (h->st_host_ctx[i]) (void)hipHostFree(h->st_host_ctx[i]);
-  if (h->aux_ev) (void)hipEventDestroy(h->aux_ev);
-  if (h->aux_stream) (void)hipStreamDestroy(h->aux_stream);
-  if (h->ev_ready) for (int i = 0; i < ST_COUNT; i++) (void)hipEventDestroy(h->ev[i]);
-  if (h->own_stream) (void)hipStreamDestroy(h->own_stream);
-  for (int i = 0; i < 2; i++) if (h->front_ev[i]) (void)hipEventDestroy(h->front_ev[i]);
-  if (h->front_stream) (void)hipStreamDestroy(h->front_stream);
-  delete h;
-}
+dvbt_rx::~dvbt_rx() { drop_graphs(this); }
 
 extern "C" int dvbt_rx_create(const dvbt_rx_params *p, dvbt_rx **out)
 {
@@ -416,15 +400,15 @@ extern "C" int dvbt_rx_create(const dvbt_rx_params *p, dvbt_rx **out)
   if (p->viterbi_verify < VIT_PLAIN || p->viterbi_verify > VIT_FORCE_CONFLICT) return fail(DVBT_ERR_INVALID, "viterbi_verify must lie in [-1, 4]");
   if (p->viterbi_verify > 0 && p->soft_decision) return fail(DVBT_ERR_INVALID, "viterbi_verify applies to the hard-decision decoder");
   HIPCHK(hipSetDevice(p->device));
-  dvbt_rx *h = new dvbt_rx();
+  std::unique_ptr<dvbt_rx> hold(new dvbt_rx()); dvbt_rx *const h = hold.get();   // released on every early return below
   h->prm = *p; h->d = d; h->T.d = d;
   // capacity of the chain proper, in samples at the OFDM elementary rate
   size_t chain_max = p->max_samples;
   if (p->resample_interp != 0 || p->resample_decim != 0) {   // 0,0 alone means no resampler: a negative pair is refused by build(), not taken for none
-    int r2 = h->rsd.build(p->resample_interp, p->resample_decim); if (r2) { delete h; return r2; }
+    if ((r = h->rsd.build(p->resample_interp, p->resample_decim))) return r;
     chain_max = (size_t)(((unsigned long long)p->max_samples * h->rsd.ri + h->rsd.rd - 1) / h->rsd.rd);
   }
-  if (chain_max < (size_t)(2 * d.N + d.cp + 16)) { delete h; return fail(DVBT_ERR_INVALID, "max_samples smaller than one acquisition window"); }
+  if (chain_max < (size_t)(2 * d.N + d.cp + 16)) return fail(DVBT_ERR_INVALID, "max_samples smaller than one acquisition window");
   h->chain_max = chain_max;
   h->fp = make_front_params(d, p->snr_db);
   int cb = p->viterbi_chunk_bytes > 0 ? p->viterbi_chunk_bytes : 768;
@@ -432,83 +416,80 @@ extern "C" int dvbt_rx_create(const dvbt_rx_params *p, dvbt_rx **out)
   if (p->viterbi_warm_windows > 0) h->vp.warm = p->viterbi_warm_windows;
   h->max_samples = p->max_samples;
   h->max_calls = (int)((chain_max - (2 * d.N + d.cp + 16)) / (d.N + d.cp) + 1);
-#define RXCHK(x) do { int r_ = (x); if (r_) { rx_free(h); return r_; } } while (0)
-#define RXHIP(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { g_err = std::string(#x) + ": " + hipGetErrorString(e_); rx_free(h); return DVBT_ERR_HIP; } } while (0)
-  RXCHK(h->T.build_fft(d.N)); RXCHK(h->T.build_front()); RXCHK(h->T.build_inner(1.0f)); RXCHK(h->T.build_rs());
-  RXHIP(hipStreamCreate(&h->own_stream));
+  if ((r = h->T.build_fft(d.N)) || (r = h->T.build_front()) || (r = h->T.build_inner(1.0f)) || (r = h->T.build_rs())) return r;
+  HIPCHK(h->own_stream.create());
   if (p->front_priority) {
-    int least = 0, greatest = 0; RXHIP(hipDeviceGetStreamPriorityRange(&least, &greatest));
-    RXHIP(hipStreamCreateWithPriority(&h->front_stream, hipStreamNonBlocking, greatest));
-    for (int i = 0; i < 2; i++) RXHIP(hipEventCreateWithFlags(&h->front_ev[i], hipEventDisableTiming));
+    int least = 0, greatest = 0; HIPCHK(hipDeviceGetStreamPriorityRange(&least, &greatest));
+    HIPCHK(h->front_stream.create(hipStreamNonBlocking, greatest));
+    for (int i = 0; i < 2; i++) HIPCHK(h->front_ev[i].create(hipEventDisableTiming));
   }
-  if (h->rsd.ri) RXHIP(hipMalloc((void **)&h->rs_iq, sizeof(float2) * (chain_max + 16)));
+  if (h->rsd.ri) HIPCHK(h->rs_iq.alloc(chain_max + 16));
   const size_t C = (size_t)h->max_calls, N = d.N, P = d.payload;
-  RXHIP(hipMalloc((void **)&h->g_init, sizeof(float2) * ACQ_INIT_TRIES_MAX * N)); RXHIP(hipMalloc((void **)&h->l_init, sizeof(float) * ACQ_INIT_TRIES_MAX * N));
-  RXHIP(hipMalloc((void **)&h->g_trk, sizeof(float2) * C * 2 * ACQ_R)); RXHIP(hipMalloc((void **)&h->l_trk, sizeof(float) * C * 2 * ACQ_R));
-  for (int i = 0; i < dvbt_rx::NCTX; i++) { RXHIP(hipMalloc((void **)&h->meta_ctx[i], sizeof(SymMeta) * C)); RXHIP(hipMalloc((void **)&h->st_ctx[i], sizeof(RxState))); RXHIP(hipMemset(h->st_ctx[i], 0, sizeof(RxState))); }
+  HIPCHK(h->g_init.alloc(ACQ_INIT_TRIES_MAX * N)); HIPCHK(h->l_init.alloc(ACQ_INIT_TRIES_MAX * N));
+  HIPCHK(h->g_trk.alloc(C * 2 * ACQ_R)); HIPCHK(h->l_trk.alloc(C * 2 * ACQ_R));
+  for (int i = 0; i < dvbt_rx::NCTX; i++) { HIPCHK(h->meta_ctx[i].alloc(C)); HIPCHK(h->st_ctx[i].alloc(1)); HIPCHK(hipMemset(h->st_ctx[i], 0, sizeof(RxState))); }
   h->meta = h->meta_ctx[0]; h->st = h->st_ctx[0]; h->ctx = 0;
-  RXHIP(hipMalloc((void **)&h->trk_cp_a, sizeof(int) * C)); RXHIP(hipMalloc((void **)&h->trk_cp_b, sizeof(int) * C));
-  RXHIP(hipMalloc((void **)&h->trk_eps, sizeof(float) * C));
-  for (int i = 0; i < dvbt_rx::NCTX; i++) { RXHIP(hipMalloc((void **)&h->trk_flags_ctx[i], sizeof(int) * 16)); RXHIP(hipMemset(h->trk_flags_ctx[i], 0, sizeof(int) * 16)); }
+  HIPCHK(h->trk_cp_a.alloc(C)); HIPCHK(h->trk_cp_b.alloc(C));
+  HIPCHK(h->trk_eps.alloc(C));
+  for (int i = 0; i < dvbt_rx::NCTX; i++) { HIPCHK(h->trk_flags_ctx[i].alloc(16)); HIPCHK(hipMemset(h->trk_flags_ctx[i], 0, sizeof(int) * 16)); }
   h->trk_flags = h->trk_flags_ctx[0];
-  RXHIP(hipStreamCreate(&h->aux_stream)); RXHIP(hipEventCreateWithFlags(&h->aux_ev, hipEventDisableTiming));
-  RXHIP(hipMalloc((void **)&h->tps_prev, sizeof(float2) * d.n_tps)); RXHIP(hipMemset(h->tps_prev, 0, sizeof(float2) * d.n_tps));
-  for (int i = 0; i < 2; i++) { RXHIP(hipMalloc((void **)&h->tps_prev_snap[i], sizeof(float2) * d.n_tps)); RXHIP(hipMalloc((void **)&h->tps_snap[i], sizeof(TpsState))); }
-  RXHIP(hipMalloc((void **)&h->descr_runs, sizeof(DescrRun) * DESCR_MAX_RUNS)); RXHIP(hipMalloc((void **)&h->descr_nruns, sizeof(int)));
-  RXHIP(hipMalloc((void **)&h->centre, sizeof(int) * (C + 1))); RXHIP(hipMalloc((void **)&h->anchor_pos, sizeof(int) * (C / ACQ_ANCHOR + 4)));
-  RXHIP(hipMalloc((void **)&h->tps_edges, sizeof(TpsEdge) * (C / TPS_SEG + 2)));
-  for (int i = 0; i < dvbt_rx::NCTX; i++) { RXHIP(hipHostMalloc((void **)&h->st_host_ctx[i], sizeof(RxState))); memset(h->st_host_ctx[i], 0, sizeof(RxState)); }
+  HIPCHK(h->aux_stream.create()); HIPCHK(h->aux_ev.create(hipEventDisableTiming));
+  HIPCHK(h->tps_prev.alloc(d.n_tps)); HIPCHK(hipMemset(h->tps_prev, 0, sizeof(float2) * d.n_tps));
+  for (int i = 0; i < 2; i++) { HIPCHK(h->tps_prev_snap[i].alloc(d.n_tps)); HIPCHK(h->tps_snap[i].alloc(1)); }
+  HIPCHK(h->descr_runs.alloc(DESCR_MAX_RUNS)); HIPCHK(h->descr_nruns.alloc(1));
+  HIPCHK(h->centre.alloc(C + 1)); HIPCHK(h->anchor_pos.alloc(C / ACQ_ANCHOR + 4));
+  HIPCHK(h->tps_edges.alloc(C / TPS_SEG + 2));
+  for (int i = 0; i < dvbt_rx::NCTX; i++) { HIPCHK(h->st_host_ctx[i].alloc(1)); memset(h->st_host_ctx[i], 0, sizeof(RxState)); }
   h->st_host = h->st_host_ctx[0];
-  RXHIP(hipMalloc((void **)&h->acq_carry, sizeof(AcqState))); RXHIP(hipMalloc((void **)&h->tps_state, sizeof(TpsState)));
-  RXHIP(hipMalloc((void **)&h->labels, C * P + 64));   // A1..A4 are one kernel: a symbol reaches HBM as label bytes; fft_out and eq exist only as debug taps
-  RXHIP(hipMalloc((void **)&h->tpsval, sizeof(float2) * C * d.n_tps)); RXHIP(hipMalloc((void **)&h->info, sizeof(SymInfo) * C));
-  RXHIP(hipMalloc((void **)&h->maj, sizeof(int) * C)); RXHIP(hipMalloc((void **)&h->sym_index, sizeof(int) * C));
-  RXHIP(hipMalloc((void **)&h->bitdeint, C * P + 64));
-  if (d.hierarchy != 0) RXHIP(hipMalloc((void **)&h->bitdeint_lp, C * P + 64));
+  HIPCHK(h->acq_carry.alloc(1)); HIPCHK(h->tps_state.alloc(1));
+  HIPCHK(h->labels.alloc(C * P + 64));   // A1..A4 are one kernel: a symbol reaches HBM as label bytes; fft_out and eq exist only as debug taps
+  HIPCHK(h->tpsval.alloc(C * d.n_tps)); HIPCHK(h->info.alloc(C));
+  HIPCHK(h->maj.alloc(C)); HIPCHK(h->sym_index.alloc(C));
+  HIPCHK(h->bitdeint.alloc(C * P + 64));
+  if (d.hierarchy != 0) HIPCHK(h->bitdeint_lp.alloc(C * P + 64));
   { int ncu = 256; (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, h->prm.device); h->sym_grid = s8_grid(ncu); h->ncu = ncu; }
   if (p->viterbi_verify != VIT_PLAIN && !p->soft_decision) {   // the proof's state slots for the most chunks a launch of this handle can have (vit_chunk_bytes)
     const long long mv = (long long)C * P * d.m * d.k / (8 * d.n) + 1;
     long long chunks;
     if (p->viterbi_chunk_bytes > 0) chunks = mv / vit_chunk_bytes(h, mv) + 2;
     else { const long long slots = (long long)h->ncu * V3_WAVES_PER_CU * 4; chunks = slots * ((mv + slots * kVitMaxChunk - 1) / (slots * kVitMaxChunk)) + 4; }
-    RXCHK(h->vproof.reserve(chunks));
+    if ((r = h->vproof.reserve(chunks))) return r;
   }
   h->vit_cap = C * P * d.m * d.k / (8 * d.n) + 4096 + (2u << 20);   // (+ 2 MB: a walk of the streaming entry carries the tail of its Viterbi stream from window to window)
   h->rs_defer_cap = (int)((h->vit_cap / 204 / 64 + 2) * (RS_LANE_MIN - 1));
-  RXHIP(hipMalloc((void **)&h->rs_defer, sizeof(RsDefer) * (size_t)h->rs_defer_cap));
-  RXHIP(hipMalloc((void **)&h->rs_sync, sizeof(unsigned long long) * (h->vit_cap / 204 / 64 + 2)));
-  RXHIP(hipMalloc((void **)&h->vit, h->vit_cap)); RXHIP(hipMalloc((void **)&h->rs_out, h->vit_cap)); RXHIP(hipMalloc((void **)&h->ts_out, h->vit_cap));
-  RXHIP(hipMemset(h->st, 0, sizeof(RxState)));
-  for (int i = 0; i < ST_COUNT; i++) RXHIP(hipEventCreate(&h->ev[i]));
-  h->ev_ready = true;
-  for (int i = 0; i < dvbt_rx::NCTX; i++) { RXHIP(hipMalloc((void **)&h->sym_ticket_ctx[i], 64)); RXHIP(hipMemset(h->sym_ticket_ctx[i], 0, 64)); }
+  HIPCHK(h->rs_defer.alloc((size_t)h->rs_defer_cap));
+  HIPCHK(h->rs_sync.alloc(h->vit_cap / 204 / 64 + 2));
+  HIPCHK(h->vit.alloc(h->vit_cap)); HIPCHK(h->rs_out.alloc(h->vit_cap)); HIPCHK(h->ts_out.alloc(h->vit_cap));
+  HIPCHK(hipMemset(h->st, 0, sizeof(RxState)));
+  for (int i = 0; i < ST_COUNT; i++) HIPCHK(h->ev[i].create());
+  for (int i = 0; i < dvbt_rx::NCTX; i++) { HIPCHK(h->sym_ticket_ctx[i].alloc(16)); HIPCHK(hipMemset(h->sym_ticket_ctx[i], 0, 64)); }
   h->sym_ticket = h->sym_ticket_ctx[0];
   if (p->soft_decision) {
-    RXHIP(hipMalloc((void **)&h->eq, sizeof(float2) * C * P)); RXHIP(hipMalloc((void **)&h->csi, sizeof(float) * C * P));
-    RXHIP(hipMalloc((void **)&h->soft_a, C * P * d.m + 64)); RXHIP(hipMalloc((void **)&h->soft_tab, sizeof(uint16_t) * 2 * P * d.m));
+    HIPCHK(h->eq.alloc(C * P)); HIPCHK(h->csi.alloc(C * P));
+    HIPCHK(h->soft_a.alloc(C * P * d.m + 64)); HIPCHK(h->soft_tab.alloc(2 * P * d.m));
     // decision slots: one per resident wavefront of the largest launch this handle can make (max_samples), not of the largest launch there is
     // (2048 workgroups = 704 MB: what a 17-superframe segment of 8k QAM64 7/8 uses; a 2-superframe handle of the streaming entry needs 1/8 of that)
     const long long max_vit_soft = (long long)C * P * d.m * d.k / (8 * d.n) + 1;
     h->soft_grid = s4_grid_bound(max_vit_soft);               // (s4_grid itself is not monotone in the stream's length: ADVICE r04)
-    RXHIP(hipMalloc((void **)&h->soft_scratch, sizeof(unsigned) * (size_t)h->soft_grid * S4_WAVES * S4_SLOT_WORDS));
+    HIPCHK(h->soft_scratch.alloc((size_t)h->soft_grid * S4_WAVES * S4_SLOT_WORDS));
     hipLaunchKernelGGL(soft_tab_kernel, dim3(64), dim3(256), 0, h->own_stream, h->T.inner_params(d.payload), (const uint16_t *)h->T.H, (const uint16_t *)h->T.Hinv, h->soft_tab);
-    RXHIP(hipStreamSynchronize(h->own_stream));
+    HIPCHK(hipStreamSynchronize(h->own_stream));
   }
   {   // the float phase accumulator's wander (k_drift.hpp): tables and sums per call, one deviation per 32 samples of every item
-    RXHIP(hipMalloc((void **)&h->drift_mem, sizeof(double) * (C * (DRIFT_TAB + 4) + 8)));
+    HIPCHK(h->drift_mem.alloc(C * (DRIFT_TAB + 4) + 8));
     h->drift.tabs = h->drift_mem; h->drift.ex_run = h->drift.tabs + C * DRIFT_TAB; h->drift.ex_entry = h->drift.ex_run + C;
     h->drift.d = h->drift.ex_entry + C; h->drift.S = h->drift.d + C; h->drift.A0 = h->drift.S + C;
-    RXHIP(hipMalloc((void **)&h->drift.delta, sizeof(float) * C * (N / 32))); for (int i = 0; i < dvbt_rx::NCTX; i++) { RXHIP(hipMalloc((void **)&h->drift_flags_ctx[i], 16)); RXHIP(hipMemset(h->drift_flags_ctx[i], 0, 16)); }
+    HIPCHK(h->drift_delta.alloc(C * (N / 32))); h->drift.delta = h->drift_delta; for (int i = 0; i < dvbt_rx::NCTX; i++) { HIPCHK(h->drift_flags_ctx[i].alloc(4)); HIPCHK(hipMemset(h->drift_flags_ctx[i], 0, 16)); }
     h->drift.flags = h->drift_flags_ctx[0];
   }
-  RXCHK(set_lds((const void *)symbol8k_kernel<false, false>, S8_LDS_BYTES)); RXCHK(set_lds((const void *)symbol8k_kernel<false, true>, S8_LDS_BYTES));
-  RXCHK(set_lds((const void *)symbol8k_kernel<true, false>, S8_LDS_BYTES)); RXCHK(set_lds((const void *)symbol8k_kernel<true, true>, S8_LDS_BYTES));
-  RXCHK(set_lds((const void *)symbol2k_kernel<false, false>, S2_LDS_BYTES)); RXCHK(set_lds((const void *)symbol2k_kernel<false, true>, S2_LDS_BYTES));
-  RXCHK(set_lds((const void *)symbol2k_kernel<true, false>, S2_LDS_BYTES)); RXCHK(set_lds((const void *)symbol2k_kernel<true, true>, S2_LDS_BYTES));
-  RXCHK(set_lds((const void *)inner_kernel<6>, inner_lds_bytes(P)));
-  RXCHK(set_lds((const void *)acq_anchor_kernel, acq_anchor_lds_bytes((int)N, d.cp)));
-  RXCHK(set_lds((const void *)acq_small_kernel, (size_t)acq_small_cpc(d.cp) * 2 * (d.cp + 2 * ACQ_R) * sizeof(float2)));
-  *out = h;
+  if ((r = set_lds((const void *)symbol8k_kernel<false, false>, S8_LDS_BYTES))) return r; if ((r = set_lds((const void *)symbol8k_kernel<false, true>, S8_LDS_BYTES))) return r;
+  if ((r = set_lds((const void *)symbol8k_kernel<true, false>, S8_LDS_BYTES))) return r; if ((r = set_lds((const void *)symbol8k_kernel<true, true>, S8_LDS_BYTES))) return r;
+  if ((r = set_lds((const void *)symbol2k_kernel<false, false>, S2_LDS_BYTES))) return r; if ((r = set_lds((const void *)symbol2k_kernel<false, true>, S2_LDS_BYTES))) return r;
+  if ((r = set_lds((const void *)symbol2k_kernel<true, false>, S2_LDS_BYTES))) return r; if ((r = set_lds((const void *)symbol2k_kernel<true, true>, S2_LDS_BYTES))) return r;
+  if ((r = set_lds((const void *)inner_kernel<6>, inner_lds_bytes(P)))) return r;
+  if ((r = set_lds((const void *)acq_anchor_kernel, acq_anchor_lds_bytes((int)N, d.cp)))) return r;
+  if ((r = set_lds((const void *)acq_small_kernel, (size_t)acq_small_cpc(d.cp) * 2 * (d.cp + 2 * ACQ_R) * sizeof(float2)))) return r;
+  *out = hold.release();
   return DVBT_OK;
 }
 
@@ -533,24 +514,28 @@ extern "C" int dvbt_rx_enable_timing(dvbt_rx *h, int enable)
 // The buffers behind the Viterbi decoder for a stream of at least `cap` bytes (contents kept).  A handle is created for one launch over max_samples; the streaming entry's
 // walk lays the lock periods of a WINDOW out in h->vit -- up to two pieces and a threshold of samples when a lost piece is harvested late -- in front of an open period that
 // alone may fill a launch (dvbt_rx_stream_push failed with DVBT_ERR_CAPACITY there).  Grows, never shrinks; synchronises the device (a walk is synchronous anyway).
+template <class T> static int grown(DevMem<T> &q, const DevMem<T> &from, size_t count, size_t keep)   // q: `count` elements, the first `keep` of them from's
+{
+  HIPCHK(q.alloc(count));
+  if (keep) HIPCHK(hipMemcpy(q, from, keep * sizeof(T), hipMemcpyDeviceToDevice));
+  return DVBT_OK;
+}
 static int rx_reserve_vit(dvbt_rx *h, size_t cap)
 {
   if (cap <= h->vit_cap) return DVBT_OK;
   HIPCHK(hipDeviceSynchronize());
   drop_graphs(h);
-  const size_t old = h->vit_cap;
-  uint8_t **bufs[] = {&h->vit, &h->rs_out, &h->ts_out, &h->deint_tap};
-  for (uint8_t **b : bufs) {
-    if (!*b) continue;                                             // (deint_tap: a debug tap, there only on request)
-    uint8_t *q = nullptr; HIPCHK(hipMalloc((void **)&q, cap));
-    HIPCHK(hipMemcpy(q, *b, old, hipMemcpyDeviceToDevice));
-    (void)hipFree(*b); *b = q;
-  }
-  const int dcap = (int)((cap / 204 / 64 + 2) * (RS_LANE_MIN - 1));
-  { RsDefer *q = nullptr; HIPCHK(hipMalloc((void **)&q, sizeof(RsDefer) * (size_t)dcap)); (void)hipFree(h->rs_defer); h->rs_defer = q; h->rs_defer_cap = dcap; }
-  { unsigned long long *q = nullptr; HIPCHK(hipMalloc((void **)&q, sizeof(unsigned long long) * (cap / 204 / 64 + 2)));
-    HIPCHK(hipMemcpy(q, h->rs_sync, sizeof(unsigned long long) * (old / 204 / 64 + 2), hipMemcpyDeviceToDevice)); (void)hipFree(h->rs_sync); h->rs_sync = q; }
-  h->vit_cap = cap;
+  const size_t old = h->vit_cap, sync_old = old / 204 / 64 + 2, sync_new = cap / 204 / 64 + 2;
+  const int dcap = (int)(sync_new * (RS_LANE_MIN - 1));
+  // every new buffer first, filled with what it keeps; the handle takes them only when all are there, so a failure leaves it as it was
+  DevMem<uint8_t> vit, rs_out, ts_out, deint_tap; DevMem<RsDefer> rs_defer; DevMem<unsigned long long> rs_sync;
+  int r;
+  if ((r = grown(vit, h->vit, cap, old)) || (r = grown(rs_out, h->rs_out, cap, old)) || (r = grown(ts_out, h->ts_out, cap, old)) ||
+      (r = grown(rs_defer, h->rs_defer, (size_t)dcap, 0)) || (r = grown(rs_sync, h->rs_sync, sync_new, sync_old))) return r;
+  if (h->deint_tap && (r = grown(deint_tap, h->deint_tap, cap, old))) return r;      // (a debug tap, there only on request)
+  h->vit = std::move(vit); h->rs_out = std::move(rs_out); h->ts_out = std::move(ts_out); h->rs_defer = std::move(rs_defer); h->rs_sync = std::move(rs_sync);
+  if (h->deint_tap) h->deint_tap = std::move(deint_tap);
+  h->rs_defer_cap = dcap; h->vit_cap = cap;
   return DVBT_OK;
 }
 
@@ -558,11 +543,11 @@ static int rx_reserve_vit(dvbt_rx *h, size_t cap)
 static int ensure_taps(dvbt_rx *h)
 {
   const size_t C = (size_t)h->max_calls, N = h->d.N, P = h->d.payload;
-  if (!h->acq_tap) HIPCHK(hipMalloc((void **)&h->acq_tap, sizeof(float2) * C * N));
-  if (!h->fft_out) HIPCHK(hipMalloc((void **)&h->fft_out, sizeof(float2) * C * N));
-  if (!h->eq) HIPCHK(hipMalloc((void **)&h->eq, sizeof(float2) * C * P));
-  if (!h->symdeint_tap) HIPCHK(hipMalloc((void **)&h->symdeint_tap, C * P + 64));
-  if (!h->deint_tap) HIPCHK(hipMalloc((void **)&h->deint_tap, h->vit_cap));
+  if (!h->acq_tap) HIPCHK(h->acq_tap.alloc(C * N));
+  if (!h->fft_out) HIPCHK(h->fft_out.alloc(C * N));
+  if (!h->eq) HIPCHK(h->eq.alloc(C * P));
+  if (!h->symdeint_tap) HIPCHK(h->symdeint_tap.alloc(C * P + 64));
+  if (!h->deint_tap) HIPCHK(h->deint_tap.alloc(h->vit_cap));
   return DVBT_OK;
 }
 extern "C" int dvbt_rx_enable_taps(dvbt_rx *h, int enable)
@@ -570,12 +555,12 @@ extern "C" int dvbt_rx_enable_taps(dvbt_rx *h, int enable)
   if (!h) return DVBT_ERR_INVALID;
   if (h->pending) return fail(DVBT_ERR_STATE, "dvbt_rx_enable_taps: a segment is in flight (dvbt_rx_segment_finish first)");
   drop_graphs(h);
-  if (enable == 2 && !h->bd_log) HIPCHK(hipMalloc((void **)&h->bd_log, (size_t)h->max_calls * h->d.payload + 64));
+  if (enable == 2 && !h->bd_log) HIPCHK(h->bd_log.alloc((size_t)h->max_calls * h->d.payload + 64));
   if (enable) return ensure_taps(h);
-  if (h->bd_log) { (void)hipFree(h->bd_log); h->bd_log = nullptr; }
+  h->bd_log.reset();
   // in soft-decision mode eq is not a debug tap but the soft demapper's input (allocated at create; it also selects the symbol kernel's instantiation that writes eq and csi)
-  void **all[] = {(void **)&h->acq_tap, (void **)&h->fft_out, h->prm.soft_decision ? (void **)nullptr : (void **)&h->eq, (void **)&h->symdeint_tap, (void **)&h->deint_tap};
-  for (void **q : all) if (q && *q) { (void)hipFree(*q); *q = nullptr; }
+  h->acq_tap.reset(); h->fft_out.reset(); h->symdeint_tap.reset(); h->deint_tap.reset();
+  if (!h->prm.soft_decision) h->eq.reset();
   return DVBT_OK;
 }
 
@@ -691,7 +676,7 @@ static int enqueue(dvbt_rx *h, const float2 *iq, size_t nsamples, hipStream_t s,
   // looked at; computing it unasked costs nothing on an otherwise idle device and saves two launches per lock period
   // (the FSM launch also clears the trackers' flag words, the symbol kernel's ticket and, for a period that starts the pilot engine afresh, its state)
   hipLaunchKernelGGL(acq_metric_kernel, dim3((N + 255) / 256, tries), dim3(256), 0, s, iq, fp, (const RxState *)h->st, 0, h->g_init, h->l_init, 0);
-  const AcqReset rz = {h->trk_flags, h->sym_ticket, (o.acq_only || o.continuation || o.tps_init) ? nullptr : reinterpret_cast<int *>(h->tps_state), (int)(sizeof(TpsState) / 4),
+  const AcqReset rz = {h->trk_flags, h->sym_ticket, (o.acq_only || o.continuation || o.tps_init) ? nullptr : reinterpret_cast<int *>(h->tps_state.get()),(int)(sizeof(TpsState) / 4),
                        o.carry_avg, o.use_carry ? 1 : 0};
   hipLaunchKernelGGL(acq_init_fsm_kernel, dim3(1), dim3(1024), (size_t)N * 5, s, fp, h->st, (const float2 *)h->g_init, (const float *)h->l_init, carry, 0, tries, rz);
   if (o.acq_only && !o.no_small && C <= ACQ_SMALL_MAX_CALLS) {
@@ -1374,7 +1359,7 @@ extern "C" int dvbt_rx_segment_run(dvbt_rx *h, const void *iq_host, size_t nsamp
   if (!h || !iq_host) return fail(DVBT_ERR_INVALID, "null argument");
   HIPCHK(hipSetDevice(h->prm.device));
   if (nsamples > h->max_samples) return fail(DVBT_ERR_CAPACITY, "segment longer than max_samples");
-  if (!h->d_iq) HIPCHK(hipMalloc((void **)&h->d_iq, sizeof(float2) * h->max_samples));
+  if (!h->d_iq) HIPCHK(h->d_iq.alloc(h->max_samples));
   HIPCHK(hipMemcpyAsync(h->d_iq, iq_host, sizeof(float2) * nsamples, hipMemcpyHostToDevice, h->own_stream));
   const float2 *chain; size_t chain_n;
   int r = prepare_chain(h, h->d_iq, nsamples, h->own_stream, &chain, &chain_n); if (r) return r;
@@ -1525,7 +1510,7 @@ extern "C" double dvbt_rx_stage_ms(dvbt_rx *h, const char *stage)
   return -1.0;
 }
 
-extern "C" void dvbt_rx_destroy(dvbt_rx *h) { if (h) rx_free(h); }
+extern "C" void dvbt_rx_destroy(dvbt_rx *h) { delete h; }
 
 // test hook: the trackers' two peak detectors (peak_detect, the reference's state machine sample by sample; peak_detect16_wave, the wavefront-wide form the
 // sequential trackers use) on n cases of 16 metric values and a carried average each.  out[4k..]: npk, pos of the first, npk, pos of the second; avg_out[2k..]: d_avg after
@@ -1533,12 +1518,11 @@ extern "C" int dvbt_debug_peak_detect(const float *lam_host, const float *avg_ho
 {
   if (!lam_host || !avg_host || !out_host || !avg_out_host || n <= 0) return fail(DVBT_ERR_INVALID, "null argument");
   int r = need_device(); if (r) return r;
-  float *dl = nullptr, *da = nullptr, *dao = nullptr; int *dout = nullptr;
-  HIPCHK(hipMalloc((void **)&dl, sizeof(float) * 16 * n)); HIPCHK(hipMalloc((void **)&da, sizeof(float) * n)); HIPCHK(hipMalloc((void **)&dao, sizeof(float) * 2 * n)); HIPCHK(hipMalloc((void **)&dout, sizeof(int) * 4 * n));
+  DevMem<float> dl, da, dao; DevMem<int> dout;
+  HIPCHK(dl.alloc((size_t)16 * n)); HIPCHK(da.alloc(n)); HIPCHK(dao.alloc((size_t)2 * n)); HIPCHK(dout.alloc((size_t)4 * n));
   HIPCHK(hipMemcpy(dl, lam_host, sizeof(float) * 16 * n, hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(da, avg_host, sizeof(float) * n, hipMemcpyHostToDevice));
   hipLaunchKernelGGL(peak_selftest_kernel, dim3(n), dim3(64), 0, nullptr, (const float *)dl, (const float *)da, n, dout, dao);
   HIPCHK(hipMemcpy(out_host, dout, sizeof(int) * 4 * n, hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(avg_out_host, dao, sizeof(float) * 2 * n, hipMemcpyDeviceToHost));
-  (void)hipFree(dl); (void)hipFree(da); (void)hipFree(dao); (void)hipFree(dout);
   return DVBT_OK;
 }
 
@@ -1564,18 +1548,16 @@ extern "C" int dvbt_debug_soft_viterbi(int constellation, int code_rate, const i
   const VitParams vp = make_vit_params(d, 768, 768);
   RxState st; memset(&st, 0, sizeof st);
   st.first_out = 0; st.n_vit_steps = total_steps; st.n_vit_in = n_soft / d.m;
-  int8_t *dsoft = nullptr; uint8_t *dout = nullptr; RxState *dst = nullptr; unsigned *scratch = nullptr;
-  auto done = [&](int code) { (void)hipFree(dsoft); (void)hipFree(dout); (void)hipFree(dst); (void)hipFree(scratch); return code; };
-#define DBGHIP(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { g_err = std::string(#x) + ": " + hipGetErrorString(e_); return done(DVBT_ERR_HIP); } } while (0)
-  DBGHIP(hipMalloc((void **)&dsoft, (size_t)n_soft + 64)); DBGHIP(hipMalloc((void **)&dout, out_cap)); DBGHIP(hipMalloc((void **)&dst, sizeof(RxState)));
-  DBGHIP(hipMalloc((void **)&scratch, sizeof(unsigned) * (size_t)grid * S4_WAVES * S4_SLOT_WORDS));
-  if (n_soft) DBGHIP(hipMemcpy(dsoft, soft_host, (size_t)n_soft, hipMemcpyHostToDevice));
-  DBGHIP(hipMemcpy(dst, &st, sizeof st, hipMemcpyHostToDevice));
-  DBGHIP(hipMemset(dout, 0xA5, out_cap));
+  DevMem<int8_t> dsoft; DevMem<uint8_t> dout; DevMem<RxState> dst; DevMem<unsigned> scratch;
+  HIPCHK(dsoft.alloc((size_t)n_soft + 64)); HIPCHK(dout.alloc(out_cap)); HIPCHK(dst.alloc(1));
+  HIPCHK(scratch.alloc((size_t)grid * S4_WAVES * S4_SLOT_WORDS));
+  if (n_soft) HIPCHK(hipMemcpy(dsoft, soft_host, (size_t)n_soft, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(dst, &st, sizeof st, hipMemcpyHostToDevice));
+  HIPCHK(hipMemset(dout, 0xA5, out_cap));
   hipLaunchKernelGGL(viterbi_soft4_kernel, dim3((unsigned)grid), dim3(64 * S4_WAVES), 0, nullptr, (const int8_t *)dsoft, dout, (const RxState *)dst, vp, scratch, B, nsteps);
-  DBGHIP(hipGetLastError());
-  DBGHIP(hipMemcpy(out_host, dout, out_cap, hipMemcpyDeviceToHost));
-  return done(DVBT_OK);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpy(out_host, dout, out_cap, hipMemcpyDeviceToHost));
+  return DVBT_OK;
 }
 
 // test hook: soft_tab_kernel, then soft_demap_kernel, on nsym host-supplied symbols of equalised carriers (cfloat[P]) and channel state (float[P]) with a symbol
@@ -1591,21 +1573,19 @@ extern "C" int dvbt_debug_soft_demap(int constellation, int mode, const void *eq
   const size_t P = d.payload, n = (size_t)nsym * P;
   RxState st; memset(&st, 0, sizeof st);
   st.first_out = 0; st.n_out_symbols = nsym;
-  float2 *deq = nullptr; float *dcsi = nullptr; int *dpar = nullptr; RxState *dst = nullptr; uint16_t *tab = nullptr; int8_t *dout = nullptr;
-  auto done = [&](int code) { (void)hipFree(deq); (void)hipFree(dcsi); (void)hipFree(dpar); (void)hipFree(dst); (void)hipFree(tab); (void)hipFree(dout); return code; };
-  DBGHIP(hipMalloc((void **)&deq, sizeof(float2) * n)); DBGHIP(hipMalloc((void **)&dcsi, sizeof(float) * n)); DBGHIP(hipMalloc((void **)&dpar, sizeof(int) * nsym));
-  DBGHIP(hipMalloc((void **)&dst, sizeof(RxState))); DBGHIP(hipMalloc((void **)&tab, sizeof(uint16_t) * 2 * P * d.m)); DBGHIP(hipMalloc((void **)&dout, n * d.m + 64));
-  DBGHIP(hipMemcpy(deq, eq_host, sizeof(float2) * n, hipMemcpyHostToDevice)); DBGHIP(hipMemcpy(dcsi, csi_host, sizeof(float) * n, hipMemcpyHostToDevice));
-  DBGHIP(hipMemcpy(dpar, parity_host, sizeof(int) * nsym, hipMemcpyHostToDevice)); DBGHIP(hipMemcpy(dst, &st, sizeof st, hipMemcpyHostToDevice));
+  DevMem<float2> deq; DevMem<float> dcsi; DevMem<int> dpar; DevMem<RxState> dst; DevMem<uint16_t> tab; DevMem<int8_t> dout;
+  HIPCHK(deq.alloc(n)); HIPCHK(dcsi.alloc(n)); HIPCHK(dpar.alloc(nsym));
+  HIPCHK(dst.alloc(1)); HIPCHK(tab.alloc(2 * P * d.m)); HIPCHK(dout.alloc(n * d.m + 64));
+  HIPCHK(hipMemcpy(deq, eq_host, sizeof(float2) * n, hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(dcsi, csi_host, sizeof(float) * n, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(dpar, parity_host, sizeof(int) * nsym, hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(dst, &st, sizeof st, hipMemcpyHostToDevice));
   const InnerParams ip = T.inner_params(d.payload);
   hipLaunchKernelGGL(soft_tab_kernel, dim3(64), dim3(256), 0, nullptr, ip, (const uint16_t *)T.H, (const uint16_t *)T.Hinv, tab);
   const float step = 2.0f * d.norm;
   hipLaunchKernelGGL(soft_demap_kernel, dim3((unsigned)nsym), dim3(256), (size_t)d.payload * d.m, nullptr, (const float2 *)deq, (const float *)dcsi, (const RxState *)dst, ip,
                      (const float2 *)T.points, 1.0f / (step * step), (const int *)dpar, (const uint16_t *)tab, dout);
-  DBGHIP(hipGetLastError());
-  DBGHIP(hipMemcpy(out_host, dout, n * d.m, hipMemcpyDeviceToHost));
-#undef DBGHIP
-  return done(DVBT_OK);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpy(out_host, dout, n * d.m, hipMemcpyDeviceToHost));
+  return DVBT_OK;
 }
 
 #include "dvbt_stream.inc"

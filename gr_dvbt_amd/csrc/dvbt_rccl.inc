@@ -56,7 +56,7 @@ Rccl *rccl()
 // its transport: what it proves is the step's own logic, not RCCL.
 struct LoopGroup {
   std::mutex m; std::condition_variable cv; int world = 1, refs = 0;
-  struct Msg { int src, dst; const void *ptr; size_t n; hipEvent_t ready; hipEvent_t taken; bool consumed; };
+  struct Msg { int src, dst; const void *ptr; size_t n; bool consumed = false; Event ready, taken; };
   std::deque<Msg *> posted;
 };
 struct LoopEnd { LoopGroup *g; int rank; };
@@ -72,8 +72,8 @@ int loop_group_end()
   int rc = 0;
   // post every send first (a rank's receives may depend on a peer that is waiting for this rank's sends)
   for (LoopOp &o : loop_ops) if (o.send) {
-    LoopGroup::Msg *m = new LoopGroup::Msg{o.e->rank, o.peer, o.buf, o.n, nullptr, nullptr, false};
-    if (hipEventCreateWithFlags(&m->ready, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&m->taken, hipEventDisableTiming) != hipSuccess ||
+    LoopGroup::Msg *m = new LoopGroup::Msg{o.e->rank, o.peer, o.buf, o.n};
+    if (m->ready.create(hipEventDisableTiming) != hipSuccess || m->taken.create(hipEventDisableTiming) != hipSuccess ||
         hipEventRecord(m->ready, o.st) != hipSuccess) rc = 1;
     { std::lock_guard<std::mutex> lk(o.e->g->m); o.e->g->posted.push_back(m); }
     o.e->g->cv.notify_all();
@@ -105,7 +105,7 @@ int loop_group_end()
     for (auto it = g->posted.begin(); it != g->posted.end(); ++it) if (*it == m) { g->posted.erase(it); break; }
     lk.unlock();
     if (!ok) rc = 2; else if (hipStreamWaitEvent(op->st, m->taken, 0) != hipSuccess) rc = 1;
-    if (ok) { (void)hipEventDestroy(m->ready); (void)hipEventDestroy(m->taken); delete m; }   // (a message nobody took stays posted: the test has failed anyway)
+    if (ok) delete m;   // (a message nobody took stays posted: the test has failed anyway)
   }
   loop_ops.clear();
   return rc;
@@ -122,14 +122,16 @@ Rccl *loop_rccl()
 }  // namespace
 
 struct dvbt_rccl_comm {
-  void *comm = nullptr; int rank = 0, world = 1, device = 0; hipStream_t st = nullptr;
+  // Members are released in reverse order of declaration: the stream and the events stand in front of the buffers the steps queued on them use, so the buffers go
+  // first and the stream last (dvbt_rccl_comm_destroy has drained the stream and destroyed the communicator before that).  last_view / last_dev_view are views.
+  void *comm = nullptr; int rank = 0, world = 1, device = 0; Stream st; Event ev[2];
   size_t slot = 0;
   // double-buffered.  Persistent from dvbt_rccl_comm_create on (a step can always exchange its headers): hdr_dev -- this rank's 64-byte header on the device, hdrs --
   // every rank's, and their page-locked mirrors.  Sized by dvbt_rccl_comm_reserve: send -- this rank's slot, recv -- the root's `world` slots (root only), h_send --
   // the staging of a run that comes from the stream's host FIFO, h_recv -- the root's host mirror of the received runs (only when a step asks for it)
-  uint8_t *hdr_dev[2] = {nullptr, nullptr}, *hdrs[2] = {nullptr, nullptr}, *h_hdr[2] = {nullptr, nullptr}, *h_hdrs[2] = {nullptr, nullptr};
-  uint8_t *send[2] = {nullptr, nullptr}, *recv[2] = {nullptr, nullptr}, *h_send[2] = {nullptr, nullptr}, *h_recv[2] = {nullptr, nullptr};
-  hipEvent_t ev[2] = {nullptr, nullptr}; bool busy[2] = {false, false}; int root_of[2] = {0, 0}, flags_of[2] = {0, 0};
+  DevMem<uint8_t> hdr_dev[2], hdrs[2]; PinMem<uint8_t> h_hdr[2], h_hdrs[2];
+  DevMem<uint8_t> send[2], recv[2]; PinMem<uint8_t> h_send[2], h_recv[2];
+  bool busy[2] = {false, false}; int root_of[2] = {0, 0}, flags_of[2] = {0, 0};
   bool staged[2] = {false, false}; int64_t staged_first[2] = {0, 0}, staged_n[2] = {0, 0};   // a run pulled from the host FIFO whose group failed: sent by the next step instead of lost
   long long seq_enq = 0, seq_wait = 0; const uint8_t *last_view = nullptr, *last_dev_view = nullptr;
   bool loopback = false; int debug_fail = 0;                      // test hooks: the loopback transport; the next `debug_fail` steps treat their buffers as not allocated
@@ -161,11 +163,7 @@ extern "C" int dvbt_rccl_unique_id(void *id128)
 
 static void rccl_free_buffers(dvbt_rccl_comm *c)
 {
-  for (int b = 0; b < 2; b++) {
-    if (c->send[b]) (void)hipFree(c->send[b]); if (c->recv[b]) (void)hipFree(c->recv[b]);
-    if (c->h_send[b]) (void)hipHostFree(c->h_send[b]); if (c->h_recv[b]) (void)hipHostFree(c->h_recv[b]);
-    c->send[b] = c->recv[b] = c->h_send[b] = c->h_recv[b] = nullptr;
-  }
+  for (int b = 0; b < 2; b++) { c->send[b].reset(); c->recv[b].reset(); c->h_send[b].reset(); c->h_recv[b].reset(); }
   c->slot = 0;
 }
 
@@ -175,13 +173,6 @@ extern "C" void dvbt_rccl_comm_destroy(dvbt_rccl_comm *c)
   Rccl *R = rccl_of(c);
   if (c->st) (void)hipStreamSynchronize(c->st);
   if (R && c->comm) R->CommDestroy(c->comm);
-  rccl_free_buffers(c);
-  for (int b = 0; b < 2; b++) {
-    if (c->hdr_dev[b]) (void)hipFree(c->hdr_dev[b]); if (c->hdrs[b]) (void)hipFree(c->hdrs[b]);
-    if (c->h_hdr[b]) (void)hipHostFree(c->h_hdr[b]); if (c->h_hdrs[b]) (void)hipHostFree(c->h_hdrs[b]);
-    if (c->ev[b]) (void)hipEventDestroy(c->ev[b]);
-  }
-  if (c->st) (void)hipStreamDestroy(c->st);
   delete c;
 }
 
@@ -203,11 +194,11 @@ extern "C" int dvbt_rccl_comm_create(const void *id128, int rank, int world, int
 static int rccl_comm_finish_create(dvbt_rccl_comm *c)
 {
   const int world = c->world;
-  bool ok = hipStreamCreate(&c->st) == hipSuccess;
+  bool ok = c->st.create() == hipSuccess;
   for (int b = 0; b < 2 && ok; b++)
-    ok = hipEventCreateWithFlags(&c->ev[b], hipEventDisableTiming) == hipSuccess && hipMalloc((void **)&c->hdr_dev[b], GATHER_HEADER) == hipSuccess &&
-         hipMalloc((void **)&c->hdrs[b], GATHER_HEADER * world) == hipSuccess && hipHostMalloc((void **)&c->h_hdr[b], GATHER_HEADER) == hipSuccess &&
-         hipHostMalloc((void **)&c->h_hdrs[b], GATHER_HEADER * world) == hipSuccess;
+    ok = c->ev[b].create(hipEventDisableTiming) == hipSuccess && c->hdr_dev[b].alloc(GATHER_HEADER) == hipSuccess &&
+         c->hdrs[b].alloc(GATHER_HEADER * world) == hipSuccess && c->h_hdr[b].alloc(GATHER_HEADER) == hipSuccess &&
+         c->h_hdrs[b].alloc(GATHER_HEADER * world) == hipSuccess;
   if (!ok) { dvbt_rccl_comm_destroy(c); return fail(DVBT_ERR_HIP, "dvbt_rccl_comm_create: stream / event / header buffers"); }
   return DVBT_OK;
 }
@@ -241,12 +232,12 @@ extern "C" int dvbt_rccl_comm_reserve(dvbt_rccl_comm *c, int root, int slot_pack
     if (c->busy[0] || c->busy[1]) return fail(DVBT_ERR_STATE, "dvbt_rccl_comm_reserve: slot_packets changed while a step is in flight");
     if (c->staged[0] || c->staged[1]) return fail(DVBT_ERR_STATE, "dvbt_rccl_comm_reserve: a run whose step failed is still staged at the old size");
     rccl_free_buffers(c);
-    for (int k = 0; k < 2; k++) { HIPCHK(hipMalloc((void **)&c->send[k], slot)); HIPCHK(hipHostMalloc((void **)&c->h_send[k], slot)); }
+    for (int k = 0; k < 2; k++) { HIPCHK(c->send[k].alloc(slot)); HIPCHK(c->h_send[k].alloc(slot)); }
     c->slot = slot;
   }
   if (c->rank == root) for (int k = 0; k < 2; k++) {               // receive space on the root only
-    if (!c->recv[k]) HIPCHK(hipMalloc((void **)&c->recv[k], slot * c->world));
-    if (!(flags & DVBT_GATHER_DEVICE) && !c->h_recv[k]) HIPCHK(hipHostMalloc((void **)&c->h_recv[k], slot * c->world));
+    if (!c->recv[k]) HIPCHK(c->recv[k].alloc(slot * c->world));
+    if (!(flags & DVBT_GATHER_DEVICE) && !c->h_recv[k]) HIPCHK(c->h_recv[k].alloc(slot * c->world));
   }
   return DVBT_OK;
 }
@@ -277,7 +268,7 @@ extern "C" int dvbt_rx_stream_gather_enqueue_ex(dvbt_rx_stream *s, dvbt_rccl_com
   if (dbg_fail) { c->debug_fail--; err = 1; why = "dvbt_rccl_debug_fail_steps"; }
   // where this rank's slot is sent from / where the root receives: its own buffers, or -- when they could not be allocated -- the stream's sample buffer (content void: err)
   const bool isroot = c->rank == root;
-  uint8_t *fallback = (s->buf[0] && s->cap * sizeof(float2) >= slot) ? (uint8_t *)s->buf[0] : nullptr;
+  uint8_t *fallback = (s->buf[0] && s->cap * sizeof(float2) >= slot) ? (uint8_t *)s->buf[0].get() : nullptr;
   uint8_t *sendp = c->slot == slot && c->send[b] && !dbg_fail ? c->send[b] : fallback;
   uint8_t *recvp = isroot ? (c->slot == slot && c->recv[b] && !dbg_fail ? c->recv[b] : nullptr) : nullptr;
   if (!sendp || (isroot && !recvp && !fallback)) return fail(DVBT_ERR_HIP, "dvbt_rx_stream_gather_enqueue: no exchange buffers (" + why + "): call dvbt_rccl_comm_reserve before the first step");

@@ -73,7 +73,10 @@ struct StreamChunk { long long first_packet; const uint8_t *data; size_t len; bo
 constexpr size_t STREAM_TS_RING_DEFAULT = 96u << 20;             // ~24 s of the fastest DVB-T transport stream; a chunk is a piece's output (a few MB)
 
 // device output (dvbt_rx_stream_set_device_output): a run of decoded packets in the stream's device ring, waiting for dvbt_rx_stream_gather_enqueue
-struct DevChunk { long long first_packet; uint8_t *data; size_t len, off; bool in_ring; uint8_t *owner = nullptr; size_t owner_cap = 0; };   // owner: a handle's former TS buffer the chunk lives in (back to the pool when released)
+struct TsBuf { DevMem<uint8_t> mem; size_t cap = 0; };            // a handle's TS buffer away from its handle, with its capacity
+// Move-only: `data` is a view -- into the stream's ring (in_ring: nothing owned), into `stolen` (a handle's former TS buffer: back to the pool when released) or of `own`
+// (the chunk's overflow allocation: released with the chunk)
+struct DevChunk { long long first_packet; uint8_t *data; size_t len, off; bool in_ring; TsBuf stolen; DevMem<uint8_t> own; };
 
 // energy_descramble's state between two calls: the item the next call starts at (always even: a call consumes two) and its offset in packets (d_index / 188)
 struct DescrState { long long base = 0; int dp = 0; long long start() const { return base * 8 + dp; } };
@@ -81,20 +84,22 @@ struct DescrState { long long base = 0; int dp = 0; long long start() const { re
 }  // namespace
 
 struct dvbt_rx_stream {
+  // Members are released in reverse order of declaration: the events stand in front of the chains and of every buffer that copies recorded on them use, so the
+  // buffers and the chains (with their HIP streams) go first and the events last.  wb, DevChunk::data, StreamChunk::data and Region::ptr are views.
   dvbt_rx_stream_params prm; Dims d;
   int rank = 0, world = 1;
   static constexpr int MAXH = 4;                               // chains (handle + sample buffer + HIP stream) a stream object can have: dvbt_rx_stream_params.chains
   int nh = 2;                                                  // ... and has: the pieces take them in turn, nh - 1 pieces decode while the next one fills
-  dvbt_rx *rx[MAXH] = {nullptr, nullptr, nullptr, nullptr};
-  float2 *buf[MAXH] = {nullptr, nullptr, nullptr, nullptr}; size_t cap = 0;         // sample buffers, one per handle
-  hipEvent_t ev_written[MAXH] = {nullptr, nullptr, nullptr, nullptr}, ev_copied[MAXH] = {nullptr, nullptr, nullptr, nullptr};
+  Event ev_written[MAXH], ev_copied[MAXH], pin_ev[STREAM_PIN_SLOTS], ev_direct;   // (pin_ev, ev_direct: the host pushes', below)
+  std::unique_ptr<dvbt_rx> rx[MAXH];
+  DevMem<float2> buf[MAXH]; size_t cap = 0;                    // sample buffers, one per handle
   // host pushes leave through a ring of pinned staging slots: memcpy into a slot, asynchronous H2D on the piece's stream, return.  A push never waits for the
   // device unless the ring has gone round (STREAM_PIN_SLOTS x STREAM_PIN_BYTES of samples are in flight in front of a busy chain: back-pressure).  Allocated at
   // the first host push (a stream fed from device memory never needs it)
-  uint8_t *pin = nullptr; hipEvent_t pin_ev[STREAM_PIN_SLOTS] = {}; bool pin_busy[STREAM_PIN_SLOTS] = {}; int pin_next = 0;
+  PinMem<uint8_t> pin; bool pin_busy[STREAM_PIN_SLOTS] = {}; int pin_next = 0;
   // ... large pushes (>= STREAM_DIRECT_BYTES) are copied straight out of the caller's buffer (the runtime pins the pages: no staging memcpy, which a single
   // host thread cannot do faster than ~20 GB/s); the call then waits for that copy, as the caller's buffer must be free when it returns
-  hipEvent_t ev_direct = nullptr; bool direct_pending = false;
+  bool direct_pending = false;
   long long pos = 0;                                           // samples pushed so far
   // borrow_device_pushes: the samples handed to dvbt_rx_stream_push_device are NOT copied: the stream remembers where they are (regions of the stream in the caller's
   // device memory, neighbours merged) and reads them there -- a piece that lies in one region is decoded in place, everything else (a piece across two regions, the
@@ -115,7 +120,7 @@ struct dvbt_rx_stream {
   int last_handle = 0;                                         // handle of the piece launched last (the next one takes the other)
   std::vector<StreamPiece> inflight;                           // enqueued, not yet harvested (at most two)
   // ---- the walk
-  float2 *wbuf[2] = {nullptr, nullptr}; size_t wcap = 0;       // its own sample buffers (allocated when a walk outgrows buf[0]: twice a piece's)
+  DevMem<float2> wbuf[2]; size_t wcap = 0;                     // its own sample buffers (allocated when a walk outgrows buf[0]: twice a piece's)
   int wh = 0;                                                  // the handle that walks (0; a sharded stream walks a piece on the piece's own handle: the other one may be busy)
   float2 *wb = nullptr; size_t wb_cap = 0; int wb_which = -1;  // the buffer the walk's samples sit in (buf[0] at the stream's beginning), -1: buf[0], else wbuf[wb_which]
   long long wb_begin = 0;                                      // stream sample of wb[0]
@@ -132,11 +137,11 @@ struct dvbt_rx_stream {
   long long w_next_sf = 0;                                     // ... the epoch's superframe the NEXT piece (another rank's) begins with
   std::vector<std::pair<long long, long long>> w_relabel;      // ... (first RS word of a lock period in the walk's stream, label shift of its packets)
   std::deque<StreamChunk> fifo; size_t fifo_off = 0;           // decoded TS of this rank, in order
-  uint8_t *ts_ring = nullptr; TsRing ring; size_t ring_bytes = 0;   // pinned ring the chunks live in (ts_ring.hpp: placement and release); allocated at the first emit
+  PinMem<uint8_t> ts_ring; TsRing ring; size_t ring_bytes = 0;   // pinned ring the chunks live in (ts_ring.hpp: placement and release); allocated at the first emit
   // device output: the decoded TS stays in device memory for the exchange step (dvbt_rccl.inc): chunks that wait (dfifo), chunks an exchange step in flight still
   // reads (dzombie: released when that step has completed), the ring they live in (overflow: own allocations)
-  bool dev_out = false; uint8_t *dring = nullptr; size_t dring_bytes = 0; TsRing dalloc; std::deque<DevChunk> dfifo, dzombie; int dzombie_of[2] = {0, 0};
-  std::vector<std::pair<uint8_t *, size_t>> ts_pool;           // device output: spare TS buffers (a piece's packets are handed over in the buffer they were decoded into, the handle takes a spare)
+  bool dev_out = false; DevMem<uint8_t> dring; size_t dring_bytes = 0; TsRing dalloc; std::deque<DevChunk> dfifo, dzombie; int dzombie_of[2] = {0, 0};
+  std::vector<TsBuf> ts_pool;                                  // device output: spare TS buffers (a piece's packets are handed over in the buffer they were decoded into, the handle takes a spare)
   long long packets_out = 0, bytes_pulled = 0;
   long long first_sf_call = -1, first_q0 = -1;                 // dvbt_rx_stream_info: the stream's first superframe start and first packet
   int status = 0;
@@ -160,28 +165,10 @@ static long long stream_post(const Dims &d)
   return (80ll * 204 * 8 + ibits - 1) / ibits + 3;             // multi.py::post_symbols
 }
 
-static void stream_free_chains(dvbt_rx_stream *s)
+static void stream_free_chains(dvbt_rx_stream *s)   // a stream_setup that failed half way keeps nothing
 {
-  for (int i = 0; i < 2; i++) { if (s->wbuf[i]) (void)hipFree(s->wbuf[i]); s->wbuf[i] = nullptr; }
-  for (int i = 0; i < dvbt_rx_stream::MAXH; i++) {
-    if (s->rx[i]) rx_free(s->rx[i]); s->rx[i] = nullptr;
-    if (s->buf[i]) (void)hipFree(s->buf[i]); s->buf[i] = nullptr;
-    if (s->ev_written[i]) (void)hipEventDestroy(s->ev_written[i]); s->ev_written[i] = nullptr;
-    if (s->ev_copied[i]) (void)hipEventDestroy(s->ev_copied[i]); s->ev_copied[i] = nullptr;
-  }
-}
-static void stream_free(dvbt_rx_stream *s)
-{
-  stream_free_chains(s);
-  for (int i = 0; i < STREAM_PIN_SLOTS; i++) if (s->pin_ev[i]) (void)hipEventDestroy(s->pin_ev[i]);
-  if (s->ev_direct) (void)hipEventDestroy(s->ev_direct);
-  if (s->ts_ring) (void)hipHostFree(s->ts_ring);
-  if (s->pin) (void)hipHostFree(s->pin);
-  for (auto *q : {&s->dfifo, &s->dzombie}) for (DevChunk &c : *q) { if (c.owner) (void)hipFree(c.owner); else if (!c.in_ring && c.data) (void)hipFree(c.data); }
-  for (auto &b : s->ts_pool) (void)hipFree(b.first);
-  s->ts_pool.clear();
-  if (s->dring) (void)hipFree(s->dring);
-  delete s;
+  for (auto &b : s->wbuf) b.reset();
+  for (int i = 0; i < dvbt_rx_stream::MAXH; i++) { s->rx[i].reset(); s->buf[i].reset(); s->ev_written[i].reset(); s->ev_copied[i].reset(); }
 }
 
 // everything that depends on the transmission parameters: dimensions, the two chains, the sample buffers; the stream begins as a walk in buf[0]
@@ -202,9 +189,10 @@ static int stream_setup(dvbt_rx_stream *s)
   s->cap = (size_t)(std::max(s->len0, piece_len) + s->thr + 8 * s->L);
   dvbt_rx_params q = p->rx; q.max_samples = s->cap; q.resample_interp = q.resample_decim = 0; q.launch_graph = 0;   // (every piece has its own cut: nothing to replay)
   for (int i = 0; i < s->nh; i++) {
-    int r = dvbt_rx_create(&q, &s->rx[i]); if (r) { stream_free_chains(s); return r; }
-    if (hipMalloc((void **)&s->buf[i], sizeof(float2) * s->cap) != hipSuccess || hipEventCreateWithFlags(&s->ev_written[i], hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&s->ev_copied[i], hipEventDisableTiming) != hipSuccess) { stream_free_chains(s); return fail(DVBT_ERR_HIP, "dvbt_rx_stream: device allocation failed"); }
+    dvbt_rx *h = nullptr; int r = dvbt_rx_create(&q, &h); if (r) { stream_free_chains(s); return r; }
+    s->rx[i].reset(h);
+    if (s->buf[i].alloc(s->cap) != hipSuccess || s->ev_written[i].create(hipEventDisableTiming) != hipSuccess ||
+        s->ev_copied[i].create(hipEventDisableTiming) != hipSuccess) { stream_free_chains(s); return fail(DVBT_ERR_HIP, "dvbt_rx_stream: device allocation failed"); }
   }
   // the stream's beginning is a walk: fresh blocks, the samples in buf[0]
   s->in_pieces = false; s->have_cur = s->have_next = false;
@@ -228,32 +216,32 @@ extern "C" int dvbt_rx_stream_create(const dvbt_rx_stream_params *p, dvbt_rx_str
                        p->rx.code_rate == DVBT_AUTO ? 0 : p->rx.code_rate, p->rx.guard_interval, p->rx.transmission_mode);
     if (!d.valid) return fail(DVBT_ERR_INVALID, "bad DVB-T parameters");
   }
-  dvbt_rx_stream *s = new dvbt_rx_stream();
+  std::unique_ptr<dvbt_rx_stream> hold(new dvbt_rx_stream()); dvbt_rx_stream *const s = hold.get();   // released on every early return below
   s->prm = *p;
   s->world = p->world > 0 ? p->world : 1; s->rank = p->world > 0 ? p->rank : 0;
   if (s->prm.segment_superframes <= 0) s->prm.segment_superframes = 16;
   s->ring_bytes = p->ts_ring_bytes > 0 ? (size_t)p->ts_ring_bytes : STREAM_TS_RING_DEFAULT;
   s->borrow = p->borrow_device_pushes != 0;
   s->nh = p->chains ? p->chains : 2;
-  if (s->borrow && au) { delete s; return fail(DVBT_ERR_INVALID, "dvbt_rx_stream: borrow_device_pushes and DVBT_AUTO do not go together (the head of an auto-configured stream is replayed from host memory)"); }
-  if (hipEventCreateWithFlags(&s->ev_direct, hipEventDisableTiming) != hipSuccess) { stream_free(s); return fail(DVBT_ERR_HIP, "dvbt_rx_stream: event creation failed"); }
+  if (s->borrow && au) return fail(DVBT_ERR_INVALID, "dvbt_rx_stream: borrow_device_pushes and DVBT_AUTO do not go together (the head of an auto-configured stream is replayed from host memory)");
+  if (s->ev_direct.create(hipEventDisableTiming) != hipSuccess) return fail(DVBT_ERR_HIP, "dvbt_rx_stream: event creation failed");
   // the page-locked buffers are taken here, not at the first delivery / the first host push: page-locking 96 + 32 MB takes ~10 ms, which belongs to the set-up and
   // not into the stream's first piece.  A stream that cannot have its TS ring lives on heap chunks; dvbt_rx_stream_set_device_output gives the ring back
-  if (hipHostMalloc((void **)&s->ts_ring, s->ring_bytes) != hipSuccess) { (void)hipGetLastError(); s->ts_ring = nullptr; s->ring.cap = 0; } else s->ring.cap = s->ring_bytes;
-  if (hipHostMalloc((void **)&s->pin, STREAM_PIN_BYTES * STREAM_PIN_SLOTS) != hipSuccess) { (void)hipGetLastError(); s->pin = nullptr; }
+  if (s->ts_ring.alloc(s->ring_bytes) != hipSuccess) { (void)hipGetLastError(); s->ring.cap = 0; } else s->ring.cap = s->ring_bytes;
+  if (s->pin.alloc(STREAM_PIN_BYTES * STREAM_PIN_SLOTS) != hipSuccess) (void)hipGetLastError();
   else for (int i = 0; i < STREAM_PIN_SLOTS; i++)
-    if (hipEventCreateWithFlags(&s->pin_ev[i], hipEventDisableTiming) != hipSuccess) { stream_free(s); return fail(DVBT_ERR_HIP, "dvbt_rx_stream: event creation failed"); }
+    if (s->pin_ev[i].create(hipEventDisableTiming) != hipSuccess) return fail(DVBT_ERR_HIP, "dvbt_rx_stream: event creation failed");
   if (au) {
     // TPS auto-configuration (gr-dvbt's TODO.txt:28 "Autodetect transmission params"): nothing that depends on constellation / hierarchy / code rate is built
     // yet.  The TPS word of a frame is complete 68 symbols after a frame start, a frame start is at most 67 symbols away, the acquisition takes a few: two
     // frames and a margin hold one whole frame for certain
     const Dims d0 = make_dims(0, 0, 0, p->rx.guard_interval, p->rx.transmission_mode);
     s->auto_pending = true; s->auto_need = (long long)(2 * 68 + 24) * (d0.N + d0.cp) + 2 * d0.N + d0.cp + 16;
-    *out = s;
+    *out = hold.release();
     return DVBT_OK;
   }
-  r = stream_setup(s); if (r) { stream_free(s); return r; }
-  *out = s;
+  r = stream_setup(s); if (r) return r;
+  *out = hold.release();
   return DVBT_OK;
 }
 
@@ -330,28 +318,28 @@ static int stream_emit_bytes(dvbt_rx_stream *s, dvbt_rx *h, const uint8_t *dev, 
 {
   if (!len) return DVBT_OK;
   if (s->dev_out && steal && len >= (1u << 20) && dev >= h->ts_out && dev + len <= h->ts_out + h->vit_cap) {
-    uint8_t *fresh = nullptr;
-    for (size_t i = 0; i < s->ts_pool.size(); i++) if (s->ts_pool[i].second >= h->vit_cap) { fresh = s->ts_pool[i].first; s->ts_pool.erase(s->ts_pool.begin() + i); break; }
-    if (!fresh && hipMalloc((void **)&fresh, h->vit_cap) != hipSuccess) { (void)hipGetLastError(); fresh = nullptr; }
+    DevMem<uint8_t> fresh;
+    for (size_t i = 0; i < s->ts_pool.size(); i++) if (s->ts_pool[i].cap >= h->vit_cap) { fresh = std::move(s->ts_pool[i].mem); s->ts_pool.erase(s->ts_pool.begin() + i); break; }
+    if (!fresh && fresh.alloc(h->vit_cap) != hipSuccess) (void)hipGetLastError();
     if (fresh) {
-      DevChunk c; c.first_packet = label; c.len = len; c.off = 0; c.in_ring = false; c.data = const_cast<uint8_t *>(dev); c.owner = h->ts_out; c.owner_cap = h->vit_cap;
-      h->ts_out = fresh;
+      DevChunk c; c.first_packet = label; c.len = len; c.off = 0; c.in_ring = false; c.data = const_cast<uint8_t *>(dev); c.stolen.mem = std::move(h->ts_out); c.stolen.cap = h->vit_cap;
+      h->ts_out = std::move(fresh);
       s->packets_out += (long long)(len / 188);
-      s->dfifo.push_back(c);
+      s->dfifo.push_back(std::move(c));
       return DVBT_OK;
     }
   }
   if (s->dev_out) {
     // the packets stay on the device: into the stream's device ring (own allocation when it is full), behind the handle's decode
-    if (!s->dring) { if (hipMalloc((void **)&s->dring, s->dring_bytes) != hipSuccess) { (void)hipGetLastError(); s->dring = nullptr; s->dalloc.cap = 0; } else s->dalloc.cap = s->dring_bytes; }
+    if (!s->dring) { if (s->dring.alloc(s->dring_bytes) != hipSuccess) { (void)hipGetLastError(); s->dalloc.cap = 0; } else s->dalloc.cap = s->dring_bytes; }
     DevChunk c; c.first_packet = label; c.len = len; c.off = 0; c.in_ring = false; c.data = nullptr;
     const size_t at = s->dring ? s->dalloc.place(len) : TsRing::NONE;
     if (at != TsRing::NONE) { c.data = s->dring + at; c.in_ring = true; }
-    else HIPCHK(hipMalloc((void **)&c.data, len));
+    else { HIPCHK(c.own.alloc(len)); c.data = c.own; }
     HIPCHK(hipMemcpyAsync(c.data, dev, len, hipMemcpyDeviceToDevice, h->own_stream));
     HIPCHK(hipStreamSynchronize(h->own_stream));                   // (the handle's TS buffer is reused by its next piece; an exchange step may read the chunk at once)
     s->packets_out += (long long)(len / 188);
-    s->dfifo.push_back(c);
+    s->dfifo.push_back(std::move(c));
     return DVBT_OK;
   }
   StreamChunk c; c.first_packet = label; c.len = len; c.in_ring = false;
@@ -476,7 +464,7 @@ static int stream_fetch_bits(dvbt_rx_stream *s, dvbt_rx *h, long long from_word 
 static int walk_flush(dvbt_rx_stream *s, bool eos, long long stop_start /* the head of an epoch: calls from here on belong to its pieces */, bool all_words = false,
                       long long clip8_word = -1 /* sharded head: its share ends at the first transmitted NSYNC at or behind this word (the pieces trim on that grid) */)
 {
-  dvbt_rx *h = s->rx[s->wh];
+  dvbt_rx *h = s->rx[s->wh].get();
   hipStream_t st = h->own_stream;
   // final: below the last multiple of 3264 bytes (the next delivering period realigns there, convolutional_deinterleaver_impl.cc:109-120); at the stream's end:
   // the even item count of the whole stream (set_output_multiple(2))
@@ -526,11 +514,11 @@ static int stream_begin_next(dvbt_rx_stream *s, const float2 *from_mem, long lon
 // the walk's samples move to the front of the other walk buffer (what lies in front of `keep_from` is final)
 static int walk_rebase(dvbt_rx_stream *s, long long keep_from /* stream sample */)
 {
-  dvbt_rx *h = s->rx[s->wh];
+  dvbt_rx *h = s->rx[s->wh].get();
   hipStream_t st = h->own_stream;
   if (!s->wbuf[0]) {
     s->wcap = (size_t)((long long)s->nh * (long long)s->cap + s->thr);
-    for (int i = 0; i < 2; i++) if (hipMalloc((void **)&s->wbuf[i], sizeof(float2) * s->wcap) != hipSuccess) return fail(DVBT_ERR_HIP, "dvbt_rx_stream: walk buffer allocation failed");
+    for (int i = 0; i < 2; i++) if (s->wbuf[i].alloc(s->wcap) != hipSuccess) return fail(DVBT_ERR_HIP, "dvbt_rx_stream: walk buffer allocation failed");
   }
   { int r = walk_fill(s); if (r) return r; }
   const int to = s->wb_which < 0 ? 0 : (s->wb_which ^ 1);
@@ -547,7 +535,7 @@ static DescrState descr_at(long long bw) { DescrState d; d.base = 2 * (bw / 16);
 // one window of the walk over wb = [wb_begin, pos); last: the stream ends here
 static int stream_walk(dvbt_rx_stream *s, bool last)
 {
-  dvbt_rx *h = s->rx[s->wh];
+  dvbt_rx *h = s->rx[s->wh].get();
   hipStream_t st = h->own_stream;
   const long long S = s->prm.segment_superframes;
   { int r = walk_fill(s); if (r) return r; }
@@ -734,7 +722,7 @@ static int stream_piece_samples(dvbt_rx_stream *s, const StreamPiece &pc, hipStr
 // counter is preset to that number: it is looked at again only at that frame's end (an epoch on a frame boundary: si_start = 0), and every later frame is complete)
 static int walk_preset_tps(dvbt_rx_stream *s, long long call, bool late = false)
 {
-  dvbt_rx *h = s->rx[s->wh];
+  dvbt_rx *h = s->rx[s->wh].get();
   // place in the superframe of the symbol BEFORE the window's first one; the epoch's superframe start (sf_call) sits `delay` symbols behind a transmitted one
   const long long p = ((call - 1 - s->sf_call + s->delay) % 272 + 272) % 272;
   TpsState t; memset(&t, 0, sizeof t);
@@ -748,7 +736,7 @@ static int walk_preset_tps(dvbt_rx_stream *s, long long call, bool late = false)
 // the walk continues the epoch inside piece `pc`: the piece's cut, the epoch's counters, the descrambler's next call; the samples are in wb = [pc.begin, ...)
 static int walk_from_piece(dvbt_rx_stream *s, const StreamPiece &pc)
 {
-  dvbt_rx *h0 = s->rx[s->wh];
+  dvbt_rx *h0 = s->rx[s->wh].get();
   const long long e0 = pc.first_sf * s->wsf, e0b = e0 * 204;
   s->in_pieces = false;
   s->wb_begin = pc.begin; s->w_hist = pc.skip;
@@ -793,7 +781,7 @@ static int stream_enter_walk(dvbt_rx_stream *s, const StreamPiece &pc_in)
   hipStream_t st = s->rx[s->wh]->own_stream;
   if (!s->wbuf[0]) {   // the walk's own buffers
     s->wcap = (size_t)((long long)s->nh * (long long)s->cap + s->thr);
-    for (int i = 0; i < 2; i++) if (hipMalloc((void **)&s->wbuf[i], sizeof(float2) * s->wcap) != hipSuccess) return fail(DVBT_ERR_HIP, "dvbt_rx_stream: walk buffer allocation failed");
+    for (int i = 0; i < 2; i++) if (s->wbuf[i].alloc(s->wcap) != hipSuccess) return fail(DVBT_ERR_HIP, "dvbt_rx_stream: walk buffer allocation failed");
   }
   const long long have_k = std::min(s->pos, pc.launch_at) - pc.begin;            // what the piece's own buffer holds
   long long total = have_k;
@@ -840,7 +828,7 @@ static int stream_enter_walk(dvbt_rx_stream *s, const StreamPiece &pc_in)
 // a piece has finished on the device: trim and queue its packets
 static int stream_harvest(dvbt_rx_stream *s, StreamPiece &pc)
 {
-  dvbt_rx *h = s->rx[pc.handle];
+  dvbt_rx *h = s->rx[pc.handle].get();
   { int r = dvbt_rx_segment_finish(h, &pc.rep); if (r) return r; }
   if (!s->in_pieces) return DVBT_OK;                                     // (dropped: a walk has taken over in front of it)
   bool lost_inside = (pc.rep.status & 2) && pc.rep.resume_sample && pc.rep.resume_sample < pc.n - pc.skip - 4 * s->L;
@@ -943,7 +931,7 @@ static int stream_launch(dvbt_rx_stream *s)
 {
   StreamPiece pc = s->cur;
   const int hi = pc.handle;
-  dvbt_rx *h = s->rx[hi];
+  dvbt_rx *h = s->rx[hi].get();
   hipStream_t st = h->own_stream;
   pc.n = std::min(pc.end, s->pos) - pc.begin;
   const long long e0 = pc.first_sf * s->wsf;
@@ -973,7 +961,7 @@ static int stream_finish_in_pieces(dvbt_rx_stream *s)
   s->wb = s->buf[pc.handle]; s->wb_cap = s->cap; s->wb_which = -1; s->wh = 0; s->wb_filled = s->borrow ? pc.begin : s->pos;
   s->wb_begin = pc.begin;
   { int r = walk_fill(s); if (r) return r; }                               // (borrowed samples: gathered into the piece's buffer)
-  { int r = stream_probe_skip(s, s->rx[0], s->wb, s->pos - pc.begin, s->rx[0]->own_stream, &pc.skip, STREAM_WALK_SKIP_MAX); if (r) return r; }
+  { int r = stream_probe_skip(s, s->rx[0].get(), s->wb, s->pos - pc.begin, s->rx[0]->own_stream, &pc.skip, STREAM_WALK_SKIP_MAX); if (r) return r; }
   { int r = walk_from_piece(s, pc); if (r) return r; }
   if (s->world > 1) s->w_clip_hi = 1ll << 61;                             // the stream's last piece: everything behind its first packet is this rank's
   s->have_cur = false;
@@ -1028,9 +1016,9 @@ static int stream_append(dvbt_rx_stream *s, const float2 *src, size_t n, bool de
           HIPCHK(hipEventRecord(s->ev_direct, st)); s->direct_pending = true;
         } else {
           if (!s->pin) {   // (it could not be had at create: once more, now that it is needed)
-            if (hipHostMalloc((void **)&s->pin, STREAM_PIN_BYTES * STREAM_PIN_SLOTS) != hipSuccess) return fail(DVBT_ERR_HIP, "dvbt_rx_stream: pinned staging allocation failed");
+            if (s->pin.alloc(STREAM_PIN_BYTES * STREAM_PIN_SLOTS) != hipSuccess) return fail(DVBT_ERR_HIP, "dvbt_rx_stream: pinned staging allocation failed");
             for (int i = 0; i < STREAM_PIN_SLOTS; i++)
-              if (hipEventCreateWithFlags(&s->pin_ev[i], hipEventDisableTiming) != hipSuccess) return fail(DVBT_ERR_HIP, "dvbt_rx_stream: event creation failed");
+              if (s->pin_ev[i].create(hipEventDisableTiming) != hipSuccess) return fail(DVBT_ERR_HIP, "dvbt_rx_stream: event creation failed");
           }
           for (size_t done = 0; done < take;) {
             const size_t n1 = std::min(take - done, slot_samples);
@@ -1071,7 +1059,7 @@ static int stream_autodetect(dvbt_rx_stream *s)
   int r = dvbt_rx_create(&q, &probe); if (r) return r;
   dvbt_rx_report rep;
   r = dvbt_rx_segment_run(probe, s->head.data(), s->head.size(), &rep);
-  rx_free(probe);
+  dvbt_rx_destroy(probe);
   if (r) return r;
   s->auto_tries++;
   if (!rep.tps_valid) return 0;
@@ -1183,7 +1171,7 @@ extern "C" int dvbt_rx_stream_set_device_output(dvbt_rx_stream *s, size_t ring_b
   if (!s) return fail(DVBT_ERR_INVALID, "null handle");
   if (s->pos || s->packets_out) return fail(DVBT_ERR_STATE, "dvbt_rx_stream_set_device_output: before the first push");
   s->dev_out = true; s->dring_bytes = ring_bytes ? ring_bytes : (64u << 20);
-  if (s->ts_ring) { (void)hipHostFree(s->ts_ring); s->ts_ring = nullptr; s->ring.cap = 0; }   // (nothing is delivered through the host ring any more)
+  s->ts_ring.reset(); s->ring.cap = 0;  // (nothing is delivered through the host ring any more)
   return DVBT_OK;
 }
 
@@ -1201,14 +1189,14 @@ static int stream_take_device(dvbt_rx_stream *s, uint8_t *dst, int max_packets, 
   HIPCHK(hipMemcpyAsync(dst, c.data + c.off, take, hipMemcpyDeviceToDevice, st));
   c.off += take; s->bytes_pulled += (long long)take;
   if (tok) { tok->take = take; tok->moved = false; }
-  if (c.off == c.len) { s->dzombie.push_back(c); s->dzombie_of[buffer]++; s->dfifo.pop_front(); if (tok) tok->moved = true; }
+  if (c.off == c.len) { s->dzombie.push_back(std::move(c)); s->dzombie_of[buffer]++; s->dfifo.pop_front(); if (tok) tok->moved = true; }
   return DVBT_OK;
 }
 // the exchange step that was to carry the run did not take place: the run is the stream's oldest waiting one again
 static void stream_untake_device(dvbt_rx_stream *s, int buffer, const DevTake &tok)
 {
   if (!tok.take) return;
-  if (tok.moved && !s->dzombie.empty() && s->dzombie_of[buffer] > 0) { s->dfifo.push_front(s->dzombie.back()); s->dzombie.pop_back(); s->dzombie_of[buffer]--; }
+  if (tok.moved && !s->dzombie.empty() && s->dzombie_of[buffer] > 0) { s->dfifo.push_front(std::move(s->dzombie.back())); s->dzombie.pop_back(); s->dzombie_of[buffer]--; }
   if (s->dfifo.empty()) return;
   DevChunk &c = s->dfifo.front();
   c.off -= std::min(c.off, tok.take); s->bytes_pulled -= (long long)tok.take;
@@ -1216,9 +1204,9 @@ static void stream_untake_device(dvbt_rx_stream *s, int buffer, const DevTake &t
 static void stream_release_taken(dvbt_rx_stream *s, int buffer)
 {
   for (; s->dzombie_of[buffer] > 0 && !s->dzombie.empty(); s->dzombie_of[buffer]--) {
-    DevChunk c = s->dzombie.front(); s->dzombie.pop_front();
-    if (c.owner) { s->ts_pool.push_back({c.owner, c.owner_cap}); continue; }
-    if (!c.in_ring) { (void)hipFree(c.data); continue; }
+    DevChunk c = std::move(s->dzombie.front()); s->dzombie.pop_front();
+    if (c.stolen.mem) { s->ts_pool.push_back(std::move(c.stolen)); continue; }
+    if (!c.in_ring) continue;                                        // (its own allocation goes with c)
     size_t next = TsRing::NONE;                                      // the ring's tail moves to the next chunk that lives in it (chunks leave in the order they came)
     for (const DevChunk &z : s->dzombie) if (z.in_ring) { next = (size_t)(z.data - s->dring); break; }
     if (next == TsRing::NONE) for (const DevChunk &z : s->dfifo) if (z.in_ring) { next = (size_t)(z.data - s->dring); break; }
@@ -1270,7 +1258,7 @@ extern "C" int dvbt_rx_stream_viterbi_proof(const dvbt_rx_stream *s, dvbt_viterb
   if (!s || !out) return fail(DVBT_ERR_INVALID, "null argument");
   out->chunks = out->decoded_again = out->sequential = 0; out->not_proven = -1;
   for (int i = 0; i < s->nh; i++) {
-    const dvbt_rx *h = s->rx[i];
+    const dvbt_rx *h = s->rx[i].get();
     if (!h || !h->vproof.ctl) continue;
     int acc[3] = {0, 0, 0};
     HIPCHK(hipMemcpy(acc, h->vproof.ctl + V3_CTL_ACC, sizeof acc, hipMemcpyDeviceToHost));
@@ -1326,5 +1314,5 @@ extern "C" void dvbt_rx_stream_destroy(dvbt_rx_stream *s)
 {
   if (!s) return;
   for (int i = 0; i < dvbt_rx_stream::MAXH; i++) if (s->rx[i] && s->rx[i]->own_stream) (void)hipStreamSynchronize(s->rx[i]->own_stream);
-  stream_free(s);
+  delete s;
 }

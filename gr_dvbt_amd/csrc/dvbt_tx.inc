@@ -88,35 +88,28 @@ inline std::vector<uint8_t> rs_encoder_rows()
   return enc;
 }
 
-template <class T> static int tx_upload(const std::vector<T> &v, T *&dptr) { return upload(v, &dptr); }
-
 }  // namespace
 
 struct dvbt_tx {
+  // Members are released in reverse order of declaration: the stream and the event stand in front of the buffers that work queued on them uses, so the buffers go
+  // first, then the event, the stream last.  tt holds views into T and the tables below.
   dvbt_tx_params p;
   Dims d;
   Tables T;                           // twiddles, symbol interleaver H / H^-1, constellation points
   TxSymParams sp;
   TxTables tt;
-  uint8_t *prbs = nullptr, *enc_tab = nullptr;
-  uint16_t *pay = nullptr, *pil = nullptr, *tps = nullptr;
-  float *pref = nullptr, *tps_base = nullptr, *tps_sign = nullptr;
-  uint8_t *rs[2] = {nullptr, nullptr}; int cur = 0;       // RS buffers: [history | this call's packets], ping-pong from call to call
+  Stream s;                           // the host entry's stream
+  Event ev; hipStream_t last_stream = nullptr; bool have_ev = false;
+  DevMem<uint8_t> prbs, enc_tab;
+  DevMem<uint16_t> pay, pil, tps;
+  DevMem<float> pref, tps_base, tps_sign;
+  DevMem<uint8_t> rs[2]; int cur = 0;                     // RS buffers: [history | this call's packets], ping-pong from call to call
   int hist = 0;
   long long packets = 0, symbols = 0, last_np = 0, last_nsym = 0;
   long long max_sym = 0;
-  float2 *carriers = nullptr;
-  uint8_t *dts = nullptr; DevBuf diq;                    // staging of the host entry
-  hipStream_t s = nullptr;                               // the host entry's stream
-  hipEvent_t ev = nullptr; hipStream_t last_stream = nullptr; bool have_ev = false;
-  ~dvbt_tx()
-  {
-    if (have_ev) (void)hipEventSynchronize(ev);
-    void *all[] = {prbs, enc_tab, pay, pil, tps, pref, tps_base, tps_sign, rs[0], rs[1], carriers, dts};
-    for (void *q : all) if (q) (void)hipFree(q);
-    if (ev) (void)hipEventDestroy(ev);
-    if (s) (void)hipStreamDestroy(s);
-  }
+  DevMem<float2> carriers;
+  DevMem<uint8_t> dts; DevBuf diq;                       // staging of the host entry
+  ~dvbt_tx() { if (have_ev) (void)hipEventSynchronize(ev); }   // the last call's work has left the buffers before any of them goes
 };
 
 static long long tx_symbols_after(const dvbt_tx *h, long long npackets)
@@ -149,29 +142,27 @@ extern "C" int dvbt_tx_create(const dvbt_tx_params *p, dvbt_tx **out)
   if (p->device < 0 || p->device >= ndev) return fail(DVBT_ERR_INVALID, "no such device");
   HIPCHK(hipSetDevice(p->device));
 
-  dvbt_tx *h = new dvbt_tx();
+  std::unique_ptr<dvbt_tx> hold(new dvbt_tx()); dvbt_tx *const h = hold.get();   // released on every early return below
   h->p = *p; h->d = d; h->T.d = d;
-#define TXCHK(x) do { int r_ = (x); if (r_) { delete h; return r_; } } while (0)
-#define TXHIP(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { delete h; return fail(DVBT_ERR_HIP, std::string(#x) + ": " + hipGetErrorString(e_)); } } while (0)
-  TXHIP(hipStreamCreateWithFlags(&h->s, hipStreamNonBlocking));
-  TXHIP(hipEventCreateWithFlags(&h->ev, hipEventDisableTiming));
-  TXCHK(h->T.build_fft(d.N));
-  TXCHK(h->T.build_inner(1.0f));
+  HIPCHK(h->s.create(hipStreamNonBlocking));
+  HIPCHK(h->ev.create(hipEventDisableTiming));
+  if ((r = h->T.build_fft(d.N))) return r;
+  if ((r = h->T.build_inner(1.0f))) return r;
 
   // outer coder tables: the PRBS of one dispersal group and the RS encoder's feedback rows
-  TXCHK(tx_upload(energy_prbs(), h->prbs));
-  TXCHK(tx_upload(rs_encoder_rows(), h->enc_tab));
+  if ((r = upload(energy_prbs(), h->prbs))) return r;
+  if ((r = upload(rs_encoder_rows(), h->enc_tab))) return r;
 
   // carriers, pilot values, TPS
   TxClasses cl;
-  TXCHK(tx_carrier_classes(d, cl));
-  TXCHK(tx_upload(cl.pay, h->pay)); TXCHK(tx_upload(cl.pil, h->pil));
+  if ((r = tx_carrier_classes(d, cl))) return r;
+  if ((r = upload(cl.pay, h->pay))) return r; if ((r = upload(cl.pil, h->pil))) return r;
   const std::vector<float> pref = pilot_ref_table(d);
-  TXCHK(tx_upload(pref, h->pref));
+  if ((r = upload(pref, h->pref))) return r;
   TxTps tp;
   tx_tps_tables(d, d.code_rate, p->include_cell_id, p->cell_id, pref, tp);
   const std::vector<uint16_t> &t16 = tp.car;
-  TXCHK(tx_upload(tp.car, h->tps)); TXCHK(tx_upload(tp.base, h->tps_base)); TXCHK(tx_upload(tp.sign, h->tps_sign));
+  if ((r = upload(tp.car, h->tps))) return r; if ((r = upload(tp.base, h->tps_base))) return r; if ((r = upload(tp.sign, h->tps_sign))) return r;
 
   // symbol kernel parameters
   TxSymParams &sp = h->sp;
@@ -197,15 +188,13 @@ extern "C" int dvbt_tx_create(const dvbt_tx_params *p, dvbt_tx **out)
   // buffers: RS history covers the interleaver's 2244 bytes plus the bits of a symbol not yet emitted (+ the 6 in front of them)
   h->hist = (2244 + d.info_bits_per_symbol / 8 + 3 + 15) & ~15;
   const size_t rs_bytes = (size_t)h->hist + p->max_packets * 204;
-  for (int i = 0; i < 2; i++) { TXHIP(hipMalloc((void **)&h->rs[i], rs_bytes + 64)); TXHIP(hipMemsetAsync(h->rs[i], 0, rs_bytes + 64, h->s)); }
+  for (int i = 0; i < 2; i++) { HIPCHK(h->rs[i].alloc(rs_bytes + 64)); HIPCHK(hipMemsetAsync(h->rs[i], 0, rs_bytes + 64, h->s)); }
   h->max_sym = ((long long)p->max_packets * 1632 + d.info_bits_per_symbol - 1) / d.info_bits_per_symbol;
-  if (p->keep_carriers) TXHIP(hipMalloc((void **)&h->carriers, (size_t)h->max_sym * d.N * sizeof(float2) + 64));
-  TXCHK(set_lds(d.N == 8192 ? (const void *)tx_symbol_kernel<8192> : (const void *)tx_symbol_kernel<2048>, tx_symbol_lds_bytes(d.N, d.payload)));
-  TXCHK(tx_rewind(h));
-  TXHIP(hipStreamSynchronize(h->s));
-#undef TXCHK
-#undef TXHIP
-  *out = h;
+  if (p->keep_carriers) HIPCHK(h->carriers.alloc((size_t)h->max_sym * d.N + 8));
+  if ((r = set_lds(d.N == 8192 ? (const void *)tx_symbol_kernel<8192> : (const void *)tx_symbol_kernel<2048>, tx_symbol_lds_bytes(d.N, d.payload)))) return r;
+  if ((r = tx_rewind(h))) return r;
+  HIPCHK(hipStreamSynchronize(h->s));
+  *out = hold.release();
   return DVBT_OK;
 }
 
@@ -222,7 +211,7 @@ static int tx_enqueue(dvbt_tx *h, const void *ts, long long np, void *iq, long l
   const int nxt = h->cur ^ 1;
   const long long nblk = (np + TX_OUTER_PK - 1) / TX_OUTER_PK;
   hipLaunchKernelGGL(tx_outer_kernel, dim3((unsigned)(nblk + 1)), dim3(TX_OUTER_PK), 0, st, (const uint8_t *)ts, np, (long long)h->p.first_packet + h->packets,
-                     (const uint8_t *)h->prbs, (const uint4 *)h->enc_tab, (const uint8_t *)h->rs[h->cur], (long long)h->hist + h->last_np * 204, h->hist, h->rs[nxt]);
+                     (const uint8_t *)h->prbs, (const uint4 *)h->enc_tab.get(), (const uint8_t *)h->rs[h->cur], (long long)h->hist + h->last_np * 204, h->hist, h->rs[nxt]);
   HIPCHK(hipGetLastError());
   if (nsym > 0) {
     TxSymParams sp = h->sp;
@@ -272,7 +261,7 @@ extern "C" int dvbt_tx_run(dvbt_tx *h, const void *ts_host, size_t npackets, voi
   if (npackets == 0) { h->last_nsym = 0; return DVBT_OK; }
   HIPCHK(hipSetDevice(h->p.device));
   const size_t nout = (size_t)nsym * (size_t)(h->d.N + h->d.cp);
-  if (!h->dts) HIPCHK(hipMalloc((void **)&h->dts, h->p.max_packets * 188 + 64));
+  if (!h->dts) HIPCHK(h->dts.alloc(h->p.max_packets * 188 + 64));
   if (h->have_ev && h->last_stream != h->s) HIPCHK(hipStreamWaitEvent(h->s, h->ev, 0));
   r = h->diq.reserve(nout * sizeof(float2)); if (r) return r;
   HIPCHK(hipMemcpyAsync(h->dts, ts_host, npackets * 188, hipMemcpyHostToDevice, h->s));

@@ -10,16 +10,15 @@ inline bool misaligned(const void *p, unsigned a) { return ((uintptr_t)p & (a - 
 }
 
 // ============================================================================ T1 energy_dispersal
-struct dvbt_energy_dispersal { dvbt_energy_dispersal_params p; BlockCtx c; uint8_t *prbs = nullptr; PinBuf probe;
-                               ~dvbt_energy_dispersal() { if (prbs) (void)hipFree(prbs); } };
+struct dvbt_energy_dispersal { dvbt_energy_dispersal_params p; BlockCtx c; DevMem<uint8_t> prbs; PinBuf probe; };
 extern "C" int dvbt_energy_dispersal_create(const dvbt_energy_dispersal_params *p, dvbt_energy_dispersal **out)
 {
   BLK_CREATE_PROLOGUE(dvbt_energy_dispersal);
   h->p = *p;
-  if (p->nblocks <= 0 || p->nblocks > 4096) BLK_FAIL(DVBT_ERR_INVALID, "nblocks must be in [1, 4096]");
-  BLK_CHK(upload(energy_prbs(), &h->prbs));
-  BLK_CHK(h->probe.reserve(188));
-  *out = h; return DVBT_OK;
+  if (p->nblocks <= 0 || p->nblocks > 4096) return fail(DVBT_ERR_INVALID, "nblocks must be in [1, 4096]");
+  WCHK(upload(energy_prbs(), h->prbs));
+  WCHK(h->probe.reserve(188));
+  *out = hold.release(); return DVBT_OK;
 }
 extern "C" int dvbt_energy_dispersal_forecast(const dvbt_energy_dispersal *h, int n, int *req)
 { if (!h || !req) return DVBT_ERR_INVALID; *req = 8 * 189 * h->p.nblocks * n; return DVBT_OK; }     // :86-91
@@ -67,15 +66,15 @@ extern "C" int dvbt_energy_dispersal_work_device(dvbt_energy_dispersal *h, int n
 extern "C" void dvbt_energy_dispersal_destroy(dvbt_energy_dispersal *h) { delete h; }
 
 // ============================================================================ T2 reed_solomon_enc
-struct dvbt_reed_solomon_enc { dvbt_reed_solomon_enc_params p; BlockCtx c; uint8_t *enc = nullptr; ~dvbt_reed_solomon_enc() { if (enc) (void)hipFree(enc); } };
+struct dvbt_reed_solomon_enc { dvbt_reed_solomon_enc_params p; BlockCtx c; DevMem<uint8_t> enc; };
 extern "C" int dvbt_reed_solomon_enc_create(const dvbt_reed_solomon_enc_params *p, dvbt_reed_solomon_enc **out)
 {
   BLK_CREATE_PROLOGUE(dvbt_reed_solomon_enc);
   h->p = *p;
   if (p->p != 2 || p->m != 8 || p->gfpoly != 0x11d || p->n != 255 || p->k != 239 || p->t != 8 || p->s != 51 || p->blocks <= 0 || p->blocks > 4096)
-    BLK_FAIL(DVBT_ERR_INVALID, "only RS(255,239,t=8) over GF(2^8)/0x11d shortened by 51 (the DVB-T outer code), blocks in [1, 4096]");
-  BLK_CHK(upload(rs_encoder_rows(), &h->enc));
-  *out = h; return DVBT_OK;
+    return fail(DVBT_ERR_INVALID, "only RS(255,239,t=8) over GF(2^8)/0x11d shortened by 51 (the DVB-T outer code), blocks in [1, 4096]");
+  WCHK(upload(rs_encoder_rows(), h->enc));
+  *out = hold.release(); return DVBT_OK;
 }
 extern "C" int dvbt_reed_solomon_enc_forecast(const dvbt_reed_solomon_enc *, int n, int *req) { if (req) *req = n; return DVBT_OK; }   // :58-62
 static int rs_enc_call(dvbt_reed_solomon_enc *h, int nout, int nin, const void *in, void *out, dvbt_sideband *sb, bool dev, hipStream_t s)
@@ -87,7 +86,7 @@ static int rs_enc_call(dvbt_reed_solomon_enc *h, int nout, int nin, const void *
   const void *src = in; void *o = out;
   if (!dev) { WCHK(h->c.put(h->c.din, in, (size_t)npk * 188)); WCHK(h->c.dout.reserve((size_t)npk * 204)); src = h->c.din.p; o = h->c.dout.p; }
   hipLaunchKernelGGL(txb_rs_enc_kernel, dim3((unsigned)((npk + TX_OUTER_PK - 1) / TX_OUTER_PK)), dim3(TX_OUTER_PK), 0, s, (const uint8_t *)src, npk,
-                     (const uint4 *)h->enc, (uint8_t *)o);
+                     (const uint4 *)h->enc.get(), (uint8_t *)o);
   HIPCHK(hipGetLastError());
   if (!dev) { WCHK(h->c.get(out, h->c.dout.p, (size_t)npk * 204)); WCHK(h->c.sync()); }
   if (sb) sb->n_consumed = n;
@@ -107,20 +106,19 @@ extern "C" void dvbt_reed_solomon_enc_destroy(dvbt_reed_solomon_enc *h) { delete
 
 // ============================================================================ T3 convolutional_interleaver
 // hist[2]: the last (I-1) M I input bytes of the stream (ping-pong: the call reads hist[cur], its kernel writes hist[cur ^ 1])
-struct dvbt_convolutional_interleaver { dvbt_convolutional_interleaver_params p; BlockCtx c; uint8_t *hist[2] = {nullptr, nullptr}; int cur = 0, H = 0;
-                                        ~dvbt_convolutional_interleaver() { for (uint8_t *q : hist) if (q) (void)hipFree(q); } };
+struct dvbt_convolutional_interleaver { dvbt_convolutional_interleaver_params p; BlockCtx c; DevMem<uint8_t> hist[2]; int cur = 0, H = 0; };
 extern "C" int dvbt_convolutional_interleaver_create(const dvbt_convolutional_interleaver_params *p, dvbt_convolutional_interleaver **out)
 {
   BLK_CREATE_PROLOGUE(dvbt_convolutional_interleaver);
   h->p = *p;
   if (p->blocks <= 0 || p->I <= 0 || p->M < 0 || (long long)p->I * p->blocks > (1 << 20) || (long long)(p->I - 1) * p->M * p->I > (1 << 26) || (p->I * p->blocks) % 4)
-    BLK_FAIL(DVBT_ERR_INVALID, "convolutional_interleaver: blocks, I >= 1, M >= 0, I * blocks a multiple of 4 (at most 2^20), (I - 1) M I at most 2^26");
+    return fail(DVBT_ERR_INVALID, "convolutional_interleaver: blocks, I >= 1, M >= 0, I * blocks a multiple of 4 (at most 2^20), (I - 1) M I at most 2^26");
   h->H = (p->I - 1) * p->M * p->I;
   for (int i = 0; i < 2; i++) {
-    if (hipMalloc((void **)&h->hist[i], (size_t)h->H + 64) != hipSuccess) BLK_FAIL(DVBT_ERR_HIP, "hipMalloc (convolutional_interleaver history)");
-    if (hipMemset(h->hist[i], 0, (size_t)h->H + 64) != hipSuccess) BLK_FAIL(DVBT_ERR_HIP, "hipMemset (convolutional_interleaver history)");
+    if (h->hist[i].alloc((size_t)h->H + 64) != hipSuccess) return fail(DVBT_ERR_HIP, "hipMalloc (convolutional_interleaver history)");
+    if (hipMemset(h->hist[i], 0, (size_t)h->H + 64) != hipSuccess) return fail(DVBT_ERR_HIP, "hipMemset (convolutional_interleaver history)");
   }
-  *out = h; return DVBT_OK;
+  *out = hold.release(); return DVBT_OK;
 }
 // sync_interpolator(I * blocks): noutput bytes need noutput / (I * blocks) items
 extern "C" int dvbt_convolutional_interleaver_forecast(const dvbt_convolutional_interleaver *h, int n, int *req)
@@ -159,16 +157,15 @@ extern "C" void dvbt_convolutional_interleaver_destroy(dvbt_convolutional_interl
 
 // ============================================================================ T4 inner_coder
 // prev[2]: the last input byte of the stream, whose low 6 bits are the encoder's register (ping-pong, as hist above)
-struct dvbt_inner_coder { dvbt_inner_coder_params p; BlockCtx c; Dims d; TxbCoderParams cp; uint8_t *prev = nullptr; int cur = 0;
-                          ~dvbt_inner_coder() { if (prev) (void)hipFree(prev); } };
+struct dvbt_inner_coder { dvbt_inner_coder_params p; BlockCtx c; Dims d; TxbCoderParams cp; DevMem<uint8_t> prev; int cur = 0; };
 extern "C" int dvbt_inner_coder_create(const dvbt_inner_coder_params *p, dvbt_inner_coder **out)
 {
   BLK_CREATE_PROLOGUE(dvbt_inner_coder);
   h->p = *p;
   h->d = make_dims(p->constellation, p->hierarchy, p->code_rate, 0, 0);
-  if (!h->d.valid) BLK_FAIL(DVBT_ERR_INVALID, "bad inner_coder parameters");
-  if (p->noutput <= 0 || p->noutput % 1512 || p->noutput > (1 << 20)) BLK_FAIL(DVBT_ERR_INVALID, "noutput must be a positive multiple of 1512 (reference assert, inner_coder_impl.cc:165)");
-  if (p->ninput != 1) BLK_FAIL(DVBT_ERR_INVALID, "ninput must be 1: the reference's input items are bytes whatever ninput says (inner_coder_impl.cc:138), its consume_each divides by ninput");
+  if (!h->d.valid) return fail(DVBT_ERR_INVALID, "bad inner_coder parameters");
+  if (p->noutput <= 0 || p->noutput % 1512 || p->noutput > (1 << 20)) return fail(DVBT_ERR_INVALID, "noutput must be a positive multiple of 1512 (reference assert, inner_coder_impl.cc:165)");
+  if (p->ninput != 1) return fail(DVBT_ERR_INVALID, "ninput must be 1: the reference's input items are bytes whatever ninput says (inner_coder_impl.cc:138), its consume_each divides by ninput");
   const Dims &d = h->d;
   memset(&h->cp, 0, sizeof h->cp);
   h->cp.m = d.m; h->cp.k = d.k; h->cp.n = d.n;
@@ -176,8 +173,8 @@ extern "C" int dvbt_inner_coder_create(const dvbt_inner_coder_params *p, dvbt_in
     if (d.punct[2 * j]) h->cp.cmap[o++] = (uint8_t)(j << 1);
     if (d.punct[2 * j + 1]) h->cp.cmap[o++] = (uint8_t)((j << 1) | 1);
   }
-  if (hipMalloc((void **)&h->prev, 64) != hipSuccess || hipMemset(h->prev, 0, 64) != hipSuccess) BLK_FAIL(DVBT_ERR_HIP, "hipMalloc (inner_coder state)");
-  *out = h; return DVBT_OK;
+  if (h->prev.alloc(64) != hipSuccess || hipMemset(h->prev, 0, 64) != hipSuccess) return fail(DVBT_ERR_HIP, "hipMalloc (inner_coder state)");
+  *out = hold.release(); return DVBT_OK;
 }
 static long long coder_input(const dvbt_inner_coder *h, long long n)                    // :208-216, :262
 { return n * h->p.noutput * h->d.k * h->d.m / ((long long)h->p.ninput * 8 * h->d.n); }
@@ -222,15 +219,15 @@ extern "C" int dvbt_bit_inner_interleaver_create(const dvbt_bit_inner_interleave
   BLK_CREATE_PROLOGUE(dvbt_bit_inner_interleaver);
   h->p = *p;
   const Dims d = make_dims(p->constellation, p->hierarchy, 0, 0, p->transmission_mode);
-  if (!d.valid || p->nsize <= 0 || p->nsize % 252 || p->nsize > 49392) BLK_FAIL(DVBT_ERR_INVALID, "nsize must be a positive multiple of 252 (126-word blocks, 4-byte items)");
+  if (!d.valid || p->nsize <= 0 || p->nsize % 252 || p->nsize > 49392) return fail(DVBT_ERR_INVALID, "nsize must be a positive multiple of 252 (126-word blocks, 4-byte items)");
   if (p->hierarchy != DVBT_NH)
-    BLK_FAIL(DVBT_ERR_INVALID, "only hierarchy NH: the reference's hierarchical branch writes outside its bit matrix (bit_inner_interleaver_impl.cc:161-167)");
+    return fail(DVBT_ERR_INVALID, "only hierarchy NH: the reference's hierarchical branch writes outside its bit matrix (bit_inner_interleaver_impl.cc:161-167)");
   memset(&h->bp, 0, sizeof h->bp);
   h->bp.m = d.m;
   for (int kk = 0; kk < d.m; kk++) h->bp.kinv[(kk / (d.m / 2)) + 2 * (kk % (d.m / 2))] = (uint8_t)kk;    // :97-98: bit kk goes to row perm(kk)
   static const uint8_t hoff[6] = {0, 63, 105, 42, 21, 84};                                              // :37-57 H(e, w)
   memcpy(h->bp.hoff, hoff, 6);
-  *out = h; return DVBT_OK;
+  *out = hold.release(); return DVBT_OK;
 }
 extern "C" int dvbt_bit_inner_interleaver_forecast(const dvbt_bit_inner_interleaver *, int n, int *req) { if (req) *req = n; return DVBT_OK; }
 static int bitint_call(dvbt_bit_inner_interleaver *h, int nout, int nin, const void *in, void *out, dvbt_sideband *sb, bool dev, hipStream_t s)
@@ -269,9 +266,9 @@ extern "C" int dvbt_map_create(const dvbt_map_params *p, dvbt_map **out)
   h->p = *p;
   h->T.d = make_dims(p->constellation, p->hierarchy, 0, 0, p->transmission_mode);
   if (!h->T.d.valid || p->nsize <= 0 || p->nsize % 2 || p->nsize > (1 << 20) || !std::isfinite(p->gain))
-    BLK_FAIL(DVBT_ERR_INVALID, "bad dvbt_map parameters (nsize a positive even number, gain finite)");
-  BLK_CHK(h->T.build_inner(p->gain));                             // make_constellation_points with gain * norm and the hierarchy's alpha (:56-139)
-  *out = h; return DVBT_OK;
+    return fail(DVBT_ERR_INVALID, "bad dvbt_map parameters (nsize a positive even number, gain finite)");
+  WCHK(h->T.build_inner(p->gain));                             // make_constellation_points with gain * norm and the hierarchy's alpha (:56-139)
+  *out = hold.release(); return DVBT_OK;
 }
 extern "C" int dvbt_map_forecast(const dvbt_map *, int n, int *req) { if (req) *req = n; return DVBT_OK; }
 static int map_call(dvbt_map *h, int nout, int nin, const void *in, void *out, dvbt_sideband *sb, bool dev, hipStream_t s)
@@ -305,32 +302,31 @@ extern "C" void dvbt_map_destroy(dvbt_map *h) { delete h; }
 // ============================================================================ T7 reference_signals
 // symbols: the items emitted so far (symbol_index = symbols mod 68, frame_index = (symbols / 68) mod 4: update_output :1175-1183)
 struct dvbt_reference_signals { dvbt_reference_signals_params p; BlockCtx c; Dims d; TxbRefParams rp; TxTables tt; long long symbols = 0;
-                                uint16_t *pay = nullptr, *pil = nullptr, *tps = nullptr; float *pref = nullptr, *tps_base = nullptr, *tps_sign = nullptr;
-                                ~dvbt_reference_signals() { void *all[] = {pay, pil, tps, pref, tps_base, tps_sign}; for (void *q : all) if (q) (void)hipFree(q); } };
+                                DevMem<uint16_t> pay, pil, tps; DevMem<float> pref, tps_base, tps_sign; };
 extern "C" int dvbt_reference_signals_create(const dvbt_reference_signals_params *p, dvbt_reference_signals **out)
 {
   BLK_CREATE_PROLOGUE(dvbt_reference_signals);
   h->p = *p;
   h->d = make_dims(p->constellation, p->hierarchy, p->code_rate_hp, p->guard_interval, p->transmission_mode);
   const Dims &d = h->d;
-  if (!d.valid || p->code_rate_lp < 0 || p->code_rate_lp > 4) BLK_FAIL(DVBT_ERR_INVALID, "bad DVB-T parameters");
+  if (!d.valid || p->code_rate_lp < 0 || p->code_rate_lp > 4) return fail(DVBT_ERR_INVALID, "bad DVB-T parameters");
   if (p->itemsize != 8 || p->ninput != d.payload || p->noutput != d.N)
-    BLK_FAIL(DVBT_ERR_INVALID, "itemsize must be 8 (gr_complex), ninput the payload and noutput the FFT length of the transmission mode");
-  if (p->include_cell_id < 0 || p->include_cell_id > 1 || p->cell_id < 0 || p->cell_id > 0xffff) BLK_FAIL(DVBT_ERR_INVALID, "bad cell id parameters");
+    return fail(DVBT_ERR_INVALID, "itemsize must be 8 (gr_complex), ninput the payload and noutput the FFT length of the transmission mode");
+  if (p->include_cell_id < 0 || p->include_cell_id > 1 || p->cell_id < 0 || p->cell_id > 0xffff) return fail(DVBT_ERR_INVALID, "bad cell id parameters");
   TxClasses cl;
-  BLK_CHK(tx_carrier_classes(d, cl));
+  WCHK(tx_carrier_classes(d, cl));
   const std::vector<float> pref = pilot_ref_table(d);
   TxTps tp;
   tx_tps_tables(d, p->code_rate_lp, p->include_cell_id, p->cell_id, pref, tp);
-  BLK_CHK(upload(cl.pay, &h->pay)); BLK_CHK(upload(cl.pil, &h->pil)); BLK_CHK(upload(pref, &h->pref));
-  BLK_CHK(upload(tp.car, &h->tps)); BLK_CHK(upload(tp.base, &h->tps_base)); BLK_CHK(upload(tp.sign, &h->tps_sign));
+  WCHK(upload(cl.pay, h->pay)); WCHK(upload(cl.pil, h->pil)); WCHK(upload(pref, h->pref));
+  WCHK(upload(tp.car, h->tps)); WCHK(upload(tp.base, h->tps_base)); WCHK(upload(tp.sign, h->tps_sign));
   memset(&h->rp, 0, sizeof h->rp);
   h->rp.payload = d.payload; h->rp.zl = d.zl; h->rp.K = d.K; h->rp.n_tps = (int)tp.car.size();
   for (int c = 0; c < TX_NCLASS; c++) h->rp.npil[c] = cl.npil[c];
   memset(&h->tt, 0, sizeof h->tt);
   h->tt.pay = h->pay; h->tt.pil = h->pil; h->tt.pref = h->pref; h->tt.tps = h->tps; h->tt.tps_base = h->tps_base; h->tt.tps_sign = h->tps_sign;
-  BLK_CHK(set_lds(d.N == 8192 ? (const void *)txb_refsig_kernel<8192> : (const void *)txb_refsig_kernel<2048>, txb_refsig_lds_bytes(d.N)));
-  *out = h; return DVBT_OK;
+  WCHK(set_lds(d.N == 8192 ? (const void *)txb_refsig_kernel<8192> : (const void *)txb_refsig_kernel<2048>, txb_refsig_lds_bytes(d.N)));
+  *out = hold.release(); return DVBT_OK;
 }
 extern "C" int dvbt_reference_signals_forecast(const dvbt_reference_signals *, int n, int *req) { if (req) *req = n; return DVBT_OK; }   // :1280-1284
 static int refsig_call(dvbt_reference_signals *h, int nout, int nin, const void *in, void *out, dvbt_sideband *sb, bool dev, hipStream_t s)
