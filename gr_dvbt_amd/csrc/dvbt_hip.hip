@@ -359,6 +359,7 @@ struct dvbt_rx {
   dvbt_rx_report last; bool have_last = false;
   dvbt_rx_cut cut = {0, 0, 0};
   DevMem<float2> tps_prev, tps_prev_snap[2]; DevMem<TpsState> tps_snap[2]; DevMem<DescrRun> descr_runs; DevMem<int> descr_nruns;
+  int descr_runs_cap = 0;                   // runs descr_runs holds: one per descrambler call of a stream of vit_cap bytes (descr_runs_for), DESCR_MAX_RUNS at the least
   int n_periods = 1; size_t seg_offset = 0;
   std::vector<dvbt_lock_period> periods;    // phase A of the last synchronous run
   DriftBufs drift = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; DevMem<double> drift_mem; DevMem<float> drift_delta;   // k_drift.hpp: drift's pointers are views into these two (flags: into drift_flags_ctx)
@@ -436,7 +437,7 @@ extern "C" int dvbt_rx_create(const dvbt_rx_params *p, dvbt_rx **out)
   HIPCHK(h->aux_stream.create()); HIPCHK(h->aux_ev.create(hipEventDisableTiming));
   HIPCHK(h->tps_prev.alloc(d.n_tps)); HIPCHK(hipMemset(h->tps_prev, 0, sizeof(float2) * d.n_tps));
   for (int i = 0; i < 2; i++) { HIPCHK(h->tps_prev_snap[i].alloc(d.n_tps)); HIPCHK(h->tps_snap[i].alloc(1)); }
-  HIPCHK(h->descr_runs.alloc(DESCR_MAX_RUNS)); HIPCHK(h->descr_nruns.alloc(1));
+  HIPCHK(h->descr_nruns.alloc(1));
   HIPCHK(h->centre.alloc(C + 1)); HIPCHK(h->anchor_pos.alloc(C / ACQ_ANCHOR + 4));
   HIPCHK(h->tps_edges.alloc(C / TPS_SEG + 2));
   for (int i = 0; i < dvbt_rx::NCTX; i++) { HIPCHK(h->st_host_ctx[i].alloc(1)); memset(h->st_host_ctx[i], 0, sizeof(RxState)); }
@@ -459,6 +460,8 @@ extern "C" int dvbt_rx_create(const dvbt_rx_params *p, dvbt_rx **out)
   h->rs_defer_cap = (int)((h->vit_cap / 204 / 64 + 2) * (RS_LANE_MIN - 1));
   HIPCHK(h->rs_defer.alloc((size_t)h->rs_defer_cap));
   HIPCHK(h->rs_sync.alloc(h->vit_cap / 204 / 64 + 2));
+  h->descr_runs_cap = (int)descr_runs_for((long long)h->vit_cap);
+  HIPCHK(h->descr_runs.alloc((size_t)h->descr_runs_cap));
   HIPCHK(h->vit.alloc(h->vit_cap)); HIPCHK(h->rs_out.alloc(h->vit_cap)); HIPCHK(h->ts_out.alloc(h->vit_cap));
   HIPCHK(hipMemset(h->st, 0, sizeof(RxState)));
   for (int i = 0; i < ST_COUNT; i++) HIPCHK(h->ev[i].create());
@@ -528,12 +531,15 @@ static int rx_reserve_vit(dvbt_rx *h, size_t cap)
   const size_t old = h->vit_cap, sync_old = old / 204 / 64 + 2, sync_new = cap / 204 / 64 + 2;
   const int dcap = (int)(sync_new * (RS_LANE_MIN - 1));
   // every new buffer first, filled with what it keeps; the handle takes them only when all are there, so a failure leaves it as it was
-  DevMem<uint8_t> vit, rs_out, ts_out, deint_tap; DevMem<RsDefer> rs_defer; DevMem<unsigned long long> rs_sync;
+  DevMem<uint8_t> vit, rs_out, ts_out, deint_tap; DevMem<RsDefer> rs_defer; DevMem<unsigned long long> rs_sync; DevMem<DescrRun> descr_runs;
+  const int rcap = (int)descr_runs_for((long long)cap);
   int r;
   if ((r = grown(vit, h->vit, cap, old)) || (r = grown(rs_out, h->rs_out, cap, old)) || (r = grown(ts_out, h->ts_out, cap, old)) ||
-      (r = grown(rs_defer, h->rs_defer, (size_t)dcap, 0)) || (r = grown(rs_sync, h->rs_sync, sync_new, sync_old))) return r;
+      (r = grown(rs_defer, h->rs_defer, (size_t)dcap, 0)) || (r = grown(rs_sync, h->rs_sync, sync_new, sync_old)) ||
+      (r = grown(descr_runs, h->descr_runs, (size_t)rcap, 0))) return r;
   if (h->deint_tap && (r = grown(deint_tap, h->deint_tap, cap, old))) return r;      // (a debug tap, there only on request)
   h->vit = std::move(vit); h->rs_out = std::move(rs_out); h->ts_out = std::move(ts_out); h->rs_defer = std::move(rs_defer); h->rs_sync = std::move(rs_sync);
+  h->descr_runs = std::move(descr_runs); h->descr_runs_cap = rcap;
   if (h->deint_tap) h->deint_tap = std::move(deint_tap);
   h->rs_defer_cap = dcap; h->vit_cap = cap;
   return DVBT_OK;
@@ -634,7 +640,7 @@ static int enqueue_tail(dvbt_rx *h, hipStream_t s, long long max_words, long lon
   hipLaunchKernelGGL(rs_fix_kernel, dim3(512), dim3(64), 0, s, (const RsDefer *)h->rs_defer, (const int *)&h->st->rs_list_n, h->rs_defer_cap, h->rs_out,
                      h->T.rs_tables(), h->prm.rs_oracle_compat, &h->st->rs_fail, &h->st->rs_corr, h->rs_sync);
   if (h->prm.descramble) {
-    hipLaunchKernelGGL(descramble_scan_kernel, dim3(1), dim3(1024), 0, s, (const uint8_t *)h->rs_out, h->st, h->descr_runs, h->descr_nruns,
+    hipLaunchKernelGGL(descramble_scan_kernel, dim3(1), dim3(1024), 0, s, (const uint8_t *)h->rs_out, h->st, h->descr_runs, h->descr_nruns, h->descr_runs_cap,
                        (const unsigned long long *)h->rs_sync, h->cut.descr_call_phase - 1);
     hipLaunchKernelGGL(descramble_runs_kernel, dim3(1024), dim3(256), 0, s, (const uint8_t *)h->rs_out, (const uint8_t *)h->T.prbs,
                        (const RxState *)h->st, (const DescrRun *)h->descr_runs, (const int *)h->descr_nruns, h->ts_out);
@@ -1586,6 +1592,87 @@ extern "C" int dvbt_debug_soft_demap(int constellation, int mode, const void *eq
   HIPCHK(hipGetLastError());
   HIPCHK(hipMemcpy(out_host, dout, n * d.m, hipMemcpyDeviceToHost));
   return DVBT_OK;
+}
+
+// test hook: the outer stage of the segment chain alone on a host-supplied Viterbi stream (include/dvbt_hip.h).  The launches are enqueue_tail's and stream_rs_range's
+// own: nothing of them is restated here.  A piece's plan (mode 1) is what plan_body leaves behind, set by a copy of the state block -- tail_patch_kernel would zero sym_off
+static int stream_rs_range(dvbt_rx_stream *s, dvbt_rx *h, long long from, long long to);   // dvbt_stream.inc
+static size_t outer_buf(dvbt_rx *h, int buffer, void **p)
+{
+  switch (buffer) {
+    case DVBT_OUTER_BUF_DEINT: *p = h->deint_tap; return h->deint_tap ? h->vit_cap : 0;
+    case DVBT_OUTER_BUF_RS: *p = h->rs_out; return h->vit_cap;
+    case DVBT_OUTER_BUF_TS: *p = h->ts_out; return h->vit_cap;
+    case DVBT_OUTER_BUF_SYNC: *p = h->rs_sync; return (h->vit_cap / 204 / 64 + 2) * sizeof(unsigned long long);
+    case DVBT_OUTER_BUF_RUNS: *p = h->descr_runs; return (size_t)h->descr_runs_cap * sizeof(DescrRun);
+    default: *p = nullptr; return 0;
+  }
+}
+extern "C" int dvbt_debug_outer(dvbt_rx *h, int mode, const uint8_t *vit_host, int64_t n_bytes, int64_t a, int64_t b, dvbt_outer_report *rep, uint64_t *sync_host, size_t sync_cap)
+{
+  if (!rep) return fail(DVBT_ERR_INVALID, "null argument");
+  if (mode < DVBT_OUTER_SEGMENT || mode > DVBT_OUTER_RANGE) return fail(DVBT_ERR_INVALID, "unknown mode");
+  if (n_bytes < 0 || n_bytes > (1ll << 30)) return fail(DVBT_ERR_INVALID, "n_bytes must lie in [0, 2^30]");
+  { int nd = need_device(); if (nd) return nd; }                   // (a handle exists only where a device does)
+  if (!h) return fail(DVBT_ERR_INVALID, "null handle");
+  const bool carry_on = mode == DVBT_OUTER_RANGE && !vit_host && n_bytes == 0;
+  if (!vit_host && !carry_on) return fail(DVBT_ERR_INVALID, "null argument");
+  if (h->pending) return fail(DVBT_ERR_STATE, "dvbt_debug_outer: a segment is in flight (dvbt_rx_segment_finish first)");
+  const long long have = carry_on ? (long long)h->vit_cap : (long long)n_bytes;
+  if (mode == DVBT_OUTER_CUT && (a < 0 || a > have / 204 || b < 0 || b > 16)) return fail(DVBT_ERR_INVALID, "a piece's n_rs_words must lie inside the stream, descr_call_phase in [0, 16]");
+  if (mode == DVBT_OUTER_RANGE && (a < 0 || a % 64 != 0 || b < a || b > have / 204)) return fail(DVBT_ERR_INVALID, "a range starts on a multiple of 64 words and lies inside the stream");
+  HIPCHK(hipSetDevice(h->prm.device));
+  hipStream_t s = h->own_stream;
+  int r;
+  if (!carry_on) {
+    if ((r = rx_reserve_vit(h, (size_t)n_bytes + 4096))) return r;
+    void *p; size_t cap;
+    for (int bf = DVBT_OUTER_BUF_DEINT; bf <= DVBT_OUTER_BUF_RUNS; bf++) if ((cap = outer_buf(h, bf, &p))) HIPCHK(hipMemsetAsync(p, 0xA5, cap, s));
+    if (n_bytes) HIPCHK(hipMemcpyAsync(h->vit, vit_host, (size_t)n_bytes, hipMemcpyHostToDevice, s));
+    RxState plan; memset(&plan, 0, sizeof plan);
+    if (mode == DVBT_OUTER_CUT) { plan.sym_off = 272; plan.n_rs_words = a; plan.n_rs_items = a / 8; plan.stream_rs_items = a / 8; }
+    *h->st_host = plan;
+    HIPCHK(hipMemcpyAsync(h->st, h->st_host, sizeof(RxState), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemsetAsync(h->descr_nruns, 0, sizeof(int), s));
+    HIPCHK(hipStreamSynchronize(s));                               // (the sources are the caller's memory and the page-locked block that the read-back below fills)
+  }
+  if (mode == DVBT_OUTER_RANGE) r = stream_rs_range(nullptr, h, a, b);
+  else {
+    const dvbt_rx_cut keep = h->cut;
+    if (mode == DVBT_OUTER_CUT) h->cut.descr_call_phase = (int32_t)b;
+    r = enqueue_tail(h, s, n_bytes / 204 + 1, mode == DVBT_OUTER_CUT ? -1 : n_bytes / 204);
+    h->cut = keep;
+  }
+  if (r) return r;
+  HIPCHK(hipGetLastError());
+  int nruns = 0;
+  HIPCHK(hipMemcpyAsync(h->st_host, h->st, sizeof(RxState), hipMemcpyDeviceToHost, s));
+  HIPCHK(hipMemcpyAsync(&nruns, h->descr_nruns, sizeof(int), hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  RxState fin = *h->st_host;
+  if (mode == DVBT_OUTER_RANGE) { fin.n_rs_words = b; fin.n_rs_items = b / 8; fin.n_ts_bytes = 0; }   // (the range form has no plan on the device: the taps show the words up to the range's end)
+  if (!carry_on) fin.n_vit_bytes = n_bytes; else fin.n_vit_bytes = h->have_last ? h->last.n_viterbi_bytes : 0;
+  dvbt_rx_report lr; fill_report(h, fin, lr);
+  h->last = lr; h->have_last = true;
+  memset(rep, 0, sizeof *rep);
+  rep->n_rs_words = fin.n_rs_words; rep->n_rs_items = fin.n_rs_items; rep->n_ts_bytes = fin.n_ts_bytes; rep->ts_first_packet = fin.ts_first_packet;
+  rep->cap_bytes = (int64_t)h->vit_cap; rep->sync_cap_words = (int64_t)(h->vit_cap / 204 / 64 + 2); rep->runs_cap = h->descr_runs_cap;
+  rep->rs_fail = fin.rs_fail; rep->rs_corr = fin.rs_corr; rep->rs_list_n = fin.rs_list_n; rep->n_runs = mode == DVBT_OUTER_RANGE ? 0 : nruns; rep->descr_unclean = fin.descr_unclean;
+  if (sync_host && sync_cap) HIPCHK(hipMemcpy(sync_host, h->rs_sync, sizeof(unsigned long long) * std::min<size_t>(sync_cap, (size_t)rep->sync_cap_words), hipMemcpyDeviceToHost));
+  return DVBT_OK;
+}
+extern "C" int64_t dvbt_debug_outer_read(dvbt_rx *h, int buffer, int64_t offset, void *dst, size_t nbytes)
+{
+  if (!dst) return fail(DVBT_ERR_INVALID, "null argument");
+  { int nd = need_device(); if (nd) return nd; }
+  if (!h) return fail(DVBT_ERR_INVALID, "null handle");
+  void *p; const size_t cap = outer_buf(h, buffer, &p);
+  if (!p) return fail(DVBT_ERR_STATE, "unknown buffer, or the de-interleaver's tap is not enabled (dvbt_rx_enable_taps)");
+  if (offset < 0 || (size_t)offset > cap) return fail(DVBT_ERR_INVALID, "offset outside the buffer");
+  HIPCHK(hipSetDevice(h->prm.device));
+  nbytes = std::min(nbytes, cap - (size_t)offset);
+  if (nbytes) HIPCHK(hipMemcpy(dst, (const uint8_t *)p + offset, nbytes, hipMemcpyDeviceToHost));
+  return (int64_t)nbytes;
 }
 
 #include "dvbt_stream.inc"

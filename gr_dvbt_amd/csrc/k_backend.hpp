@@ -650,12 +650,15 @@ __global__ __launch_bounds__(256) void conv_deint_kernel(const uint8_t *__restri
 // lane exactly as above.  What is delivered is a list of runs of whole items (normally one: lock on the first NSYNC, deliver from
 // there to two items before the end); descramble_runs_kernel copies them through the PRBS.
 struct DescrRun { long long src_byte, dst_byte, nbytes; };
-constexpr int DESCR_MAX_RUNS = 1024;
+constexpr int DESCR_MAX_RUNS = 1024;                            // runs per launch of descramble_runs_kernel in the streaming entry's batches; the least a run list holds
+// The segment chain's list holds one run per call of the longest stream its handle takes (descr_runs_for): every lost NSYNC on the call grid ends a run, and the
+// reference's descrambler goes on however often that happens -- a list that is full would end the TS there, short of the reference's, without a word
+__host__ __device__ constexpr long long descr_runs_for(long long stream_bytes) { return stream_bytes / 204 / 16 + 1 > DESCR_MAX_RUNS ? stream_bytes / 204 / 16 + 1 : DESCR_MAX_RUNS; }
 
 // sync_bits (the segment chain): bit w = payload byte 0 of RS word w is 0xB8, written by deint_rs_kernel / rs_fix_kernel -- the walk then reads one bit per
 // packet out of a few KB instead of one byte per 188 out of the whole TS (21,000 cache lines through ONE compute unit: 45 us of the 65-superframe step);
 // nullptr: the bytes themselves.
-__global__ __launch_bounds__(1024) void descramble_scan_kernel(const uint8_t *__restrict__ in, RxState *st, DescrRun *runs, int *nruns,
+__global__ __launch_bounds__(1024) void descramble_scan_kernel(const uint8_t *__restrict__ in, RxState *st, DescrRun *runs, int *nruns, int runs_cap,
                                                               const unsigned long long *__restrict__ sync_bits = nullptr, int phase16 = -1)
 {
   __shared__ long long s_first;
@@ -722,7 +725,7 @@ __global__ __launch_bounds__(1024) void descramble_scan_kernel(const uint8_t *__
       const long long kf = s_first;
       if (kf > 0) {                                                // kf calls in a row found their NSYNC: one run
         const int r = s_nr;
-        if (r < DESCR_MAX_RUNS) {
+        if (r < runs_cap) {
           if (r == 0) { st->descr_base = (int)base; st->descr_index = d_index; st->ts_first_packet = (base * 1504 + d_index) / 188; }
           runs[r].src_byte = base * 1504 + d_index; runs[r].dst_byte = s_written; runs[r].nbytes = kf * 2 * 1504; s_nr = r + 1;
           s_written += kf * 2 * 1504;
@@ -756,9 +759,9 @@ __global__ __launch_bounds__(256) void descramble_runs_kernel(const uint8_t *__r
     const unsigned long long g = i / 376ull; const unsigned t = (unsigned)(i - g * 376ull);
     const long long dst = (long long)g * 1504;
     long long src = src0 + dst;                                  // one run (the usual case): it starts at destination byte 0
-    if (nr > 1) {
-      int r = 0;
-      while (r + 1 < nr && runs[r + 1].dst_byte <= dst) r++;
+    if (nr > 1) {                                                // the last run that starts at or in front of dst (runs[0] starts at 0, every run holds bytes)
+      int r = 0, hi = nr - 1;
+      while (r < hi) { const int mid = (r + hi + 1) >> 1; if (runs[mid].dst_byte <= dst) r = mid; else hi = mid - 1; }
       src = runs[r].src_byte + (dst - runs[r].dst_byte);
     }
     unsigned v = reinterpret_cast<const unsigned *>(in + src)[t] ^ sq[t];

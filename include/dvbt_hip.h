@@ -801,6 +801,32 @@ int dvbt_debug_soft_viterbi(int constellation, int code_rate, const int8_t *soft
 /* the soft demapper's two kernels (csrc/k_soft.hpp: the scatter table of both inner de-interleavers, then the demapper) on nsym host symbols: eq cfloat[nsym][P],
  * csi float[nsym][P], parity[s] = symbol index & 1; out_host int8[nsym][P m], the soft values in the decoder's input order */
 int dvbt_debug_soft_demap(int constellation, int transmission_mode, const void *eq_host, const float *csi_host, const int32_t *parity_host, int nsym, int8_t *out_host);
+/* the segment chain's outer stage alone (byte de-interleaver + RS with its defer list and second pass + sync bitmap + descrambler: the launches of enqueue_tail in
+ * csrc/dvbt_hip.hip, and the range form stream_rs_range of csrc/dvbt_stream.inc) on n_bytes host-supplied bytes of a Viterbi stream, uploaded into the handle's own
+ * buffers (grown as the streaming entry grows them).  The RS, TS and DEINT buffers (the last when the taps are enabled), the sync bitmap and the run list are 0xA5 up to
+ * their capacity before the launches.  Afterwards dvbt_rx_read_tap(DEINT / RS / TS) deliver the counts reported here; dvbt_debug_outer_read reads any of the buffers
+ * up to its capacity.  mode:
+ *   DVBT_OUTER_SEGMENT  enqueue_tail on a stream whose length the host knows (n_bytes / 204 words); a, b unused
+ *   DVBT_OUTER_CUT      the same launches on the plan of a piece that continues a cut stream: a = n_rs_words (any value with a * 204 <= n_bytes), b = descr_call_phase
+ *                       as in dvbt_rx_cut (0 = unknown, else 1 + phase)
+ *   DVBT_OUTER_RANGE    stream_rs_range over the words [a, b) (a: a multiple of 64), no descrambler.  vit_host = NULL with n_bytes = 0: on the stream already in the
+ *                       handle, nothing refilled, the counters carried on -- as the streaming entry's walk calls it behind every window
+ * sync_host: the first sync_cap words of the bitmap (NULL: none).  DVBT_ERR_INVALID, nothing allocated or launched, for negative sizes, more than 2^30 bytes, or a plan
+ * outside the uploaded stream; behind those checks DVBT_ERR_NO_DEVICE without a GPU, whatever the handle.  tests/test_gpu_outer.py */
+enum { DVBT_OUTER_SEGMENT = 0, DVBT_OUTER_CUT = 1, DVBT_OUTER_RANGE = 2 };
+enum { DVBT_OUTER_BUF_DEINT = 0, DVBT_OUTER_BUF_RS = 1, DVBT_OUTER_BUF_TS = 2, DVBT_OUTER_BUF_SYNC = 3, DVBT_OUTER_BUF_RUNS = 4 };
+typedef struct {
+  int64_t n_rs_words, n_rs_items, n_ts_bytes, ts_first_packet;
+  int64_t cap_bytes;       /* capacity of the DEINT / RS / TS buffers */
+  int64_t sync_cap_words;  /* ... of the bitmap, in 64-bit words */
+  int64_t runs_cap;        /* ... of the run list, in runs of three int64 (source byte, destination byte, bytes) */
+  int32_t rs_fail, rs_corr;
+  int32_t rs_list_n;       /* words the first pass handed to the second */
+  int32_t n_runs, descr_unclean, reserved;
+} dvbt_outer_report;
+int dvbt_debug_outer(dvbt_rx *h, int mode, const uint8_t *vit_host, int64_t n_bytes, int64_t a, int64_t b, dvbt_outer_report *report, uint64_t *sync_host, size_t sync_cap);
+/* nbytes bytes from byte `offset` of one of the buffers above (DVBT_OUTER_BUF_*), within its capacity; returns the bytes copied */
+int64_t dvbt_debug_outer_read(dvbt_rx *h, int buffer, int64_t offset, void *dst, size_t nbytes);
 
 #ifdef __cplusplus
 }

@@ -64,6 +64,17 @@ def test_no_cpu_fallback(g):
     class P(C.Structure):
         _fields_ = [("fft_size", C.c_int), ("forward", C.c_int), ("shift", C.c_int)]
     assert L.dvbt_fft_create(C.byref(P(2048, 1, 1)), C.byref(h)) == -2
+    # the test hooks that launch kernels: bad sizes are refused first, then the missing device; a hook on a handle says so before it asks for the handle
+    rep = (C.c_int64 * 16)()
+    buf = (C.c_ubyte * 204)()
+    L.dvbt_debug_outer.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_size_t]
+    L.dvbt_debug_outer_read.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_size_t]
+    L.dvbt_debug_outer_read.restype = C.c_int64
+    assert L.dvbt_debug_outer(None, 0, buf, -1, 0, 0, rep, None, 0) == -1
+    assert L.dvbt_debug_outer(None, 0, buf, (1 << 30) + 1, 0, 0, rep, None, 0) == -1
+    for mode in (0, 1, 2):
+        assert L.dvbt_debug_outer(None, mode, buf, 204, 0, 0, rep, None, 0) == -2
+    assert L.dvbt_debug_outer_read(None, 1, 0, buf, 8) == -2
 
 
 def test_product_does_not_import_oracle():
