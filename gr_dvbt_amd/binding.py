@@ -64,6 +64,27 @@ class RxReport(C.Structure):
                 ("n_lock_periods", C.c_int32), ("total_symbols", C.c_int32)]
 
 
+class RxQuality(C.Structure):
+    """dvbt_rx_quality_report.  The ratios are properties; each is nan where its figure was not measured."""
+    _fields_ = [("mer_carriers", C.c_int64), ("mer_signal", C.c_double), ("mer_error", C.c_double),
+                ("channel_bits", C.c_int64), ("channel_bit_errors", C.c_int64), ("post_bits", C.c_int64), ("post_bit_errors", C.c_int64),
+                ("rs_fail_words", C.c_int32), ("rs_corrected_symbols", C.c_int32), ("n_lock_periods", C.c_int32), ("flags", C.c_int32)]
+
+    @property
+    def mer_db(self):
+        if self.mer_carriers <= 0 or not self.mer_signal > 0.0:
+            return float("nan")
+        return float("inf") if self.mer_error <= 0.0 else 10.0 * float(np.log10(self.mer_signal / self.mer_error))
+
+    @property
+    def channel_ber(self):
+        return self.channel_bit_errors / self.channel_bits if self.channel_bits > 0 else float("nan")
+
+    @property
+    def post_viterbi_ber(self):
+        return self.post_bit_errors / self.post_bits if self.post_bits > 0 else float("nan")
+
+
 class LockPeriod(C.Structure):
     _fields_ = [("offset", C.c_int64), ("first_call", C.c_int32), ("cp_start0", C.c_int32), ("n_symbols", C.c_int32),
                 ("first_out_symbol", C.c_int32)]
@@ -144,7 +165,7 @@ class Rx:
 
     def __init__(self, constellation, code_rate, mode, max_samples, guard=G1_32, hierarchy=NH, snr_db=30.0,
                  viterbi_bsize=768, rs_oracle_compat=0, descramble=1, device=0, viterbi_chunk_bytes=0, taps=False,
-                 resample=(0, 0), front_scale=0.0, soft_decision=0, hier_stream=0, launch_graph=0, front_priority=0, viterbi_warm_windows=0, viterbi_verify=0):
+                 resample=(0, 0), front_scale=0.0, soft_decision=0, hier_stream=0, launch_graph=0, front_priority=0, viterbi_warm_windows=0, viterbi_verify=0, quality=False):
         self.L = lib()
         self.p = RxParams(constellation, hierarchy, code_rate, guard, mode, 0, 0, snr_db, viterbi_bsize,
                           rs_oracle_compat, descramble, max_samples, device, viterbi_chunk_bytes, resample[0], resample[1], front_scale, soft_decision, hier_stream, launch_graph, front_priority,
@@ -154,7 +175,21 @@ class Rx:
         self.dims = get_dims(constellation, code_rate, mode, guard, hierarchy)
         if taps:
             _chk(self.L.dvbt_rx_enable_taps(self.h, int(taps)))          # True / 1: the debug taps; 2: plus the per-lock-period log of the decoder's input
+        if quality:
+            self.enable_quality()
         self.report = None
+
+    def enable_quality(self, on=True):
+        """keep the equalised carriers of the segments that follow, so that quality() can measure their MER (dvbt_rx_enable_quality)"""
+        self.L.dvbt_rx_enable_quality.argtypes = [C.c_void_p, C.c_int]
+        _chk(self.L.dvbt_rx_enable_quality(self.h, int(bool(on))))
+
+    def quality(self):
+        """RxQuality of the last finished segment (dvbt_rx_quality): MER, channel and post-Viterbi bit errors, measured on the device"""
+        q = RxQuality()
+        self.L.dvbt_rx_quality.argtypes = [C.c_void_p, C.POINTER(RxQuality)]
+        _chk(self.L.dvbt_rx_quality(self.h, C.byref(q)))
+        return q
 
     def run(self, iq):
         iq = np.ascontiguousarray(iq, dtype=np.complex64)

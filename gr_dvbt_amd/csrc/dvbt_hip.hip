@@ -23,6 +23,7 @@
 #include "k_resample.hpp"
 #include "k_viterbi3.hpp"
 #include "k_soft4.hpp"
+#include "k_quality.hpp"
 #include "k_tx.hpp"
 #include "k_txblocks.hpp"
 
@@ -347,6 +348,8 @@ struct dvbt_rx {
   DevMem<float2> acq_tap, fft_out, eq, tpsval; DevMem<SymInfo> info; DevMem<int> maj, sym_index;
   DevMem<uint8_t> labels, symdeint_tap, bitdeint, vit, deint_tap, rs_out, ts_out;
   DevMem<uint8_t> bitdeint_lp;              // hierarchical modes: the bit de-interleaver's second output
+  DevMem<float2> q_sym; DevMem<double> q_mer; DevMem<unsigned long long> q_cnt;   // dvbt_rx_quality (dvbt_quality.inc): MER sums per symbol, their total, the bit counters
+  unsigned long long seg_serial = 0, q_eq_serial = 0;   // finished segments so far / their count when dvbt_rx_enable_quality allocated eq (it holds carriers only of a later one)
   DevMem<uint8_t> bd_log; std::vector<dvbt_period_tap> plog; size_t plog_bytes = 0;   // dvbt_rx_enable_taps(h, 2): every lock period's decoder input
   VitProof vproof; bool vit_checked = false;   // the Viterbi stage's proof + repair passes (dvbt_rx_params.viterbi_verify): the chunk decoders' states, the passes' counters
   size_t vit_cap = 0; DevMem<RsDefer> rs_defer; int rs_defer_cap = 0;
@@ -898,7 +901,7 @@ extern "C" int dvbt_rx_segment_finish(dvbt_rx *h, dvbt_rx_report *rep)
   dvbt_rx_report r;
   fill_report(h, *h->st_host, r);
   r.n_lock_periods = r.first_out_symbol >= 0 ? 1 : 0;
-  h->last = r; h->have_last = true;
+  h->last = r; h->have_last = true; h->seg_serial++;
   if (rep) *rep = r;
   return DVBT_OK;
 }
@@ -1134,7 +1137,7 @@ static int segment_periods(dvbt_rx *h, const float2 *chain, size_t chain_n, hipS
     fill_report(h, st, r);
     if (capped) r.status |= 256;
     h->n_periods = 0; h->seg_offset = 0;
-    h->last = r; h->have_last = true; if (rep) *rep = r;
+    h->last = r; h->have_last = true; h->seg_serial++; if (rep) *rep = r;
     return DVBT_OK;
   }
   if (delivering <= 1 && processed == 1 && per.size() >= 1 && acc == (size_t)last_st.n_vit_bytes) {
@@ -1157,7 +1160,7 @@ static int segment_periods(dvbt_rx *h, const float2 *chain, size_t chain_n, hipS
   if (h->cut.stream_symbol_offset != 0 && (delivering > 1 || processed > 1)) r.status |= 128;   // a cut piece that lost the lock: laid out from its own start, not in the stream's coordinates
   if (delivering == 0) { r.first_out_symbol = -1; r.status |= 4; }
   h->n_periods = delivering; h->seg_offset = last_off;
-  h->last = r; h->have_last = true;
+  h->last = r; h->have_last = true; h->seg_serial++;
   if (rep) *rep = r;
   return DVBT_OK;
 }
@@ -1653,7 +1656,7 @@ extern "C" int dvbt_debug_outer(dvbt_rx *h, int mode, const uint8_t *vit_host, i
   if (mode == DVBT_OUTER_RANGE) { fin.n_rs_words = b; fin.n_rs_items = b / 8; fin.n_ts_bytes = 0; }   // (the range form has no plan on the device: the taps show the words up to the range's end)
   if (!carry_on) fin.n_vit_bytes = n_bytes; else fin.n_vit_bytes = h->have_last ? h->last.n_viterbi_bytes : 0;
   dvbt_rx_report lr; fill_report(h, fin, lr);
-  h->last = lr; h->have_last = true;
+  h->last = lr; h->have_last = true; h->seg_serial++;
   memset(rep, 0, sizeof *rep);
   rep->n_rs_words = fin.n_rs_words; rep->n_rs_items = fin.n_rs_items; rep->n_ts_bytes = fin.n_ts_bytes; rep->ts_first_packet = fin.ts_first_packet;
   rep->cap_bytes = (int64_t)h->vit_cap; rep->sync_cap_words = (int64_t)(h->vit_cap / 204 / 64 + 2); rep->runs_cap = h->descr_runs_cap;
@@ -1675,6 +1678,7 @@ extern "C" int64_t dvbt_debug_outer_read(dvbt_rx *h, int buffer, int64_t offset,
   return (int64_t)nbytes;
 }
 
+#include "dvbt_quality.inc"
 #include "dvbt_stream.inc"
 #include "dvbt_rccl.inc"
 #include "dvbt_blocks.inc"

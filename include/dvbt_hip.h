@@ -600,6 +600,24 @@ int  dvbt_rx_enable_taps(dvbt_rx *h, int enable);
  * log (DVBT_TAP_BITDEINT_LOG) and where its decoded bytes lie in the VITERBI tap */
 typedef struct { int64_t bitdeint_offset, bitdeint_bytes, viterbi_offset, viterbi_bytes; } dvbt_period_tap;
 int  dvbt_rx_period_taps(dvbt_rx *h, dvbt_period_tap *out, int cap);   /* returns the number of entries */
+/* Blind signal-quality measurement of the last finished segment (INTEGRATION.md "Signal quality"): a pass of its own over what the segment left on the device,
+ * launched by dvbt_rx_quality alone -- never part of the chain's launch sequence.  MER = 10 log10(mer_signal / mer_error) over the equalised payload carriers
+ * against the constellation point of the demapper's own decision; channel_*: the decoder's output re-encoded against the decoder's input (pre-Viterbi);
+ * post_*: what the RS decoder changed in the 188 data bytes of every word (post-Viterbi; words it gave up on add nothing). */
+typedef struct {
+  int64_t mer_carriers;  double mer_signal, mer_error;          /* mer_carriers == 0: not measured */
+  int64_t channel_bits, channel_bit_errors;                     /* channel_bits == 0: not measured */
+  int64_t post_bits, post_bit_errors;
+  int32_t rs_fail_words, rs_corrected_symbols, n_lock_periods, flags;  /* echoed from the report; flags bit0: EQ not enabled, bit1: more than one lock period */
+} dvbt_rx_quality_report;
+/* 1: allocate the equalised-carrier buffer (8 bytes per payload carrier of max_samples; the symbol kernel then runs its instantiation that writes it) and the
+ * result buffers; 0: free it unless dvbt_rx_enable_taps or soft mode holds it.  Call before the segment to be measured.  DVBT_ERR_STATE while a segment is pending. */
+int  dvbt_rx_enable_quality(dvbt_rx *h, int enable);
+/* Behind dvbt_rx_segment_finish / _run / _run_device and before the next enqueue (else DVBT_ERR_STATE): launches the measurement on the handle's own stream,
+ * synchronises and fills *out.  Without dvbt_rx_enable_quality the MER is not measured (flags bit0).  A segment of more than one lock period: MER and channel
+ * figures not measured (flags bit1; the front-end buffers hold the last period only), post_* over the whole segment.  DVBT_ERR_INVALID for a hierarchical
+ * handle, DVBT_ERR_STATE for a soft-decision handle or one with a cut set (dvbt_rx_set_cut). */
+int  dvbt_rx_quality(dvbt_rx *h, dvbt_rx_quality_report *out);
 void dvbt_rx_destroy(dvbt_rx *h);
 
 /* ------------------------------------------------------------------ streaming entry: the whole chain behind push / pull
@@ -827,6 +845,15 @@ typedef struct {
 int dvbt_debug_outer(dvbt_rx *h, int mode, const uint8_t *vit_host, int64_t n_bytes, int64_t a, int64_t b, dvbt_outer_report *report, uint64_t *sync_host, size_t sync_cap);
 /* nbytes bytes from byte `offset` of one of the buffers above (DVBT_OUTER_BUF_*), within its capacity; returns the bytes copied */
 int64_t dvbt_debug_outer_read(dvbt_rx *h, int buffer, int64_t offset, void *dst, size_t nbytes);
+
+/* the channel-error kernel alone (csrc/k_quality.hpp) on host bytes: in_host = n_in decoder input bytes (m bits each), vit_host = n_vit decoded bytes; counts as
+ * dvbt_rx_quality's channel_bits / channel_bit_errors (n_vit < 2: both 0).  Sizes outside [0, 2^30] are refused before the device is asked for. */
+int dvbt_debug_quality_channel(int constellation, int code_rate, const uint8_t *in_host, int64_t n_in, const uint8_t *vit_host, int64_t n_vit, int64_t *bits, int64_t *errors);
+/* the post-Viterbi kernel alone: n_words RS words of 188 bytes (rs_host) against the words regathered from the n_vit bytes of vit_host */
+int dvbt_debug_quality_post(const uint8_t *vit_host, int64_t n_vit, const uint8_t *rs_host, int64_t n_words, int64_t *bits, int64_t *errors);
+/* every kernel of dvbt_rx_quality alone on the last finished segment's buffers, `warmup` launches and `iters` timed ones each (HIP events): ms[4][iters] in the order
+ * mer, sum, channel, rs; bytes_read[4] what each reads.  tools/quality_bench.py */
+int dvbt_debug_quality_time(dvbt_rx *h, int warmup, int iters, float *ms, int64_t *bytes_read);
 
 #ifdef __cplusplus
 }
