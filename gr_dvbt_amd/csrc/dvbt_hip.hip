@@ -318,6 +318,27 @@ struct ResamplerDesign {
   }
 };
 
+// k_drift.hpp on C calls: the scratch (doubles) and its carving, and THE launch sequence of the segment path (enqueue and dvbt_debug_drift both call it)
+static size_t drift_scratch_doubles(size_t C) { return C * DRIFT_SCRATCH_PER_CALL + DRIFT_SCRATCH_EXTRA; }
+static void drift_carve(DriftBufs &D, double *mem, size_t C)
+{
+  D.tabs = mem; D.ex_run = D.tabs + C * DRIFT_TAB; D.ex_entry = D.ex_run + C; D.d = D.ex_entry + C; D.S = D.d + C; D.e = D.S + C; D.c = D.e + C; D.A0 = D.c + C;
+}
+static void launch_drift(hipStream_t s, const FrontParams &fp, const RxState *st, const SymMeta *meta, const DriftBufs &D, int C)
+{
+  hipLaunchKernelGGL(drift_prep_kernel, dim3((C + 255) / 256), dim3(256), 0, s, fp, st, meta, D);
+  hipLaunchKernelGGL(drift_exact_kernel, dim3(1), dim3(1024), 0, s, fp, st, meta, D);
+  // three rounds of the fixed point (d ping-pongs between D.d and D.e), then the prefix sums S the table kernel reads and the test whether the last two rounds agree;
+  // where they do not, the recurrence over the calls (one wave; it returns at once otherwise)
+  const dim3 rg((C + 255) / 256);
+  hipLaunchKernelGGL(drift_round_kernel<0>, rg, dim3(256), 0, s, fp, st, meta, D, (const double *)nullptr, (const double *)nullptr, D.d);
+  hipLaunchKernelGGL(drift_round_kernel<1>, rg, dim3(256), 0, s, fp, st, meta, D, (const double *)D.d, (const double *)nullptr, D.e);
+  hipLaunchKernelGGL(drift_round_kernel<1>, rg, dim3(256), 0, s, fp, st, meta, D, (const double *)D.e, (const double *)nullptr, D.d);
+  hipLaunchKernelGGL(drift_round_kernel<2>, rg, dim3(256), 0, s, fp, st, meta, D, (const double *)D.d, (const double *)D.e, D.S);
+  hipLaunchKernelGGL(drift_seq_kernel, dim3(1), dim3(64), 0, s, fp, st, meta, D);
+  hipLaunchKernelGGL(drift_table_kernel, dim3(C), dim3(fp.N / 32 < 256 ? fp.N / 32 : 256), 0, s, fp, st, meta, D);
+}
+
 struct dvbt_rx {
   // Members are released in reverse order of declaration: the streams and events stand in front of the page-locked blocks, and those in front of the device
   // buffers that work queued on the streams uses, so the buffers go first and the streams last.  Members of pointer type own nothing: they are views
@@ -365,7 +386,7 @@ struct dvbt_rx {
   int descr_runs_cap = 0;                   // runs descr_runs holds: one per descrambler call of a stream of vit_cap bytes (descr_runs_for), DESCR_MAX_RUNS at the least
   int n_periods = 1; size_t seg_offset = 0;
   std::vector<dvbt_lock_period> periods;    // phase A of the last synchronous run
-  DriftBufs drift = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; DevMem<double> drift_mem; DevMem<float> drift_delta;   // k_drift.hpp: drift's pointers are views into these two (flags: into drift_flags_ctx)
+  DriftBufs drift = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; DevMem<double> drift_mem; DevMem<float> drift_delta;   // k_drift.hpp: drift's pointers are views into these two (flags: into drift_flags_ctx)
   struct GraphEntry { const void *iq; size_t n; hipStream_t s; long long sym_off; int delay, phase; hipGraphExec_t exec; };
   std::vector<GraphEntry> graphs;           // launch_graph: the captured launch sequences (a handful: a receiver's ring of segments)
   int ncu = 256;
@@ -482,9 +503,8 @@ extern "C" int dvbt_rx_create(const dvbt_rx_params *p, dvbt_rx **out)
     HIPCHK(hipStreamSynchronize(h->own_stream));
   }
   {   // the float phase accumulator's wander (k_drift.hpp): tables and sums per call, one deviation per 32 samples of every item
-    HIPCHK(h->drift_mem.alloc(C * (DRIFT_TAB + 4) + 8));
-    h->drift.tabs = h->drift_mem; h->drift.ex_run = h->drift.tabs + C * DRIFT_TAB; h->drift.ex_entry = h->drift.ex_run + C;
-    h->drift.d = h->drift.ex_entry + C; h->drift.S = h->drift.d + C; h->drift.A0 = h->drift.S + C;
+    HIPCHK(h->drift_mem.alloc(drift_scratch_doubles(C)));
+    drift_carve(h->drift, h->drift_mem, C);
     HIPCHK(h->drift_delta.alloc(C * (N / 32))); h->drift.delta = h->drift_delta; for (int i = 0; i < dvbt_rx::NCTX; i++) { HIPCHK(h->drift_flags_ctx[i].alloc(4)); HIPCHK(hipMemset(h->drift_flags_ctx[i], 0, 16)); }
     h->drift.flags = h->drift_flags_ctx[0];
   }
@@ -724,20 +744,11 @@ static int enqueue(dvbt_rx *h, const float2 *iq, size_t nsamples, hipStream_t s,
   // a period found by acq_small_kernel whose state block the host has just read back: the drift model's verdict is known (and flags[1] cleared on the device)
   const bool drift_off = o.skip_acq && h->st_host->drift_known_off;
   if (!drift_off) {
-    // the wander of the reference's float phase accumulator (k_drift.hpp): tables per call, the fixed point (one workgroup), the deviations per 32-sample block;
+    // the wander of the reference's float phase accumulator (k_drift.hpp): tables per call, the fixed point (or the recurrence), the deviations per 32-sample block;
     // every kernel returns at once when the lock period has no usable carrier offset (drift.flags, device side: no host round trip).  (Round 4 put the
     // launches behind drift_exact_kernel and the DRIFT instantiation on a second stream, beside the plain symbol kernel: its persistent workgroups hold every
     // VGPR of the machine, the empty launches waited for them to retire and the join cost what the fork had saved -- measured, taken out again.)
-    const DriftBufs &D = h->drift;
-    hipLaunchKernelGGL(drift_prep_kernel, dim3((C + 255) / 256), dim3(256), 0, s, fp, (const RxState *)h->st, (const SymMeta *)h->meta, D);
-    hipLaunchKernelGGL(drift_exact_kernel, dim3(1), dim3(1024), 0, s, fp, (const RxState *)h->st, (const SymMeta *)h->meta, D);
-    // three rounds of the fixed point (d ping-pongs between D.d and D.S), then the prefix sums S the table kernel reads
-    const dim3 rg((C + 255) / 256);
-    hipLaunchKernelGGL(drift_round_kernel<0>, rg, dim3(256), 0, s, fp, (const RxState *)h->st, (const SymMeta *)h->meta, D, (const double *)nullptr, D.d);
-    hipLaunchKernelGGL(drift_round_kernel<1>, rg, dim3(256), 0, s, fp, (const RxState *)h->st, (const SymMeta *)h->meta, D, (const double *)D.d, D.S);
-    hipLaunchKernelGGL(drift_round_kernel<1>, rg, dim3(256), 0, s, fp, (const RxState *)h->st, (const SymMeta *)h->meta, D, (const double *)D.S, D.d);
-    hipLaunchKernelGGL(drift_round_kernel<2>, rg, dim3(256), 0, s, fp, (const RxState *)h->st, (const SymMeta *)h->meta, D, (const double *)D.d, D.S);
-    hipLaunchKernelGGL(drift_table_kernel, dim3(C), dim3(N / 32 < 256 ? N / 32 : 256), 0, s, fp, (const RxState *)h->st, (const SymMeta *)h->meta, D);
+    launch_drift(s, fp, h->st, h->meta, h->drift, C);
   }
   const bool taps = h->acq_tap || h->fft_out || h->eq;
 #define SYM_ARGS iq, fp, (const RxState *)h->st, (const SymMeta *)h->meta, (const float2 *)h->T.tw, h->acq_tap, h->fft_out, h->T.demod_tables(), h->eq, h->tpsval, h->info, \
@@ -1676,6 +1687,45 @@ extern "C" int64_t dvbt_debug_outer_read(dvbt_rx *h, int buffer, int64_t offset,
   nbytes = std::min(nbytes, cap - (size_t)offset);
   if (nbytes) HIPCHK(hipMemcpy(dst, (const uint8_t *)p + offset, nbytes, hipMemcpyDeviceToHost));
   return (int64_t)nbytes;
+}
+
+// test hook: the kernels of k_drift.hpp alone on host-supplied calls (include/dvbt_hip.h).  path 0 is launch_drift, the segment path's own sequence; path 1 the
+// block path's per-call kernel.  The scratch doubles and delta are 0xFF bytes (NaN) before the launches; the flag words start as the caller gives them
+extern "C" int dvbt_debug_drift(int N, int cp, int nsym, const int32_t *sw, const double *incA, const double *incB, const float *ph_base, int status, int path,
+                                float *delta_host, int32_t *flags, float *ms)
+{
+  if (!sw || !incA || !incB || !ph_base || !delta_host || !flags) return fail(DVBT_ERR_INVALID, "null argument");
+  if (nsym < 0 || nsym > DVBT_DEBUG_DRIFT_MAX_CALLS) return fail(DVBT_ERR_INVALID, "nsym outside [0, DVBT_DEBUG_DRIFT_MAX_CALLS]");
+  if (path != 0 && path != 1) return fail(DVBT_ERR_INVALID, "unknown path");
+  if ((N != 2048 && N != 8192) || (cp != N / 32 && cp != N / 16 && cp != N / 8 && cp != N / 4)) return fail(DVBT_ERR_INVALID, "bad DVB-T parameters");
+  int r = need_device(); if (r) return r;
+  const int C = nsym + 257;                                       // as in a segment, more calls are launched than the period has (and the last workgroup of a round is partial)
+  const size_t nb = (size_t)N / 32, nd = drift_scratch_doubles(C);
+  FrontParams fp; memset(&fp, 0, sizeof fp); fp.N = N; fp.cp = cp; fp.ncalls = C;
+  RxState st; memset(&st, 0, sizeof st); st.status = status; st.n_symbols = nsym;
+  std::vector<SymMeta> mh((size_t)C);
+  memset(mh.data(), 0, sizeof(SymMeta) * mh.size());
+  for (int i = 0; i < nsym; i++) { mh[i].sw = sw[i]; mh[i].incA = incA[i]; mh[i].incB = incB[i]; mh[i].ph_base = ph_base[i]; }
+  DevMem<double> mem; DevMem<float> delta; DevMem<int> dfl; DevMem<SymMeta> meta; DevMem<RxState> dst; Event e0, e1;
+  HIPCHK(mem.alloc(nd)); HIPCHK(delta.alloc((size_t)C * nb)); HIPCHK(dfl.alloc(4)); HIPCHK(meta.alloc(C)); HIPCHK(dst.alloc(1));
+  HIPCHK(e0.create()); HIPCHK(e1.create());
+  HIPCHK(hipMemset(mem, 0xFF, sizeof(double) * nd)); HIPCHK(hipMemset(delta, 0xFF, sizeof(float) * C * nb));
+  const int fl4[4] = {flags[0], flags[1], flags[2], flags[3]};
+  HIPCHK(hipMemcpy(dfl, fl4, sizeof fl4, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(meta, mh.data(), sizeof(SymMeta) * mh.size(), hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(dst, &st, sizeof st, hipMemcpyHostToDevice));
+  DriftBufs D; drift_carve(D, mem, C); D.delta = delta; D.flags = dfl;
+  HIPCHK(hipEventRecord(e0, nullptr));
+  if (path == 0) launch_drift(nullptr, fp, dst, meta, D, C);
+  else hipLaunchKernelGGL(drift_table_entry_kernel, dim3(C), dim3(nb < 256 ? nb : 256), 0, nullptr, fp, (const RxState *)dst, (const SymMeta *)meta, (float *)delta, (int *)dfl);
+  HIPCHK(hipEventRecord(e1, nullptr));
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipEventSynchronize(e1));
+  if (ms) HIPCHK(hipEventElapsedTime(ms, e0, e1));
+  int out4[4];
+  HIPCHK(hipMemcpy(out4, dfl, sizeof out4, hipMemcpyDeviceToHost));
+  for (int i = 0; i < 4; i++) flags[i] = out4[i];
+  if (nsym) HIPCHK(hipMemcpy(delta_host, delta, sizeof(float) * nsym * nb, hipMemcpyDeviceToHost));
+  return DVBT_OK;
 }
 
 #include "dvbt_quality.inc"

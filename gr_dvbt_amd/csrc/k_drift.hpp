@@ -14,8 +14,14 @@
 //    its grid is finer than 2^-28);
 //  * the increment changes once per call ("run" r = the samples between the switch positions of calls r and r+1, increment -eps_r / N), so the phase at
 //    the start of run s obeys  T_{s-1}(phi_s) = T_0(phi_0) + (n_s - n_0) - sum_{r=1}^{s-1} [T_{r-1}(phi_r) - T_r(phi_r)] : the sum's terms depend on phi_r
-//    only through the small difference of two neighbouring tables, so a fixed-point iteration that evaluates them at the previous iterate (start: the exact
-//    line) and takes a prefix sum converges in two or three rounds, all runs in parallel;
+//    only through the difference of two neighbouring tables, so a fixed-point iteration evaluates them at the previous iterate (start: the exact line) and
+//    takes a prefix sum, all runs in parallel.  It is a Jacobi sweep over a triangular system: exact after as many rounds as there are calls, and after
+//    two or three only while neighbouring tables are (nearly) equal -- a steady offset, or estimates that jitter by less than the increment's rounding
+//    step.  When the increment is a few float ulps and the estimates jitter by one, the step rint(inc / ulp) * ulp jumps by 20 % from call to call and
+//    every round carries the right phase only about one call further: three rounds then leave 2e-4 .. 1e-3 rad, as much as the wander itself
+//    (tests/test_drift_model.py lists such periods).  So three rounds are run, the last two iterates are compared as phases (drift_round_kernel<2>),
+//    and a period on which they differ takes the recurrence over its calls instead: drift_seq_kernel, one drift_T and one drift_Tinv per call on
+//    the tables already built, one wave (flags[3], decided on the device);
 //  * from a call's entry phase every thread of a small kernel evaluates the deviation at one 32-sample block; the symbol kernels multiply the derotation
 //    phasor of a sample by (1 + i delta) of its block.
 //
@@ -23,6 +29,9 @@
 // call; otherwise (clean loopbacks, offsets that jitter around zero: the accumulator then lives near zero, where its grid is fine, and wanders < 1e-4)
 // nothing is applied.  The first lock period of a segment is reproduced from the reference's start state (phase 0, increment 0); later periods start
 // from phase 0 as well (the reference carries d_phase through the search calls in between; its value only sets where the binade crossings fall).
+// A limit of the closed form itself, not of the kernels: an increment that sits for thousands of calls just beside a rounding tie of one binade (8k, 17,680
+// calls, epsilon 0.0167 with a jitter of 1e-7) leaves 3.3e-5 rad even in the sequential recurrence -- under the 1.35e-4 rad that the tolerance of the
+// equalised-carrier tap corresponds to (1e-3 of the spacing at 3.7e-3 per 5e-4 rad), above the 1e-5 reached everywhere else.
 // The pure arithmetic is host-callable so that tests/test_drift_model.py can check it against the literal accumulator on the CPU.
 #pragma once
 #include "k_drift_math.hpp"
@@ -31,8 +40,10 @@ namespace dvbt {
 
 #if defined(__HIPCC__)
 // ------------------------------------------------------------------------------------------------ kernels (segment path)
-// scratch layout (doubles): tabs[C][DRIFT_TAB] | ex_run[C] | ex_entry[C] | d[C] | S[C] | A0[1]
-struct DriftBufs { double *tabs, *ex_run, *ex_entry, *d, *S, *A0; float *delta; int *flags; };   // flags[0]: sign / validity bits (collected by drift_prep_kernel, cleared by drift_exact_kernel), flags[1]: 1 = applied, flags[2]: 1 = negative increments
+// scratch layout (doubles): tabs[C][DRIFT_TAB] | ex_run[C] | ex_entry[C] | d[C] | S[C] | e[C] | c[C] | A0[1]
+struct DriftBufs { double *tabs, *ex_run, *ex_entry, *d, *S, *e, *c, *A0; float *delta; int *flags; };   // flags[0]: sign / validity bits (collected by drift_prep_kernel, cleared by drift_exact_kernel), flags[1]: 1 = applied, flags[2]: 1 = negative increments,
+                                                                                                      // flags[3]: 1 = the fixed point has not settled, the run phases are drift_seq_kernel's (in ex_run)
+constexpr int DRIFT_SCRATCH_PER_CALL = DRIFT_TAB + 6, DRIFT_SCRATCH_EXTRA = 8;   // doubles of scratch for C calls: C * PER_CALL + EXTRA
 
 __device__ __forceinline__ void drift_load(const double *tabs, int r, double *q, double *tc)
 {
@@ -66,10 +77,10 @@ __global__ __launch_bounds__(256) void drift_prep_kernel(FrontParams p, const Rx
 }
 
 // the float phase at the start of run r from the current prefix sums: T_{r-1}(phi_r) = A0 + (n_r - n_0) - S_{r-1}; first round: the exact line
-__device__ __forceinline__ double drift_phi_run(const DriftBufs &B, const SymMeta *meta, int r, int L, bool neg, bool first)
+__device__ __forceinline__ double drift_phi_run(const DriftBufs &B, const SymMeta *meta, int r, int L, bool neg, bool stored)
 {
   if (r == 0) return 0.0;
-  if (first) return B.ex_run[r];
+  if (stored) return B.ex_run[r];                              // drift_seq_kernel's
   double q[DRIFT_NR], tc[DRIFT_NR + 1];
   drift_load(B.tabs, r - 1, q, tc);
   const double steps = (double)r * L + meta[r].sw - meta[0].sw;
@@ -85,7 +96,7 @@ __global__ __launch_bounds__(1024) void drift_exact_kernel(FrontParams p, const 
   const int fl = B.flags[0];
   const bool on = !(st->status & 1) && nsym >= 2 && (fl == 1 || fl == 2);
   __syncthreads();
-  if (tid == 0) { B.flags[1] = on ? 1 : 0; B.flags[2] = fl == 2 ? 1 : 0; B.flags[0] = 0; }     // flags[0] is left clear for the next lock period's drift_prep_kernel
+  if (tid == 0) { B.flags[1] = on ? 1 : 0; B.flags[2] = fl == 2 ? 1 : 0; B.flags[3] = 0; B.flags[0] = 0; }     // flags[0] is left clear for the next lock period's drift_prep_kernel
   if (!on) return;
   const bool neg = fl == 2;
   const int per = (nsym + 1023) / 1024, sbeg = tid * per, cnt = sbeg >= nsym ? 0 : (nsym - sbeg < per ? nsym - sbeg : per);
@@ -107,31 +118,53 @@ __global__ __launch_bounds__(1024) void drift_exact_kernel(FrontParams p, const 
 // calls -- 1.5 ms on a 65-superframe segment -- loading three 31-double tables per run and round on ONE compute unit):
 //   d_r = T_{r-1}(phi_r) - T_r(phi_r) at the previous round's phases (MODE 0: the exact line), S_r = d_1 + ... + d_r.
 // The prefix S of the previous round's d is formed here: the workgroup sums everything in front of its 256 runs (at most nsym doubles from L2) and scans
-// its own.  MODE 2: that prefix alone, written out for drift_table_kernel.  d_prev / d_next ping-pong between B.d and B.S.
+// its own.  MODE 2: that prefix alone, written out for drift_table_kernel, and beside it the prefix of (d_prev - d_old), d_old being the round before:
+// where the two prefixes give phases further apart than DRIFT_SETTLED allows for the period's jumps c_r (written by MODE 0, summed here), flags[3] is raised.  d_prev / d_next ping-pong between B.d and B.e.
 template <int MODE> __global__ __launch_bounds__(256) void drift_round_kernel(FrontParams p, const RxState *st, const SymMeta *__restrict__ meta, DriftBufs B,
-                                                                              const double *__restrict__ d_prev, double *__restrict__ d_next)
+                                                                              const double *__restrict__ d_prev, const double *__restrict__ d_old, double *__restrict__ d_next)
 {
-  __shared__ double s_red[256];
+  __shared__ double s_red[256], s_dif[256], s_amp;
   if (!B.flags[1]) return;
   const int tid = threadIdx.x, nsym = st->n_symbols, L = p.N + p.cp, base = blockIdx.x * 256, r = base + tid;
   if (base >= nsym) return;
   const bool neg = B.flags[2] != 0;
   double s_before = 0.0;                                          // S_{r-1} of the previous round
   if (MODE != 0) {
-    double acc = 0.0;
-    for (int i = tid; i < base; i += 256) acc += d_prev[i];
-    s_red[tid] = acc;
+    double acc = 0.0, acd = 0.0;
+    for (int i = tid; i < base; i += 256) { const double v = d_prev[i]; acc += v; if (MODE == 2) acd += v - d_old[i]; }
+    s_red[tid] = acc; if (MODE == 2) s_dif[tid] = acd;
     __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) { if (tid < o) s_red[tid] += s_red[tid + o]; __syncthreads(); }
-    const double front = s_red[0];
+    for (int o = 128; o > 0; o >>= 1) { if (tid < o) { s_red[tid] += s_red[tid + o]; if (MODE == 2) s_dif[tid] += s_dif[tid + o]; } __syncthreads(); }
+    const double front = s_red[0], front_d = MODE == 2 ? s_dif[0] : 0.0;
     __syncthreads();
+    if (MODE == 2) {                                              // A of DRIFT_SETTLED: the jumps of the whole period
+      double a = 0.0;
+      for (int i = tid; i < nsym; i += 256) a += B.c[i];
+      s_red[tid] = a;
+      __syncthreads();
+      for (int o = 128; o > 0; o >>= 1) { if (tid < o) s_red[tid] += s_red[tid + o]; __syncthreads(); }
+      if (tid == 0) s_amp = s_red[0];
+      __syncthreads();
+    }
     const double v = r < nsym ? d_prev[r] : 0.0;
-    s_red[tid] = v;
+    s_red[tid] = v; if (MODE == 2) s_dif[tid] = r < nsym ? v - d_old[r] : 0.0;
     __syncthreads();
-    for (int off = 1; off < 256; off <<= 1) { const double u = tid >= off ? s_red[tid - off] : 0.0; __syncthreads(); s_red[tid] += u; __syncthreads(); }
+    for (int off = 1; off < 256; off <<= 1) {
+      const double u = tid >= off ? s_red[tid - off] : 0.0, ud = (MODE == 2 && tid >= off) ? s_dif[tid - off] : 0.0;
+      __syncthreads();
+      s_red[tid] += u; if (MODE == 2) s_dif[tid] += ud;
+      __syncthreads();
+    }
     const double incl = front + s_red[tid];
     s_before = incl - v;
-    if (MODE == 2) { if (r < nsym) d_next[r] = incl; return; }
+    if (MODE == 2) {
+      if (r < nsym) {
+        d_next[r] = incl;
+        // S_r sets the phase at the start of run r + 1 through T_r^-1: a step of run r is at most 1.25 |inc_r| (rint(a / u) u <= a + u / 2, a >= 2 u)
+        if (fabs(front_d + s_dif[tid]) * 1.25 * fabs(meta[r].incB) * (1.0 + 1.5 * s_amp) > DRIFT_SETTLED) B.flags[3] = 1;
+      }
+      return;
+    }
   }
   if (r >= nsym) return;
   double dr = 0.0;
@@ -142,8 +175,40 @@ template <int MODE> __global__ __launch_bounds__(256) void drift_round_kernel(Fr
     const double a = drift_T(q, tc, neg, phi);
     drift_load(B.tabs, r, q, tc);
     dr = a - drift_T(q, tc, neg, phi);
-  }
+    if (MODE == 0) B.c[r] = drift_jump(B.tabs + (size_t)(r - 1) * DRIFT_TAB, q);
+  } else if (MODE == 0) B.c[0] = 0.0;
   d_next[r] = dr;
+}
+
+// The recurrence over the calls, for a period on which the fixed point has not settled (flags[3]): phi_{r+1} = T_r^-1(T_r(phi_r) + n_{r+1} - n_r), run after
+// run from phi_0 = 0, on the tables of drift_prep_kernel.  One wave: it stages DRIFT_SEQ_CHUNK tables in LDS at a time (all lanes), lane 0 walks them.
+// The phases go to ex_run (the exact line there is not needed behind the first round); drift_table_kernel takes them from there.
+constexpr int DRIFT_SEQ_CHUNK = 64;
+__global__ __launch_bounds__(64) void drift_seq_kernel(FrontParams p, const RxState *st, const SymMeta *__restrict__ meta, DriftBufs B)
+{
+  __shared__ double s_tab[DRIFT_SEQ_CHUNK * DRIFT_TAB], s_steps[DRIFT_SEQ_CHUNK], s_phi[DRIFT_SEQ_CHUNK], s_carry;
+  if (!B.flags[1] || !B.flags[3]) return;
+  const int lane = threadIdx.x, nsym = st->n_symbols, L = p.N + p.cp;
+  const bool neg = B.flags[2] != 0;
+  if (lane == 0) s_carry = 0.0;                                   // run 0 starts at phase 0
+  for (int base = 0; base + 1 < nsym; base += DRIFT_SEQ_CHUNK) {  // runs base .. base + cnt - 1 give the phases of runs base + 1 .. base + cnt
+    const int cnt = nsym - 1 - base < DRIFT_SEQ_CHUNK ? nsym - 1 - base : DRIFT_SEQ_CHUNK;
+    __syncthreads();
+    for (int i = lane; i < cnt * DRIFT_TAB; i += 64) s_tab[i] = B.tabs[(size_t)base * DRIFT_TAB + i];
+    for (int i = lane; i < cnt; i += 64) s_steps[i] = (double)(L + meta[base + i + 1].sw - meta[base + i].sw);
+    __syncthreads();
+    if (lane == 0) {
+      double phi = s_carry;
+      for (int i = 0; i < cnt; i++) {
+        const double *q = s_tab + i * DRIFT_TAB, *tc = q + 16;
+        phi = drift_Tinv(q, tc, neg, drift_T(q, tc, neg, phi) + s_steps[i]);
+        s_phi[i] = phi;
+      }
+      s_carry = phi;
+    }
+    __syncthreads();
+    for (int i = lane; i < cnt; i += 64) B.ex_run[base + 1 + i] = s_phi[i];
+  }
 }
 
 // one workgroup per call, one thread per 32-sample block of the item: delta[s][k] = (float phase - exact line) after step 32 k + 17, relative to the call's entry
@@ -158,7 +223,7 @@ __global__ __launch_bounds__(256) void drift_table_kernel(FrontParams p, const R
   if (k == 0) {
     double ent = 0.0;
     if (s > 0) {   // the entry lies in run s - 1, (s L - n_{s-1}) steps after its start
-      const double phr = drift_phi_run(B, meta, s - 1, L, neg, false);
+      const double phr = drift_phi_run(B, meta, s - 1, L, neg, B.flags[3] != 0);
       double q[DRIFT_NR], tc[DRIFT_NR + 1];
       drift_load(B.tabs, s - 1, q, tc);
       ent = drift_Tinv(q, tc, neg, drift_T(q, tc, neg, phr) + (double)(L - meta[s - 1].sw));

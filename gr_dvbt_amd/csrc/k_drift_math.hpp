@@ -18,6 +18,14 @@ constexpr int DRIFT_TAB = 32;                      // doubles per table in memor
 constexpr double DRIFT_PI_F = 3.1415927410125732;  // (float)M_PI: the wrap limits of the reference (:297-300)
 constexpr double DRIFT_2PI_F = 6.2831854820251465; // (float)(2.0 * M_PI)
 constexpr double DRIFT_MIN_INC = 2.0 * 2.384185791015625e-07;   // 2 ulp of [2, 4): below that the accumulator's steps are granular (rint = 0 or 1)
+// When the last two iterates of the fixed point count as equal.  If they were equal exactly, the iterate would be the triangular system's one solution.  With the
+// phases of the two iterates e apart at the worst, the iterate is at most e (1 + 1.5 A) from the solution: a change of the phase at run r changes d_r =
+// T_{r-1}(phi_r) - T_r(phi_r) by (1 / q_{r-1} - 1 / q_r) of it, a share c_r = max_j |q_{r-1}[j] / q_r[j] - 1| of the phase itself, and what the phase at a later
+// run owes to the one at run r is a ratio of two steps (the slope of T^-1 o T, telescoped), <= 1.5; A = the sum of c_r over the period's runs
+// (drift_jump, summed by drift_round_kernel<2>).  A steady offset has A near 0 (its tables are equal but for a step of one ulp now and then) and may differ by
+// all of DRIFT_SETTLED; a period whose step jumps between 4 and 5 ulp at every call has A = 0.25 per call and has to agree 1,000 times better.  DRIFT_SETTLED
+// is a quarter of the 1e-5 rad that the tests hold the deviations to, beside the closed form's own error (up to 7.4e-6 on the tested periods, sequential).
+constexpr double DRIFT_SETTLED = 2.5e-6;
 
 DRIFT_HD double drift_bnd(int j)                   // lower boundary of region j (j = DRIFT_NR: the upper end)
 {
@@ -54,6 +62,13 @@ DRIFT_HD void drift_build(double inc, double *q /* [DRIFT_NR] */, double *tc /* 
     t += (drift_bnd(j + 1) - drift_bnd(j)) / qq;
   }
   tc[DRIFT_NR] = t;
+}
+// c_r of DRIFT_SETTLED: how far the steps of two neighbouring tables differ, relative
+DRIFT_HD double drift_jump(const double *q_prev, const double *q)
+{
+  double c = 0.0;
+  for (int j = 0; j < DRIFT_NR; j++) { const double v = fabs(q_prev[j] / q[j] - 1.0); c = v > c ? v : c; }
+  return c;
 }
 // T(phi): steps needed from the (virtual) phase -PI_F of cycle 0 to the unwrapped float phase phi.  neg: the increment is negative (mirror)
 DRIFT_HD double drift_T(const double *q, const double *tc, bool neg, double phi)

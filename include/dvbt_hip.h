@@ -846,6 +846,21 @@ int dvbt_debug_outer(dvbt_rx *h, int mode, const uint8_t *vit_host, int64_t n_by
 /* nbytes bytes from byte `offset` of one of the buffers above (DVBT_OUTER_BUF_*), within its capacity; returns the bytes copied */
 int64_t dvbt_debug_outer_read(dvbt_rx *h, int buffer, int64_t offset, void *dst, size_t nbytes);
 
+/* the kernels that reproduce the reference's float phase accumulator (csrc/k_drift.hpp) alone, on nsym host-supplied calls of a lock period: sw[s] the sample of call s
+ * at which the increment switches from incA[s] to incB[s] (rad per sample), ph_base[s] the accumulator's float value at the call's entry (block path only), `status` the
+ * state block's status word, N / cp any transmission mode with any of its guard intervals.  path 0: the segment path's launch sequence (enqueue's own: tables, exact
+ * line, three rounds of the fixed point, the prefix and its convergence test, the recurrence where that fails, the deviations); path 1: the block path's per-call
+ * kernel.  More calls are launched than nsym, as in a segment.  The scratch and delta are 0xFF bytes (NaN) on the device before the launches.  flags[4], in and out:
+ * the device's flag words start as given (all 0 for a fresh handle; a second call may pass on what the first returned) and are read back behind the launches:
+ * [0] the sign / validity bits drift_prep_kernel collects (cleared again by drift_exact_kernel), [1] 1 = the deviations apply, [2] 1 = negative increments, [3] 1 = the fixed point's last two rounds disagreed and the recurrence over the calls was taken.
+ * delta_host float[nsym][N / 32]: the deviation (rad) of the float accumulator from the exact line at sample 32 k + 17 of call s, relative to the call's entry.
+ * ms (may be NULL): the launch sequence's time between two events.  DVBT_ERR_INVALID, nothing allocated or launched, for a null pointer, nsym outside
+ * [0, DVBT_DEBUG_DRIFT_MAX_CALLS] (what the hook sizes its scratch for), an unknown path or an N / cp that is no mode / guard pair; behind those checks
+ * DVBT_ERR_NO_DEVICE without a GPU.  tests/test_gpu_drift_kernels.py */
+enum { DVBT_DEBUG_DRIFT_MAX_CALLS = 65536 };
+int dvbt_debug_drift(int N, int cp, int nsym, const int32_t *sw, const double *incA, const double *incB, const float *ph_base, int status, int path,
+                     float *delta_host, int32_t *flags, float *ms);
+
 /* the channel-error kernel alone (csrc/k_quality.hpp) on host bytes: in_host = n_in decoder input bytes (m bits each), vit_host = n_vit decoded bytes; counts as
  * dvbt_rx_quality's channel_bits / channel_bit_errors (n_vit < 2: both 0).  Sizes outside [0, 2^30] are refused before the device is asked for. */
 int dvbt_debug_quality_channel(int constellation, int code_rate, const uint8_t *in_host, int64_t n_in, const uint8_t *vit_host, int64_t n_vit, int64_t *bits, int64_t *errors);

@@ -75,6 +75,17 @@ def test_no_cpu_fallback(g):
     for mode in (0, 1, 2):
         assert L.dvbt_debug_outer(None, mode, buf, 204, 0, 0, rep, None, 0) == -2
     assert L.dvbt_debug_outer_read(None, 1, 0, buf, 8) == -2
+    # dvbt_debug_drift: null pointers, a negative nsym, more calls than its scratch is sized for, an unknown path, an N / cp that is no mode / guard pair
+    L.dvbt_debug_drift.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    sw, inc, ph, fl, delta = (C.c_int32 * 4)(), (C.c_double * 4)(), (C.c_float * 4)(), (C.c_int32 * 4)(), (C.c_float * (4 * 256))()
+    ok = [8192, 256, 4, sw, inc, inc, ph, 0, 0, delta, fl, None]
+    for i, v in ((3, None), (4, None), (5, None), (6, None), (9, None), (10, None), (2, -1), (2, 65537), (8, 2), (8, -1),
+                 (0, 4096), (0, 0), (1, 0), (1, 255), (1, 4096), (1, 128)):
+        bad = list(ok)
+        bad[i] = v
+        assert L.dvbt_debug_drift(*bad) == -1, (i, v)
+    for N, cp, path in ((8192, 256, 0), (8192, 2048, 1), (2048, 64, 0), (2048, 512, 1), (2048, 128, 0), (8192, 1024, 0)):
+        assert L.dvbt_debug_drift(N, cp, 4, sw, inc, inc, ph, 0, path, delta, fl, None) == -2
 
 
 def test_product_does_not_import_oracle():

@@ -70,6 +70,9 @@ CLEAN = [
     ("8k cfo +0.0001", K8, dict(cfo=0.0001)),             # below it: granular steps of the accumulator, nothing applied
     ("8k echo 0.3 cp -16 dB", K8, dict(echoes=((77, 0.15),))),
     ("8k echo 0.3 cp -20 dB + cfo 2.2", K8, dict(echoes=((77, 0.1),), cfo=2.2)),
+    # a small residual offset under estimates that jitter: epsilon 0.009 .. 0.033, increments of a few ulps of the float accumulator, where the fixed point of
+    # k_drift.hpp does not settle in its three rounds and the recurrence over the calls is taken (tests/test_gpu_drift_kernels.py)
+    ("8k echo 0.3 cp -20 dB + cfo 0.003", K8, dict(echoes=((77, 0.1),), cfo=0.003)),
 ]
 
 
