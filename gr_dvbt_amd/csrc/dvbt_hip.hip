@@ -671,6 +671,34 @@ static int enqueue_tail(dvbt_rx *h, hipStream_t s, long long max_words, long lon
   return DVBT_OK;
 }
 
+// the symbol kernels of one lock period (enqueue and dvbt_debug_symbols both call it): C calls from iq on, the instantiation by the handle's taps; grid 0: as many
+// workgroups as the period keeps busy, at most sym_grid (a test hook may ask for fewer: who takes which symbol must not matter)
+static void launch_symbols(dvbt_rx *h, hipStream_t s, const float2 *iq, const FrontParams &fp, int C, bool drift_off, int grid = 0)
+{
+  const Dims &d = h->d; const int N = d.N;
+  const bool taps = h->acq_tap || h->fft_out || h->eq;
+#define SYM_ARGS iq, fp, (const RxState *)h->st, (const SymMeta *)h->meta, (const float2 *)h->T.tw, h->acq_tap, h->fft_out, h->T.demod_tables(), h->eq, h->tpsval, h->info, \
+                 h->T.inner_params(d.payload), (const float2 *)h->T.points, (const unsigned char *)h->T.label_tab, h->labels, h->sym_ticket, (const float *)h->drift.delta, (const int *)h->drift.flags, h->csi
+  // 8k: persistent workgroups, two per CU (k_symbol8k.hpp); 2k: the same design, four symbols per workgroup (k_symbol2k.hpp).  The plain and the DRIFT
+  // instantiation are both launched: the one that drift.flags[1] does not select returns before it takes a symbol
+  // (the persistent workgroups take symbols off a ticket: a short lock period launches no more of them than it has symbols)
+  const int g8 = grid > 0 ? grid : std::min(h->sym_grid, C), g2 = grid > 0 ? grid : std::min(h->sym_grid, (C + S2_Q - 1) / S2_Q);
+  if (N == S8_N && !taps) {
+    hipLaunchKernelGGL((symbol8k_kernel<false, false>), dim3(g8), dim3(S8_T), S8_LDS_BYTES, s, SYM_ARGS);
+    if (!drift_off) hipLaunchKernelGGL((symbol8k_kernel<false, true>), dim3(g8), dim3(S8_T), S8_LDS_BYTES, s, SYM_ARGS);
+  } else if (N == S8_N) {
+    hipLaunchKernelGGL((symbol8k_kernel<true, false>), dim3(g8), dim3(S8_T), S8_LDS_BYTES, s, SYM_ARGS);
+    if (!drift_off) hipLaunchKernelGGL((symbol8k_kernel<true, true>), dim3(g8), dim3(S8_T), S8_LDS_BYTES, s, SYM_ARGS);
+  } else if (N == S2_N && !taps) {
+    hipLaunchKernelGGL((symbol2k_kernel<false, false>), dim3(g2), dim3(S2_T * S2_Q), S2_LDS_BYTES, s, SYM_ARGS);
+    if (!drift_off) hipLaunchKernelGGL((symbol2k_kernel<false, true>), dim3(g2), dim3(S2_T * S2_Q), S2_LDS_BYTES, s, SYM_ARGS);
+  } else if (N == S2_N) {
+    hipLaunchKernelGGL((symbol2k_kernel<true, false>), dim3(g2), dim3(S2_T * S2_Q), S2_LDS_BYTES, s, SYM_ARGS);
+    if (!drift_off) hipLaunchKernelGGL((symbol2k_kernel<true, true>), dim3(g2), dim3(S2_T * S2_Q), S2_LDS_BYTES, s, SYM_ARGS);
+  }
+#undef SYM_ARGS
+}
+
 // one lock period of the chain, iq at the OFDM elementary rate
 static int enqueue(dvbt_rx *h, const float2 *iq, size_t nsamples, hipStream_t s, const EnqOpt &o = EnqOpt())
 {
@@ -750,27 +778,7 @@ static int enqueue(dvbt_rx *h, const float2 *iq, size_t nsamples, hipStream_t s,
     // VGPR of the machine, the empty launches waited for them to retire and the join cost what the fork had saved -- measured, taken out again.)
     launch_drift(s, fp, h->st, h->meta, h->drift, C);
   }
-  const bool taps = h->acq_tap || h->fft_out || h->eq;
-#define SYM_ARGS iq, fp, (const RxState *)h->st, (const SymMeta *)h->meta, (const float2 *)h->T.tw, h->acq_tap, h->fft_out, h->T.demod_tables(), h->eq, h->tpsval, h->info, \
-                 h->T.inner_params(d.payload), (const float2 *)h->T.points, (const unsigned char *)h->T.label_tab, h->labels, h->sym_ticket, (const float *)h->drift.delta, (const int *)h->drift.flags, h->csi
-  // 8k: persistent workgroups, two per CU (k_symbol8k.hpp); 2k: the same design, four symbols per workgroup (k_symbol2k.hpp).  The plain and the DRIFT
-  // instantiation are both launched: the one that drift.flags[1] does not select returns before it takes a symbol
-  // (the persistent workgroups take symbols off a ticket: a short lock period launches no more of them than it has symbols)
-  const int g8 = std::min(h->sym_grid, C), g2 = std::min(h->sym_grid, (C + S2_Q - 1) / S2_Q);
-  if (N == S8_N && !taps) {
-    hipLaunchKernelGGL((symbol8k_kernel<false, false>), dim3(g8), dim3(S8_T), S8_LDS_BYTES, s, SYM_ARGS);
-    if (!drift_off) hipLaunchKernelGGL((symbol8k_kernel<false, true>), dim3(g8), dim3(S8_T), S8_LDS_BYTES, s, SYM_ARGS);
-  } else if (N == S8_N) {
-    hipLaunchKernelGGL((symbol8k_kernel<true, false>), dim3(g8), dim3(S8_T), S8_LDS_BYTES, s, SYM_ARGS);
-    if (!drift_off) hipLaunchKernelGGL((symbol8k_kernel<true, true>), dim3(g8), dim3(S8_T), S8_LDS_BYTES, s, SYM_ARGS);
-  } else if (N == S2_N && !taps) {
-    hipLaunchKernelGGL((symbol2k_kernel<false, false>), dim3(g2), dim3(S2_T * S2_Q), S2_LDS_BYTES, s, SYM_ARGS);
-    if (!drift_off) hipLaunchKernelGGL((symbol2k_kernel<false, true>), dim3(g2), dim3(S2_T * S2_Q), S2_LDS_BYTES, s, SYM_ARGS);
-  } else if (N == S2_N) {
-    hipLaunchKernelGGL((symbol2k_kernel<true, false>), dim3(g2), dim3(S2_T * S2_Q), S2_LDS_BYTES, s, SYM_ARGS);
-    if (!drift_off) hipLaunchKernelGGL((symbol2k_kernel<true, true>), dim3(g2), dim3(S2_T * S2_Q), S2_LDS_BYTES, s, SYM_ARGS);
-  }
-#undef SYM_ARGS
+  launch_symbols(h, s, iq, fp, C, drift_off);
   if (tm) HIPCHK(hipEventRecord(h->ev[ST_DEMOD], s));
   if (!o.continuation) {
     hipLaunchKernelGGL(tps_vote_kernel, dim3((C + 63) / 64), dim3(256), 0, s, (const float2 *)h->tpsval, d.n_tps, (const RxState *)h->st, 0,
@@ -1725,6 +1733,77 @@ extern "C" int dvbt_debug_drift(int N, int cp, int nsym, const int32_t *sw, cons
   HIPCHK(hipMemcpy(out4, dfl, sizeof out4, hipMemcpyDeviceToHost));
   for (int i = 0; i < 4; i++) flags[i] = out4[i];
   if (nsym) HIPCHK(hipMemcpy(delta_host, delta, sizeof(float) * nsym * nb, hipMemcpyDeviceToHost));
+  return DVBT_OK;
+}
+
+// test hook: the symbol kernels alone on host-supplied samples and per-symbol metadata (include/dvbt_hip.h).  The launch is launch_symbols, enqueue's own; what the
+// acquisition leaves behind for it -- the state block's n_symbols / call0, the SymMeta rows, the zeroed ticket, the drift flag word and table -- is set from the arguments
+extern "C" int dvbt_debug_symbols(dvbt_rx *h, const void *iq_host, size_t nsamples, int nsym, int call0, int keep_last, int64_t avail, const int32_t *cp_start,
+                                  const int32_t *sw, const float *ph_base, const double *incA, const double *incB, int grid, const float *delta_host, int nread,
+                                  uint8_t *labels, int32_t *freq_offset, int32_t *mod_index, void *tpsval, void *acq, void *fft, void *eq, float *csi)
+{
+  if (!iq_host || !cp_start || !sw || !ph_base || !incA || !incB) return fail(DVBT_ERR_INVALID, "null argument");
+  if (nsym < 1) return fail(DVBT_ERR_INVALID, "nsym must be at least 1");
+  if (grid < 0) return fail(DVBT_ERR_INVALID, "grid must be 0 (enqueue's choice) or lie in [1, the handle's sym_grid]");
+  if (nsamples == 0 || nsamples > ((size_t)1 << 31) || avail <= 0 || (uint64_t)avail > nsamples) return fail(DVBT_ERR_INVALID, "avail must lie in (0, nsamples]");
+  if (call0 < 0 || call0 > (1 << 20) || nread < 0) return fail(DVBT_ERR_INVALID, "call0 must lie in [0, 2^20], nread must not be negative");
+  for (int i = 0; i < nsym; i++)
+    if (!std::isfinite(ph_base[i]) || !std::isfinite(incA[i]) || !std::isfinite(incB[i])) return fail(DVBT_ERR_INVALID, "non-finite ph_base / incA / incB");
+  { int nd = need_device(); if (nd) return nd; }                   // (a handle exists only where a device does)
+  if (!h) return fail(DVBT_ERR_INVALID, "null handle");
+  if (h->pending) return fail(DVBT_ERR_STATE, "dvbt_debug_symbols: a segment is in flight (dvbt_rx_segment_finish first)");
+  const Dims &d = h->d;
+  const size_t C = (size_t)h->max_calls, N = (size_t)d.N, P = (size_t)d.payload, nb = N / 32;
+  if ((size_t)nsym > C) return fail(DVBT_ERR_INVALID, "nsym beyond what the handle's buffers hold (max_samples)");
+  if (grid > h->sym_grid) return fail(DVBT_ERR_INVALID, "grid must be 0 (enqueue's choice) or lie in [1, the handle's sym_grid]");
+  if (nread == 0) nread = nsym;
+  if (nread < nsym || (size_t)nread > C) return fail(DVBT_ERR_INVALID, "nread must be 0 (nsym) or lie in [nsym, the symbols the handle's buffers hold]");
+  for (int i = 0; i < nsym; i++)      // the kernels' range check is the upper one alone (FrontParams.avail): no window may begin in front of the buffer
+    if ((long long)(call0 + i) * (d.N + d.cp) + (long long)cp_start[i] - d.N + 1 < 0) return fail(DVBT_ERR_INVALID, "a symbol's window begins before sample 0");
+  if (delta_host)
+    for (size_t i = 0; i < (size_t)nsym * nb; i++)
+      if (!(std::fabs(delta_host[i]) < 2e-3f)) return fail(DVBT_ERR_INVALID, "|delta| must stay below 2e-3 (symbol8k_kernel's precondition)");
+  HIPCHK(hipSetDevice(h->prm.device));
+  hipStream_t s = h->own_stream;
+  DevMem<float2> iq; HIPCHK(iq.alloc(nsamples));
+  std::vector<SymMeta> mh((size_t)nsym);
+  memset(mh.data(), 0, sizeof(SymMeta) * mh.size());
+  for (int i = 0; i < nsym; i++) { mh[i].cp_start = cp_start[i]; mh[i].sw = sw[i]; mh[i].ph_base = ph_base[i]; mh[i].incA = incA[i]; mh[i].incB = incB[i]; }
+  // every buffer the kernels write: 0xA5 up to its capacity
+  HIPCHK(hipMemsetAsync(h->labels, 0xA5, C * P + 64, s)); HIPCHK(hipMemsetAsync(h->tpsval, 0xA5, sizeof(float2) * C * d.n_tps, s)); HIPCHK(hipMemsetAsync(h->info, 0xA5, sizeof(SymInfo) * C, s));
+  if (h->acq_tap) HIPCHK(hipMemsetAsync(h->acq_tap, 0xA5, sizeof(float2) * C * N, s));
+  if (h->fft_out) HIPCHK(hipMemsetAsync(h->fft_out, 0xA5, sizeof(float2) * C * N, s));
+  if (h->eq) HIPCHK(hipMemsetAsync(h->eq, 0xA5, sizeof(float2) * C * P, s));
+  if (h->csi) HIPCHK(hipMemsetAsync(h->csi, 0xA5, sizeof(float) * C * P, s));
+  HIPCHK(hipMemsetAsync(h->meta, 0, sizeof(SymMeta) * C, s));
+  HIPCHK(hipMemcpyAsync(iq, iq_host, sizeof(float2) * nsamples, hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(h->meta, mh.data(), sizeof(SymMeta) * mh.size(), hipMemcpyHostToDevice, s));
+  RxState plan; memset(&plan, 0, sizeof plan); plan.n_symbols = nsym; plan.call0 = call0; plan.first_out = -1;
+  *h->st_host = plan;
+  HIPCHK(hipMemcpyAsync(h->st, h->st_host, sizeof(RxState), hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemsetAsync(h->sym_ticket, 0, sizeof(int), s));
+  const int fl4[4] = {0, delta_host ? 1 : 0, 0, 0};
+  HIPCHK(hipMemcpyAsync(h->drift.flags, fl4, sizeof fl4, hipMemcpyHostToDevice, s));
+  if (delta_host) HIPCHK(hipMemcpyAsync(h->drift.delta, delta_host, sizeof(float) * nsym * nb, hipMemcpyHostToDevice, s));
+  HIPCHK(hipStreamSynchronize(s));                                 // (the sources are the caller's memory and locals)
+  FrontParams fp = h->fp;
+  fp.ncalls = nsym; fp.hist = 0; fp.keep_last = keep_last ? 1 : 0; fp.avail = avail;
+  launch_symbols(h, s, iq, fp, nsym, false, grid);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemsetAsync(h->sym_ticket, 0, sizeof(int), s)); HIPCHK(hipMemsetAsync(h->drift.flags, 0, sizeof fl4, s));   // as a fresh handle's
+  HIPCHK(hipStreamSynchronize(s));
+  const size_t R = (size_t)nread;
+  if (labels) HIPCHK(hipMemcpy(labels, h->labels, R * P, hipMemcpyDeviceToHost));
+  if (freq_offset || mod_index) {
+    std::vector<SymInfo> si(R);
+    HIPCHK(hipMemcpy(si.data(), h->info, sizeof(SymInfo) * R, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < R; i++) { if (freq_offset) freq_offset[i] = si[i].freq_offset; if (mod_index) mod_index[i] = si[i].mod_index; }
+  }
+  if (tpsval) HIPCHK(hipMemcpy(tpsval, h->tpsval, sizeof(float2) * R * d.n_tps, hipMemcpyDeviceToHost));
+  if (acq && h->acq_tap) HIPCHK(hipMemcpy(acq, h->acq_tap, sizeof(float2) * R * N, hipMemcpyDeviceToHost));
+  if (fft && h->fft_out) HIPCHK(hipMemcpy(fft, h->fft_out, sizeof(float2) * R * N, hipMemcpyDeviceToHost));
+  if (eq && h->eq) HIPCHK(hipMemcpy(eq, h->eq, sizeof(float2) * R * P, hipMemcpyDeviceToHost));
+  if (csi && h->csi) HIPCHK(hipMemcpy(csi, h->csi, sizeof(float) * R * P, hipMemcpyDeviceToHost));
   return DVBT_OK;
 }
 

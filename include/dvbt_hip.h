@@ -861,6 +861,23 @@ enum { DVBT_DEBUG_DRIFT_MAX_CALLS = 65536 };
 int dvbt_debug_drift(int N, int cp, int nsym, const int32_t *sw, const double *incA, const double *incB, const float *ph_base, int status, int path,
                      float *delta_host, int32_t *flags, float *ms);
 
+/* the per-symbol kernels of the segment path alone (csrc/k_symbol8k.hpp, csrc/k_symbol2k.hpp: derotation, FFT, pilot engine, equaliser, demapper) through the segment
+ * path's own launch routine (launch_symbols of csrc/dvbt_hip.hip, which enqueue calls), on the handle's tables and buffers.  Mode, constellation, hierarchy, guard
+ * interval, soft decisions and the tap state are the handle's, the instantiation the one a segment would get.  From the host: nsamples complex64 samples; nsym symbols
+ * whose state block says call0; keep_last and avail (samples in memory: reads at or beyond it return zeros) as in FrontParams; per symbol cp_start, sw, ph_base, incA,
+ * incB as the acquisition's SymMeta (symbol s reads the N samples from (call0 + s)(N + cp) + cp_start - N + 1 on); grid: workgroups, 0 = as a segment of nsym calls;
+ * delta_host: NULL, or float[nsym][N / 32] deviations -- then the drift flag word is 1 and the DRIFT instantiation works.  Every buffer the kernels write is 0xA5 up
+ * to its capacity before the launch, the ticket is zero; behind it the ticket and the drift flag words are zero again.  Outputs (each may be NULL), nread symbols each
+ * (0: nsym; more than nsym shows what lies behind the last symbol): labels uint8[nread][payload], freq_offset / mod_index int32[nread], tpsval cfloat[nread][n_tps],
+ * acq / fft cfloat[nread][N], eq cfloat[nread][payload], csi float[nread][payload] -- a tap the handle does not have (dvbt_rx_enable_taps; csi: soft decisions) leaves
+ * its array as it was.  DVBT_ERR_INVALID, nothing allocated or launched, for: a null required pointer; nsym < 1 or beyond the calls the handle's buffers hold; grid
+ * outside [0, the handle's workgroup count]; avail outside (0, nsamples]; a non-finite ph_base / incA / incB; a symbol whose window begins before sample 0 (the kernels
+ * check the upper bound only); |delta| >= 2e-3 (the kernels' stated precondition); nread outside [nsym, capacity].  Behind the checks that need no handle
+ * DVBT_ERR_NO_DEVICE without a GPU.  tests/test_gpu_symbol_kernels.py */
+int dvbt_debug_symbols(dvbt_rx *h, const void *iq_host, size_t nsamples, int nsym, int call0, int keep_last, int64_t avail, const int32_t *cp_start,
+                       const int32_t *sw, const float *ph_base, const double *incA, const double *incB, int grid, const float *delta_host, int nread,
+                       uint8_t *labels, int32_t *freq_offset, int32_t *mod_index, void *tpsval, void *acq, void *fft, void *eq, float *csi);
+
 /* the channel-error kernel alone (csrc/k_quality.hpp) on host bytes: in_host = n_in decoder input bytes (m bits each), vit_host = n_vit decoded bytes; counts as
  * dvbt_rx_quality's channel_bits / channel_bit_errors (n_vit < 2: both 0).  Sizes outside [0, 2^30] are refused before the device is asked for. */
 int dvbt_debug_quality_channel(int constellation, int code_rate, const uint8_t *in_host, int64_t n_in, const uint8_t *vit_host, int64_t n_vit, int64_t *bits, int64_t *errors);

@@ -86,6 +86,18 @@ def test_no_cpu_fallback(g):
         assert L.dvbt_debug_drift(*bad) == -1, (i, v)
     for N, cp, path in ((8192, 256, 0), (8192, 2048, 1), (2048, 64, 0), (2048, 512, 1), (2048, 128, 0), (8192, 1024, 0)):
         assert L.dvbt_debug_drift(N, cp, 4, sw, inc, inc, ph, 0, path, delta, fl, None) == -2
+    # dvbt_debug_symbols: what it can refuse without a handle (null pointers, nsym < 1, a negative grid, avail outside (0, nsamples], a negative call0 or nread, non-finite
+    # phases) before it asks for the device; the refusals that need the handle's sizes are in tests/test_gpu_symbol_kernels.py
+    L.dvbt_debug_symbols.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int64] + [C.c_void_p] * 5 + [C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 8
+    iq, cps, phs = (C.c_float * (2 * 4096))(), (C.c_int32 * 4)(), (C.c_float * 4)()
+    nan_f, inf_d = (C.c_float * 4)(0, float("nan"), 0, 0), (C.c_double * 4)(0, 0, 0, float("inf"))
+    ok = [None, iq, 4096, 4, 0, 1, 4096, cps, sw, phs, inc, inc, 0, None, 0] + [None] * 8
+    for i, v in ((1, None), (7, None), (8, None), (9, None), (10, None), (11, None), (3, 0), (3, -2), (12, -1), (6, 0), (6, -1), (6, 4097), (2, 0), (4, -1), (14, -1),
+                 (9, nan_f), (10, inf_d), (11, inf_d)):
+        bad = list(ok)
+        bad[i] = v
+        assert L.dvbt_debug_symbols(*bad) == -1, (i, v)
+    assert L.dvbt_debug_symbols(*ok) == -2
 
 
 def test_product_does_not_import_oracle():
