@@ -699,6 +699,48 @@ static void launch_symbols(dvbt_rx *h, hipStream_t s, const float2 *iq, const Fr
 #undef SYM_ARGS
 }
 
+// what acq_init_fsm_kernel's reset leaves in the pilot engine's state for a period that starts it afresh (enqueue's skip_acq path and dvbt_debug_frames do the same)
+static hipError_t reset_tps_state(dvbt_rx *h, hipStream_t s) { return hipMemsetAsync(h->tps_state, 0, sizeof(TpsState), s); }
+// dvbt_rx_cut.start_delay_symbols: the hunt fires that many symbols behind the true start (enqueue and dvbt_debug_frames)
+static void cut_hunt(FrontParams &fp, const Dims &d, int cut_delay)
+{
+  fp.hunt_known = cut_delay > 0 ? 1 : 0;
+  fp.si_start = cut_delay % 68; fp.fi_start = (d.fi_start + cut_delay / 68) % 4;
+}
+
+// the frame bookkeeping and the inner stage of one lock period (enqueue and dvbt_debug_frames both call it): DBPSK vote, TPS bookkeeping (segment-parallel with the
+// sequential fallback, or sequential alone for a continuation), the sizes behind it, then A5 + A6 on the labels -- the last not for a soft-decision handle, whose
+// demapper reads sym_index itself.  ev_inner: recorded between the bookkeeping and the inner stage (dvbt_rx_enable_timing), or null
+static int launch_frames(dvbt_rx *h, hipStream_t s, const FrontParams &fp, int C, bool continuation, bool tps_init, long long sym_off, hipEvent_t ev_inner)
+{
+  const Dims &d = h->d;
+  if (!continuation) {
+    hipLaunchKernelGGL(tps_vote_kernel, dim3((C + 63) / 64), dim3(256), 0, s, (const float2 *)h->tpsval, d.n_tps, (const RxState *)h->st, 0,
+                       (const float2 *)nullptr, h->maj, fp.keep_last);
+    // flags[8] = first superframe-start candidate (min), flags[9] = need_seq for the TPS bookkeeping (set by acq_init_fsm_kernel's reset)
+    hipLaunchKernelGGL(tps_fsm_par_kernel, dim3((C + TPS_THREADS * TPS_SEG - 1) / (TPS_THREADS * TPS_SEG)), dim3(TPS_THREADS), 0, s, fp, (const RxState *)h->st, (const SymInfo *)h->info,
+                       (const int *)h->maj, h->sym_index, h->tps_edges, h->trk_flags + 8, &h->st->tps_bits, (const unsigned short *)h->T.tps_bch,
+                       tps_init ? (const TpsState *)h->tps_state : (const TpsState *)nullptr);
+    hipLaunchKernelGGL(tps_tail_kernel, dim3(1), dim3(256), 0, s, fp, h->st, (const SymInfo *)h->info, (const int *)h->maj, h->tps_state, h->sym_index,
+                       (const TpsEdge *)h->tps_edges, (const int *)(h->trk_flags + 8), h->trk_flags + 9, 0, h->vp, sym_off);
+  } else {
+    // the pilot engine's members live on (FIFO, symbol and frame counters: reference_signals_impl.h); the sync_start tag on the period's first
+    // item clears d_init (the superframe hunt starts over); DBPSK against the last symbol in front of the gap.  Sequential bookkeeping.
+    hipLaunchKernelGGL(tps_vote_kernel, dim3((C + 63) / 64), dim3(256), 0, s, (const float2 *)h->tpsval, d.n_tps, (const RxState *)h->st, 0,
+                       (const float2 *)h->tps_prev, h->maj, fp.keep_last);
+    hipLaunchKernelGGL(tps_tail_kernel, dim3(1), dim3(256), 0, s, fp, h->st, (const SymInfo *)h->info, (const int *)h->maj, h->tps_state, h->sym_index,
+                       (const TpsEdge *)nullptr, (const int *)nullptr, (int *)nullptr, 1, h->vp, sym_off);
+  }
+  if (ev_inner) HIPCHK(hipEventRecord(ev_inner, s));
+  if (h->prm.soft_decision) return DVBT_OK;
+  InnerParams ip = h->T.inner_params(d.payload);
+  // A5 + A6 on the label bytes of the symbols from first_out on (A4 ran inside the symbol kernel)
+  hipLaunchKernelGGL(inner_kernel<6>, dim3(C), dim3(INNER_THREADS), inner_lds_bytes((size_t)d.payload), s, (const float2 *)nullptr, (const uint8_t *)h->labels, ip,
+                     (const RxState *)h->st, 0, (const int *)h->sym_index, (const float2 *)nullptr, (const unsigned char *)nullptr,
+                     (const uint16_t *)h->T.H, (const uint16_t *)h->T.Hinv, (uint8_t *)nullptr, h->symdeint_tap, h->bitdeint, h->bitdeint_lp);
+  return DVBT_OK;
+}
+
 // one lock period of the chain, iq at the OFDM elementary rate
 static int enqueue(dvbt_rx *h, const float2 *iq, size_t nsamples, hipStream_t s, const EnqOpt &o = EnqOpt())
 {
@@ -708,8 +750,7 @@ static int enqueue(dvbt_rx *h, const float2 *iq, size_t nsamples, hipStream_t s,
   FrontParams fp = h->fp;
   const long long cut_sym_off = o.cut_set ? o.sym_off : (long long)h->cut.stream_symbol_offset;
   const int cut_delay = o.cut_set ? o.delay : h->cut.start_delay_symbols;
-  fp.hunt_known = cut_delay > 0 ? 1 : 0;
-  fp.si_start = cut_delay % 68; fp.fi_start = (d.fi_start + cut_delay / 68) % 4;     // dvbt_rx_cut.start_delay_symbols: the hunt fires that many symbols behind the true start
+  cut_hunt(fp, d, cut_delay);
   fp.ncalls = (int)((nsamples - (2 * d.N + d.cp + 16)) / (d.N + d.cp) + 1);
   fp.hist = o.hist; fp.keep_last = o.keep_last ? 1 : 0; fp.avail = o.avail > 0 ? o.avail : (long long)nsamples;
   const int C = fp.ncalls, N = d.N;
@@ -724,7 +765,7 @@ static int enqueue(dvbt_rx *h, const float2 *iq, size_t nsamples, hipStream_t s,
   if (tm) HIPCHK(hipEventRecord(h->ev[ST_ACQ], s));
   if (o.skip_acq) {
     // what acq_init_fsm_kernel's reset would have done on top of the acq_only run's (tracker flags and the symbol ticket are still clear)
-    if (!o.continuation && !o.tps_init) HIPCHK(hipMemsetAsync(h->tps_state, 0, sizeof(TpsState), s));
+    if (!o.continuation && !o.tps_init) HIPCHK(reset_tps_state(h, s));
   } else {
   const AcqState *carry = nullptr;
   int tries = C < o.init_tries ? C : o.init_tries;
@@ -780,27 +821,10 @@ static int enqueue(dvbt_rx *h, const float2 *iq, size_t nsamples, hipStream_t s,
   }
   launch_symbols(h, s, iq, fp, C, drift_off);
   if (tm) HIPCHK(hipEventRecord(h->ev[ST_DEMOD], s));
-  if (!o.continuation) {
-    hipLaunchKernelGGL(tps_vote_kernel, dim3((C + 63) / 64), dim3(256), 0, s, (const float2 *)h->tpsval, d.n_tps, (const RxState *)h->st, 0,
-                       (const float2 *)nullptr, h->maj, fp.keep_last);
-    // flags[8] = first superframe-start candidate (min), flags[9] = need_seq for the TPS bookkeeping (set by acq_init_fsm_kernel's reset)
-    hipLaunchKernelGGL(tps_fsm_par_kernel, dim3((C + TPS_THREADS * TPS_SEG - 1) / (TPS_THREADS * TPS_SEG)), dim3(TPS_THREADS), 0, s, fp, (const RxState *)h->st, (const SymInfo *)h->info,
-                       (const int *)h->maj, h->sym_index, h->tps_edges, h->trk_flags + 8, &h->st->tps_bits, (const unsigned short *)h->T.tps_bch,
-                       o.tps_init ? (const TpsState *)h->tps_state : (const TpsState *)nullptr);
-    hipLaunchKernelGGL(tps_tail_kernel, dim3(1), dim3(256), 0, s, fp, h->st, (const SymInfo *)h->info, (const int *)h->maj, h->tps_state, h->sym_index,
-                       (const TpsEdge *)h->tps_edges, (const int *)(h->trk_flags + 8), h->trk_flags + 9, 0, h->vp, cut_sym_off);
-  } else {
-    // the pilot engine's members live on (FIFO, symbol and frame counters: reference_signals_impl.h); the sync_start tag on the period's first
-    // item clears d_init (the superframe hunt starts over); DBPSK against the last symbol in front of the gap.  Sequential bookkeeping.
-    hipLaunchKernelGGL(tps_vote_kernel, dim3((C + 63) / 64), dim3(256), 0, s, (const float2 *)h->tpsval, d.n_tps, (const RxState *)h->st, 0,
-                       (const float2 *)h->tps_prev, h->maj, fp.keep_last);
-    hipLaunchKernelGGL(tps_tail_kernel, dim3(1), dim3(256), 0, s, fp, h->st, (const SymInfo *)h->info, (const int *)h->maj, h->tps_state, h->sym_index,
-                       (const TpsEdge *)nullptr, (const int *)nullptr, (int *)nullptr, 1, h->vp, cut_sym_off);
-  }
-  if (tm) HIPCHK(hipEventRecord(h->ev[ST_INNER], s));
-  InnerParams ip = h->T.inner_params(d.payload);
   long long max_vit = (long long)C * d.payload * d.m * d.k / (8 * d.n) + 1;
   if (o.vit_off + (size_t)max_vit > h->vit_cap) return fail(DVBT_ERR_CAPACITY, "Viterbi stream buffer too small for the segment's lock periods");
+  { int r = launch_frames(h, s, fp, C, o.continuation, o.tps_init, cut_sym_off, tm ? (hipEvent_t)h->ev[ST_INNER] : nullptr); if (r) return r; }
+  InnerParams ip = h->T.inner_params(d.payload);
   if (h->prm.soft_decision) {
     // soft decisions (k_soft.hpp): LLRs from the equalised carriers and their channel state, A5 + A6 as one gather on the soft values, soft-input decoder
     const float step = 2.0f * d.norm;
@@ -814,10 +838,6 @@ static int enqueue(dvbt_rx *h, const float2 *iq, size_t nsamples, hipStream_t s,
     hipLaunchKernelGGL(viterbi_soft4_kernel, dim3(grid), dim3(64 * S4_WAVES), 0, s, (const int8_t *)h->soft_a, h->vit + o.vit_off, (const RxState *)h->st, h->vp,
                        h->soft_scratch, sp.B, sp.nsteps);
   } else {
-  // A5 + A6 on the label bytes of the symbols from first_out on (A4 ran inside the symbol kernel)
-  hipLaunchKernelGGL(inner_kernel<6>, dim3(C), dim3(INNER_THREADS), inner_lds_bytes((size_t)d.payload), s, (const float2 *)nullptr, (const uint8_t *)h->labels, ip,
-                     (const RxState *)h->st, 0, (const int *)h->sym_index, (const float2 *)nullptr, (const unsigned char *)nullptr,
-                     (const uint16_t *)h->T.H, (const uint16_t *)h->T.Hinv, (uint8_t *)nullptr, h->symdeint_tap, h->bitdeint, h->bitdeint_lp);
   { int r = join_front(); if (r) return r; }
   if (tmv) HIPCHK(hipEventRecord(h->ev[ST_VIT], s));
   VitParams vp = h->vp;
@@ -1804,6 +1824,77 @@ extern "C" int dvbt_debug_symbols(dvbt_rx *h, const void *iq_host, size_t nsampl
   if (fft && h->fft_out) HIPCHK(hipMemcpy(fft, h->fft_out, sizeof(float2) * R * N, hipMemcpyDeviceToHost));
   if (eq && h->eq) HIPCHK(hipMemcpy(eq, h->eq, sizeof(float2) * R * P, hipMemcpyDeviceToHost));
   if (csi && h->csi) HIPCHK(hipMemcpy(csi, h->csi, sizeof(float) * R * P, hipMemcpyDeviceToHost));
+  return DVBT_OK;
+}
+
+// test hook: the frame bookkeeping and the inner stage alone on host-supplied pattern indices, TPS carriers and labels (include/dvbt_hip.h).  The launches are
+// launch_frames, enqueue's own; what the kernels in front leave behind -- the state block's n_symbols, the SymInfo rows, the TPS carriers, the labels, the reset's
+// flag words and pilot-engine state -- is set from the arguments
+static_assert(sizeof(dvbt_tps_state) == sizeof(TpsState) && offsetof(dvbt_tps_state, d_init) == offsetof(TpsState, d_init), "dvbt_tps_state is TpsState");
+extern "C" int dvbt_debug_frames(dvbt_rx *h, int n_symbols, int keep_last, const int32_t *mod_index, const void *tpsval, const void *prev0, const dvbt_tps_state *init,
+                                 const uint8_t *labels, int64_t sym_off, int start_delay_symbols, dvbt_frames_report *rep, int32_t *maj, int32_t *sym_index,
+                                 dvbt_tps_state *final_state, uint8_t *bitdeint, uint8_t *bitdeint_lp, uint8_t *symdeint)
+{
+  if (!mod_index || !tpsval || !labels || !rep || !maj || !sym_index || !final_state || !bitdeint) return fail(DVBT_ERR_INVALID, "null argument");
+  if (n_symbols < 0) return fail(DVBT_ERR_INVALID, "n_symbols must not be negative");
+  if (sym_off < 0 || sym_off % 272 != 0) return fail(DVBT_ERR_INVALID, "sym_off must be a non-negative multiple of 272 (whole superframes)");
+  if (start_delay_symbols < 0 || start_delay_symbols >= 272) return fail(DVBT_ERR_INVALID, "start_delay_symbols must lie in [0, 272)");
+  { int nd = need_device(); if (nd) return nd; }                   // (a handle exists only where a device does)
+  if (!h) return fail(DVBT_ERR_INVALID, "null handle");
+  if (h->pending) return fail(DVBT_ERR_STATE, "dvbt_debug_frames: a segment is in flight (dvbt_rx_segment_finish first)");
+  if (h->prm.soft_decision) return fail(DVBT_ERR_INVALID, "dvbt_debug_frames: a soft-decision handle has no inner_kernel launch (tests/test_gpu_soft_kernels.py has that path)");
+  const Dims &d = h->d;
+  const size_t C = (size_t)h->max_calls, P = (size_t)d.payload, n = (size_t)n_symbols;
+  if (n > C) return fail(DVBT_ERR_INVALID, "n_symbols beyond what the handle's buffers hold (max_samples)");
+  HIPCHK(hipSetDevice(h->prm.device));
+  hipStream_t s = h->own_stream;
+  const bool continuation = prev0 != nullptr;
+  std::vector<SymInfo> ih(C);
+  memset(ih.data(), 0xA5, sizeof(SymInfo) * C);
+  for (size_t i = 0; i < n; i++) ih[i].mod_index = mod_index[i];
+  // every buffer the kernels write, and what lies behind the inputs: 0xA5 up to its capacity
+  HIPCHK(hipMemsetAsync(h->maj, 0xA5, sizeof(int) * C, s)); HIPCHK(hipMemsetAsync(h->sym_index, 0xA5, sizeof(int) * C, s));
+  HIPCHK(hipMemsetAsync(h->tps_edges, 0xA5, sizeof(TpsEdge) * (C / TPS_SEG + 2), s));
+  HIPCHK(hipMemsetAsync(h->bitdeint, 0xA5, C * P + 64, s));
+  if (h->bitdeint_lp) HIPCHK(hipMemsetAsync(h->bitdeint_lp, 0xA5, C * P + 64, s));
+  if (h->symdeint_tap) HIPCHK(hipMemsetAsync(h->symdeint_tap, 0xA5, C * P + 64, s));
+  HIPCHK(hipMemsetAsync(h->labels, 0xA5, C * P + 64, s)); HIPCHK(hipMemsetAsync(h->tpsval, 0xA5, sizeof(float2) * C * d.n_tps, s));
+  HIPCHK(hipMemcpyAsync(h->info, ih.data(), sizeof(SymInfo) * C, hipMemcpyHostToDevice, s));
+  if (n) { HIPCHK(hipMemcpyAsync(h->tpsval, tpsval, sizeof(float2) * n * d.n_tps, hipMemcpyHostToDevice, s)); HIPCHK(hipMemcpyAsync(h->labels, labels, n * P, hipMemcpyHostToDevice, s)); }
+  if (continuation) HIPCHK(hipMemcpyAsync(h->tps_prev, prev0, sizeof(float2) * d.n_tps, hipMemcpyHostToDevice, s));
+  // the reset of acq_init_fsm_kernel: the flag words, and the pilot engine's state unless the period carries it on or is given it
+  int fl[16];
+  for (int i = 0; i < 16; i++) fl[i] = trk_flag_reset(i);
+  HIPCHK(hipMemcpyAsync(h->trk_flags, fl, sizeof fl, hipMemcpyHostToDevice, s));
+  dvbt_tps_state start; if (init) { start = *init; if (!continuation) start.d_init = 0; }   // (a fresh period hunts from the beginning: the stream's preset holds 0 there too)
+  if (init) HIPCHK(hipMemcpyAsync(h->tps_state, &start, sizeof(TpsState), hipMemcpyHostToDevice, s));
+  else if (!continuation) { HIPCHK(hipMemsetAsync(h->tps_state, 0xA5, sizeof(TpsState), s)); HIPCHK(reset_tps_state(h, s)); }
+  RxState plan; memset(&plan, 0, sizeof plan); plan.n_symbols = n_symbols; plan.first_out = -1;
+  *h->st_host = plan;
+  HIPCHK(hipMemcpyAsync(h->st, h->st_host, sizeof(RxState), hipMemcpyHostToDevice, s));
+  HIPCHK(hipStreamSynchronize(s));                                 // (the sources are the caller's memory and locals)
+  FrontParams fp = h->fp;
+  cut_hunt(fp, d, start_delay_symbols);
+  fp.ncalls = (int)C; fp.hist = 0; fp.keep_last = keep_last ? 1 : 0;
+  { int r = launch_frames(h, s, fp, (int)C, continuation, init && !continuation, (long long)sym_off, nullptr); if (r) return r; }
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(h->st_host, h->st, sizeof(RxState), hipMemcpyDeviceToHost, s));
+  HIPCHK(hipMemcpyAsync(fl, h->trk_flags, sizeof fl, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  const RxState f = *h->st_host;
+  memset(rep, 0, sizeof *rep);
+  rep->status = f.status; rep->call0 = f.call0; rep->cp_start0 = f.cp_start0; rep->n_symbols = f.n_symbols; rep->first_out = f.first_out; rep->n_out_symbols = f.n_out_symbols;
+  rep->n_vit_in = f.n_vit_in; rep->n_vit_steps = f.n_vit_steps; rep->n_vit_bytes = f.n_vit_bytes; rep->n_rs_items = f.n_rs_items; rep->n_ts_bytes = f.n_ts_bytes;
+  rep->descr_base = f.descr_base; rep->descr_index = f.descr_index; rep->rs_fail = f.rs_fail; rep->rs_corr = f.rs_corr; rep->rs_list_n = f.rs_list_n;
+  rep->sym_off = f.sym_off; rep->n_rs_words = f.n_rs_words; rep->stream_rs_items = f.stream_rs_items; rep->ts_first_packet = f.ts_first_packet; rep->tps_bits = f.tps_bits;
+  rep->small_viol = f.small_viol; rep->drift_known_off = f.drift_known_off; rep->descr_unclean = f.descr_unclean;
+  rep->first_cand = fl[8]; rep->need_seq = fl[9]; rep->cap_symbols = (int32_t)C; rep->cap_bytes = (int64_t)(C * P + 64);
+  rep->has_lp = h->bitdeint_lp ? 1 : 0; rep->has_tap = h->symdeint_tap ? 1 : 0;
+  HIPCHK(hipMemcpy(maj, h->maj, sizeof(int) * C, hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(sym_index, h->sym_index, sizeof(int) * C, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(final_state, h->tps_state, sizeof(TpsState), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(bitdeint, h->bitdeint, C * P + 64, hipMemcpyDeviceToHost));
+  if (bitdeint_lp && h->bitdeint_lp) HIPCHK(hipMemcpy(bitdeint_lp, h->bitdeint_lp, C * P + 64, hipMemcpyDeviceToHost));
+  if (symdeint && h->symdeint_tap) HIPCHK(hipMemcpy(symdeint, h->symdeint_tap, C * P + 64, hipMemcpyDeviceToHost));
   return DVBT_OK;
 }
 

@@ -425,12 +425,13 @@ __device__ __forceinline__ float wrap_pi(double ph)
 //      maximum of the open peak, so a step costs a few cycles instead of a dependent float chain.
 // reset (segment path, first launch of a lock period): the flag words of the trackers (trk_flags[0..15]; [8], [9] = first superframe-start candidate, need_seq of the
 // TPS bookkeeping), the symbol kernel's ticket and -- for a period that starts the pilot engine afresh -- its state: three memset / copy launches less
+__host__ __device__ inline int trk_flag_reset(int i) { return i == 8 ? 0x7fffffff : 0; }   // what the reset leaves in trk_flags[i]
 struct AcqReset { int *trk_flags; int *ticket; int *tps_state; int tps_state_words; float carry_avg; int has_carry; };   // carry_avg: d_avg carried in from the call that lost the previous lock
 __global__ __launch_bounds__(1024) void acq_init_fsm_kernel(FrontParams p, RxState *st, const float2 *gamma, const float *lambda, const AcqState *as,
                                                           int t_begin, int t_end, AcqReset rz = AcqReset{nullptr, nullptr, nullptr, 0, 0.f, 0})
 {
   if (t_begin == 0) {
-    if (rz.trk_flags && threadIdx.x < 16) rz.trk_flags[threadIdx.x] = threadIdx.x == 8 ? 0x7fffffff : 0;
+    if (rz.trk_flags && threadIdx.x < 16) rz.trk_flags[threadIdx.x] = trk_flag_reset((int)threadIdx.x);
     if (rz.ticket && threadIdx.x == 16) rz.ticket[0] = 0;
     if (rz.tps_state) for (int i = threadIdx.x; i < rz.tps_state_words; i += blockDim.x) rz.tps_state[i] = 0;
   }
@@ -1603,9 +1604,14 @@ inline std::vector<uint16_t> tps_bch_table_host()
 // One symbol of the bookkeeping on registers: the 68-bit FIFO as three 32-bit words (v_alignbit shifts), no branch outside the sync-word match.
 // (The first version walked a TpsState with 64-bit variable shifts and fetched every symbol's two values from LDS inside the dependent chain:
 // ~600 cycles per symbol, 236 symbols per lane = 61 us.)
+// The report carries the word of the period's LAST valid frame (the sequential rule: a broadcast alternates the two halves of its cell id in s40-s47 from frame to
+// frame).  Every lane packs the symbol of its own last valid frame above the word's static bits (s17..s53, 37 bits; the symbol + 1 in the 27 bits above: a handle
+// holds fewer than 2^26 calls) and takes one 64-bit integer maximum on the state block's word, which the reset left at 0; tps_tail_kernel unpacks the winner.
+__device__ __forceinline__ unsigned long long tps_key(int s, unsigned long long word) { return ((unsigned long long)(s + 1) << 37) | ((word & TPS_STATIC_MASK) >> 17); }
+__device__ __forceinline__ unsigned long long tps_unkey(unsigned long long key) { return key ? ((key & ((1ull << 37) - 1)) << 17) | (1ull << 63) : 0ull; }
 struct TpsRegs { unsigned f0, f1, f2; int symbol_index, known, frame_index, prev_mod; };
 __device__ __forceinline__ void tps_advance(TpsRegs &t, int mod, unsigned neg, int fi_start, int si_start, int hunt_known, unsigned mask_even, unsigned mask_odd,
-                                            int &si_out, int &cand, const unsigned short *T, unsigned long long *tps_bits)
+                                            int &si_out, int &cand, const unsigned short *T, int s, unsigned long long *key)
 {
   const int diff = (mod - t.prev_mod) & 3;
   t.prev_mod = mod;
@@ -1624,7 +1630,7 @@ __device__ __forceinline__ void tps_advance(TpsRegs &t, int mod, unsigned neg, i
     if (bch_check_tab(T, lo, t.f2) == 0) {
       t.frame_index = (int)(((lo >> 23) & 1ull) << 1 | ((lo >> 24) & 1ull));
       t.known = 1; t.symbol_index = 67;
-      if (tps_bits) *tps_bits = (lo & TPS_STATIC_MASK) | (1ull << 63);   // every valid frame of a stream stores the same word
+      if (key) *key = tps_key(s, lo);                                    // (the lane's own variable: its last valid frame, symbol s)
     } else t.known = 0;
     t.f0 = 0; t.f1 = 0; t.f2 = 0;
   }
@@ -1687,11 +1693,12 @@ __global__ __launch_bounds__(TPS_THREADS) void tps_fsm_par_kernel(FrontParams p,
     const unsigned w = nxt;
     nxt = word(g + 4);                                             // the next dword is on its way while this one is walked (the array has 8 spare bytes)
 #pragma unroll
-    for (int k = 0; k < 4; k++) tps_advance(t, (int)((w >> (8 * k)) & 3u), (w >> (8 * k + 2)) & 1u, p.fi_start, p.si_start, p.hunt_known, mask_even, mask_odd, si, cand, s_T, nullptr);
+    for (int k = 0; k < 4; k++) tps_advance(t, (int)((w >> (8 * k)) & 3u), (w >> (8 * k + 2)) & 1u, p.fi_start, p.si_start, p.hunt_known, mask_even, mask_odd, si, cand, s_T, 0, nullptr);
   }
   const int seg = s0 / TPS_SEG;
   edges[seg].start = tps_pack(t);
   int first = 0x7fffffff;
+  unsigned long long key = 0;
   for (int g = s0; g < s1; g += 4) {
     const unsigned w = nxt;
     nxt = word(g + 4 < s1 ? g + 4 : g);
@@ -1699,7 +1706,7 @@ __global__ __launch_bounds__(TPS_THREADS) void tps_fsm_par_kernel(FrontParams p,
     for (int k = 0; k < 4; k++) {
       const int s = g + k;
       if (s < s1) {
-        tps_advance(t, (int)((w >> (8 * k)) & 3u), (w >> (8 * k + 2)) & 1u, p.fi_start, p.si_start, p.hunt_known, mask_even, mask_odd, si, cand, s_T, tps_bits);
+        tps_advance(t, (int)((w >> (8 * k)) & 3u), (w >> (8 * k + 2)) & 1u, p.fi_start, p.si_start, p.hunt_known, mask_even, mask_odd, si, cand, s_T, s, &key);
         sym_index[s] = si;
         if (cand && first == 0x7fffffff) first = s;
       }
@@ -1707,6 +1714,7 @@ __global__ __launch_bounds__(TPS_THREADS) void tps_fsm_par_kernel(FrontParams p,
   }
   edges[seg].end = tps_pack(t);
   if (first != 0x7fffffff) atomicMin(first_cand, first);
+  if (key) atomicMax(tps_bits, key);
 }
 
 // (all 256 threads of the workgroup; returns whether the sequential bookkeeping has to run -- the same value in every thread)
@@ -1726,6 +1734,7 @@ __device__ __forceinline__ int tps_finalize_body(RxState *st, const TpsEdge *edg
   __syncthreads();
   if (tid == 0) {
     *need_seq = s_bad;
+    st->tps_bits = s_bad ? 0ull : tps_unkey(st->tps_bits);         // (the sequential bookkeeping stores the words of the frames it finds valid itself)
     if (!s_bad) {
       int fo = *first_cand;
       if (fo == 0x7fffffff) { st->first_out = -1; st->status |= 4; st->n_out_symbols = 0; }

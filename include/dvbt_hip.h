@@ -878,6 +878,36 @@ int dvbt_debug_symbols(dvbt_rx *h, const void *iq_host, size_t nsamples, int nsy
                        const int32_t *sw, const float *ph_base, const double *incA, const double *incB, int grid, const float *delta_host, int nread,
                        uint8_t *labels, int32_t *freq_offset, int32_t *mod_index, void *tpsval, void *acq, void *fft, void *eq, float *csi);
 
+/* the launches between the symbol kernels and the Viterbi decoder alone (DBPSK vote, TPS / frame bookkeeping in its segment-parallel form with the sequential
+ * fallback, the sizes of every later stage, symbol and bit de-interleaver: tps_vote_kernel, tps_fsm_par_kernel, tps_tail_kernel, inner_kernel) through the segment
+ * path's own launch routine (launch_frames of csrc/dvbt_hip.hip, which enqueue calls), on the handle's tables and buffers; launched for as many calls as the handle
+ * holds, as a segment launches more than it acquires.  From the host: n_symbols (the state block's) and keep_last as in a segment; mod_index int32[n] the scattered
+ * pilots' pattern per symbol (the other fields of the per-symbol record are 0xA5); tpsval cfloat[n][n_tps] the equalised TPS carriers; prev0 NULL, or cfloat[n_tps]
+ * the TPS carriers in front of symbol 0 -- then the period is a continuation: sequential bookkeeping, the members carried on, the superframe hunt restarted; init
+ * NULL, or the pilot engine's members in front of symbol 0 (a fresh period starts from them, d_init taken as 0, as a piece of a stream with known counters does; a continuation
+ * carries on from them, and with NULL from what the handle's last period left); labels uint8[n][payload]; sym_off (a multiple of 272) and start_delay_symbols as in
+ * dvbt_rx_cut.  Before the launches the flag words and, for a fresh period without init, the pilot engine's state are what the acquisition's reset leaves; the vote,
+ * the symbol indices, the parallel pass's edge records, both de-interleaver outputs and the symbol de-interleaver's tap, and what lies behind the n rows of the inputs,
+ * are 0xA5 up to capacity.  Outputs: the report (the state block behind the launches, the two flag words, the capacities); maj and sym_index int32[cap_symbols];
+ * final_state; bitdeint, bitdeint_lp, symdeint uint8[cap_bytes] (cap_bytes = cap_symbols * payload + 64; the last two may be NULL, and stay as they were where the
+ * handle has no such buffer: has_lp, has_tap).  The caller sizes the arrays from the handle's max_samples: cap_symbols = (max_samples - (2 N + cp + 16)) / (N + cp) + 1.
+ * DVBT_ERR_INVALID, nothing written, allocated or launched, for: a null required pointer, a negative n_symbols, a sym_off that is negative or no multiple of 272, a
+ * start_delay_symbols outside [0, 272), and -- behind DVBT_ERR_NO_DEVICE without a GPU -- a null or soft-decision handle and n_symbols beyond the handle's calls.
+ * tests/test_gpu_frames.py */
+typedef struct { uint64_t fifo_lo; uint32_t fifo_hi; int32_t symbol_index, symbol_index_known, frame_index, prev_mod, d_init; } dvbt_tps_state;   /* bit i of the FIFO = s_i */
+typedef struct {
+  int32_t status, call0, cp_start0, n_symbols, first_out, n_out_symbols;
+  int32_t descr_base, descr_index, rs_fail, rs_corr, rs_list_n, small_viol, drift_known_off, descr_unclean;
+  int64_t n_vit_in, n_vit_steps, n_vit_bytes, n_rs_items, n_ts_bytes, sym_off, n_rs_words, stream_rs_items, ts_first_packet;
+  uint64_t tps_bits;                   /* bit 63: a valid frame was seen; bits 17..53 its static fields */
+  int32_t first_cand, need_seq;        /* the flag words: the parallel pass's earliest start candidate (0x7fffffff: none), 1 = the sequential bookkeeping ran */
+  int32_t cap_symbols, has_lp, has_tap, reserved;
+  int64_t cap_bytes;
+} dvbt_frames_report;
+int dvbt_debug_frames(dvbt_rx *h, int n_symbols, int keep_last, const int32_t *mod_index, const void *tpsval, const void *prev0, const dvbt_tps_state *init,
+                      const uint8_t *labels, int64_t sym_off, int start_delay_symbols, dvbt_frames_report *report, int32_t *maj, int32_t *sym_index,
+                      dvbt_tps_state *final_state, uint8_t *bitdeint, uint8_t *bitdeint_lp, uint8_t *symdeint);
+
 /* the channel-error kernel alone (csrc/k_quality.hpp) on host bytes: in_host = n_in decoder input bytes (m bits each), vit_host = n_vit decoded bytes; counts as
  * dvbt_rx_quality's channel_bits / channel_bit_errors (n_vit < 2: both 0).  Sizes outside [0, 2^30] are refused before the device is asked for. */
 int dvbt_debug_quality_channel(int constellation, int code_rate, const uint8_t *in_host, int64_t n_in, const uint8_t *vit_host, int64_t n_vit, int64_t *bits, int64_t *errors);

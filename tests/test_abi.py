@@ -98,6 +98,17 @@ def test_no_cpu_fallback(g):
         bad[i] = v
         assert L.dvbt_debug_symbols(*bad) == -1, (i, v)
     assert L.dvbt_debug_symbols(*ok) == -2
+    # dvbt_debug_frames: null pointers, a negative n_symbols, a sym_off that is negative or no multiple of 272, a start_delay_symbols outside [0, 272) before it asks
+    # for the device; the refusals that need the handle (null, soft decisions, n_symbols beyond its calls) are in tests/test_gpu_frames.py
+    L.dvbt_debug_frames.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 5 + [C.c_int64, C.c_int] + [C.c_void_p] * 7
+    i32, tps, lab, frep, st = (C.c_int32 * 8)(), (C.c_float * (2 * 8 * 68))(), (C.c_ubyte * (8 * 6048))(), (C.c_int64 * 32)(), (C.c_int64 * 4)()
+    ok = [None, 8, 1, i32, tps, None, None, lab, 0, 0, frep, i32, i32, st, lab, None, None]
+    for i, v in ((3, None), (4, None), (7, None), (10, None), (11, None), (12, None), (13, None), (14, None), (1, -1), (8, 1), (8, 271), (8, -272), (9, -1), (9, 272)):
+        bad = list(ok)
+        bad[i] = v
+        assert L.dvbt_debug_frames(*bad) == -1, (i, v)
+    assert L.dvbt_debug_frames(*ok) == -2
+    assert all(x == 0 for x in frep) and all(x == 0 for x in st)
 
 
 def test_product_does_not_import_oracle():
