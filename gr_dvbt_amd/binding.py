@@ -506,6 +506,85 @@ class Tx:
             pass
 
 
+CHANNEL_MAX_PATHS, CHANNEL_MAX_DELAY = 8, 8192
+
+
+class ChannelParams(C.Structure):
+    _fields_ = [("n_paths", C.c_int), ("delay", C.c_int * 8), ("amp_re", C.c_float * 8), ("amp_im", C.c_float * 8), ("cfo", C.c_double),
+                ("fft_length", C.c_int), ("noise_sigma", C.c_float), ("seed", C.c_uint64), ("first_sample", C.c_int64), ("device", C.c_int)]
+
+
+def _channel_lib():
+    L = lib()
+    if not getattr(L, "_channel_typed", False):
+        L.dvbt_channel_create.argtypes = [C.POINTER(ChannelParams), C.POINTER(C.c_void_p)]
+        L.dvbt_channel_run.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+        L.dvbt_channel_run_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+        L.dvbt_channel_power.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(C.c_double)]
+        L.dvbt_channel_reset.argtypes = [C.c_void_p]
+        L.dvbt_channel_destroy.argtypes = [C.c_void_p]
+        L._channel_typed = True
+    return L
+
+
+class Channel:
+    """dvbt_channel_*: static echoes, a carrier offset and seeded AWGN on complex64 baseband, on the GPU.  echoes: ((delay in samples, complex amplitude), ...)
+    of the extra paths; cfo in subcarrier spacings of an fft_length-point symbol; noise_sigma per component (Channel.sigma for an SNR).  One stream, delivered
+    over any number of run() / run_device() calls of any size; the concatenated outputs are bit for bit those of one call.  The noise of a sample depends on
+    (seed, first_sample + its index) alone."""
+
+    def __init__(self, echoes=(), cfo=0.0, fft_length=0, noise_sigma=0.0, seed=0, first_sample=0, device=0):
+        self.L = _channel_lib()
+        echoes = tuple(echoes)
+        if len(echoes) > CHANNEL_MAX_PATHS:
+            raise ValueError(f"at most {CHANNEL_MAX_PATHS} echoes")
+        p = ChannelParams()
+        p.n_paths = len(echoes)
+        for i, (d, a) in enumerate(echoes):
+            p.delay[i], p.amp_re[i], p.amp_im[i] = int(d), float(np.real(a)), float(np.imag(a))
+        p.cfo, p.fft_length, p.noise_sigma = float(cfo), int(fft_length), float(noise_sigma)
+        p.seed, p.first_sample, p.device = int(seed) & 0xffffffffffffffff, int(first_sample), int(device)
+        self.p = p
+        self.h = C.c_void_p()
+        _chk(self.L.dvbt_channel_create(C.byref(p), C.byref(self.h)))
+
+    @staticmethod
+    def sigma(snr_db, ref_power):
+        """the noise's standard deviation per component for an SNR of snr_db relative to ref_power (power())"""
+        return float(np.sqrt(ref_power / 10.0 ** (snr_db / 10.0) / 2.0))
+
+    def run(self, iq):
+        """complex64 samples in, as many out; continues the stream"""
+        iq = np.ascontiguousarray(iq, dtype=np.complex64).reshape(-1)
+        out = np.empty_like(iq)
+        _chk(self.L.dvbt_channel_run(self.h, iq.ctypes.data_as(C.c_void_p), len(iq), out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def run_device(self, in_ptr, nsamples, out_ptr, stream=None):
+        """device pointers (ints) to nsamples complex64 each, not overlapping: enqueues on `stream` (a hipStream_t as int, None: the default stream)"""
+        _chk(self.L.dvbt_channel_run_device(self.h, C.c_void_p(in_ptr), nsamples, C.c_void_p(out_ptr), C.c_void_p(stream) if stream else None))
+
+    def power(self, ptr, nsamples, stream=None):
+        """mean |x|^2 of nsamples complex64 at the device pointer `ptr`: the ref_power of sigma().  Synchronises `stream`."""
+        v = C.c_double()
+        _chk(self.L.dvbt_channel_power(self.h, C.c_void_p(ptr), nsamples, C.c_void_p(stream) if stream else None, C.byref(v)))
+        return v.value
+
+    def reset(self):
+        _chk(self.L.dvbt_channel_reset(self.h))
+
+    def close(self):
+        if self.h:
+            self.L.dvbt_channel_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 # ------------------------------------------------------------------ per-block C ABI (one triple per reference block)
 TAG_SYNC_START, TAG_SUPERFRAME_START, TAG_SYMBOL_INDEX = 1, 2, 3
 

@@ -26,6 +26,7 @@
 #include "k_quality.hpp"
 #include "k_tx.hpp"
 #include "k_txblocks.hpp"
+#include "k_channel.hpp"
 
 using namespace dvbt;
 using hip_own::DevMem; using hip_own::PinMem; using hip_own::Stream; using hip_own::Event;
@@ -1904,3 +1905,4 @@ extern "C" int dvbt_debug_frames(dvbt_rx *h, int n_symbols, int keep_last, const
 #include "dvbt_blocks.inc"
 #include "dvbt_tx.inc"
 #include "dvbt_txblocks.inc"
+#include "dvbt_channel.inc"

@@ -917,6 +917,40 @@ int dvbt_debug_quality_post(const uint8_t *vit_host, int64_t n_vit, const uint8_
  * mer, sum, channel, rs; bytes_read[4] what each reads.  tools/quality_bench.py */
 int dvbt_debug_quality_time(dvbt_rx *h, int warmup, int iters, float *ms, int64_t *bytes_read);
 
+/* ------------------------------------------------------------------ the channel: echoes, carrier offset, seeded AWGN
+ * What stands between a modulator and a receiver in a loopback (the noise source and adder of apps/dvbt_rx_demo*.grc, plus static multipath and a carrier
+ * offset), on complex64 baseband, in one kernel and one pass over the samples (csrc/k_channel.hpp).  For the stream's absolute sample index n:
+ *   e[n] = x[n] + sum_i a_i x[n - d_i]                  x[k] = 0 in front of the stream's first sample; the direct path is implicit
+ *   r[n] = e[n] exp(2 pi j phi(n))                      phi(n) = (inc n mod 2^64) / 2^64, inc = round(cfo / fft_length 2^64) mod 2^64: cfo in subcarrier spacings
+ *   y[n] = r[n] + noise_sigma (g_re(n) + j g_im(n))     noise_sigma: standard deviation per component, sqrt(ref_power / 10^(snr_db / 10) / 2) for an SNR
+ * The noise of sample n is a function of (seed, n) alone: Philox4x32-10 with key (seed low 32, seed high 32) and counter (n >> 1, 0, 0) split into low and high
+ * words; sample n takes output words (0, 1) for even n, (2, 3) for odd n as (w_a, w_b); u1 = ((w_a >> 9) + 0.5) 2^-23, u2 = (w_b >> 8) 2^-24, rho =
+ * sqrt(-2 ln u1), g = rho (cos, sin)(2 pi u2).  u1 >= 2^-24, so the Gaussian's tails end at 5.77 sigma.  The phase is an integer product -- exact, wrapping by
+ * itself, as good at n = 2^40 as at 0 -- and the phasor is taken from its top 32 bits.  The handle keeps the last DVBT_CHANNEL_MAX_DELAY input samples on the
+ * device, so calls of any size (0 and 1 included) continue the stream, and a stream cut into calls gives bit for bit what one call gives.  With no paths, cfo == 0
+ * and noise_sigma == 0 the output is the input bit for bit.
+ * Buffers: n <= 2^31 complex64 each per call, 8-byte aligned; input and output ranges that overlap are DVBT_ERR_INVALID (the echoes read behind the sample being written).  A
+ * failed call leaves the stream position and the history as they were.  dvbt_channel_run_device only enqueues on `stream`; calls on different streams are ordered
+ * by the handle (an event).  One thread per handle.  Every parameter is checked before the device is asked for: a bad struct is DVBT_ERR_INVALID everywhere, a
+ * good one DVBT_ERR_NO_DEVICE without a GPU -- there is no CPU path. */
+enum { DVBT_CHANNEL_MAX_PATHS = 8, DVBT_CHANNEL_MAX_DELAY = 8192 };
+typedef struct {
+  int n_paths; int delay[8]; float amp_re[8], amp_im[8];
+  double cfo; int fft_length;          /* fft_length > 0 whenever cfo != 0 */
+  float noise_sigma; uint64_t seed;    /* noise_sigma >= 0, finite */
+  int64_t first_sample;                /* >= 0: absolute index of the stream's first sample (a piece of a cut stream) */
+  int device;
+} dvbt_channel_params;
+typedef struct dvbt_channel dvbt_channel;
+int  dvbt_channel_create(const dvbt_channel_params *p, dvbt_channel **out);
+int  dvbt_channel_run(dvbt_channel *h, const void *iq_host, size_t n, void *out_host);
+int  dvbt_channel_run_device(dvbt_channel *h, const void *iq_device, size_t n, void *out_device, void *stream);
+/* mean of |x|^2 over n > 0 samples of a device buffer (the ref_power of noise_sigma): partial sums in double, added in a fixed order without atomics -- two calls
+ * on the same data return the same bits.  Ordered on `stream`; synchronises. */
+int  dvbt_channel_power(dvbt_channel *h, const void *iq_device, size_t n, void *stream, double *mean_power);   /* synchronises */
+int  dvbt_channel_reset(dvbt_channel *h);   /* back to first_sample, history cleared */
+void dvbt_channel_destroy(dvbt_channel *h);
+
 #ifdef __cplusplus
 }
 #endif
