@@ -290,6 +290,18 @@ class Rx:
         _chk(self.L.dvbt_rx_viterbi_proof_total(self.h, C.byref(p)))
         return {"chunks": int(p.chunks), "decoded_again": int(p.decoded_again), "sequential": int(p.sequential), "not_proven": int(p.not_proven)}
 
+    def set_viterbi_walk(self, always):
+        """always: the Viterbi decoder's traceback chains walk every hop instead of taking the shortcut over chained best states (the same bytes)"""
+        self.L.dvbt_rx_set_viterbi_walk.argtypes = [C.c_void_p, C.c_int]
+        _chk(self.L.dvbt_rx_set_viterbi_walk(self.h, int(bool(always))))
+
+    def viterbi_shortcut(self):
+        """(shortcut, walked): blocks of 24 windows, per wavefront, whose bytes left by the traceback's shortcut / whose chains walked, since the handle was created"""
+        out = (C.c_longlong * 2)()
+        self.L.dvbt_rx_viterbi_shortcut.argtypes = [C.c_void_p, C.POINTER(C.c_longlong)]
+        _chk(self.L.dvbt_rx_viterbi_shortcut(self.h, out))
+        return int(out[0]), int(out[1])
+
     def viterbi_check(self):
         """viterbi_verify >= 1: (chunks of the last launch of the Viterbi decoder, chunks NOT proven equal to the streaming decoder when the launch ends)"""
         a, b = C.c_int64(), C.c_int64()
@@ -673,6 +685,18 @@ class Block:
         self.L.dvbt_viterbi_decoder_proof.argtypes = [C.c_void_p, C.POINTER(ViterbiProof)]
         _chk(self.L.dvbt_viterbi_decoder_proof(self.h, C.byref(p)))
         return {"chunks": int(p.chunks), "decoded_again": int(p.decoded_again), "sequential": int(p.sequential), "not_proven": int(p.not_proven)}
+
+    def set_viterbi_walk(self, always):
+        """viterbi_decoder only: the traceback chains of the following calls walk every hop instead of taking the shortcut over chained best states"""
+        self.L.dvbt_viterbi_decoder_set_walk.argtypes = [C.c_void_p, C.c_int]
+        _chk(self.L.dvbt_viterbi_decoder_set_walk(self.h, int(bool(always))))
+
+    def viterbi_shortcut(self):
+        """viterbi_decoder only: (shortcut, walked) blocks of 24 windows, per wavefront, since the block was created"""
+        out = (C.c_longlong * 2)()
+        self.L.dvbt_viterbi_decoder_shortcut.argtypes = [C.c_void_p, C.POINTER(C.c_longlong)]
+        _chk(self.L.dvbt_viterbi_decoder_shortcut(self.h, out))
+        return int(out[0]), int(out[1])
 
     def close(self):
         if self.h:

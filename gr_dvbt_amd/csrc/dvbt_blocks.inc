@@ -328,6 +328,7 @@ struct dvbt_viterbi_decoder {
   dvbt_viterbi_decoder_params p; BlockCtx c; Dims d; VitParams vp;
   size_t hist = 0; long long in_total = 0, steps = 0; int d_init = 0;      // hist: bytes of consumed input kept at the front of din
   static constexpr size_t kTail = 8192;
+  bool walk = false;                                                       // dvbt_viterbi_decoder_set_walk
   VitProof proof; DevMem<int> carry; int cur = 0; bool have_carry = false; long long grid0 = 0;   // carry: 2 x 32 words (ping-pong), [cur] = the state at byte grid0
 };
 extern "C" int dvbt_viterbi_decoder_create(const dvbt_viterbi_decoder_params *p, dvbt_viterbi_decoder **out)
@@ -373,13 +374,13 @@ static int viterbi_call(dvbt_viterbi_decoder *h, int nout, int nin, const void *
     if (!dev) { WCHK(h->c.dout.reserve((size_t)produced)); o = (uint8_t *)h->c.dout.p; }
     const int B = h->vp.chunk_bytes;
     const long long g0 = h->have_carry ? h->grid0 : 0, chunks = (out_hi - g0 + B - 1) / B;
-    if (chunks + 2 > h->proof.cap) { HIPCHK(hipStreamSynchronize(s)); int acc[3]; HIPCHK(hipMemcpy(acc, h->proof.ctl + V3_CTL_ACC, sizeof acc, hipMemcpyDeviceToHost));
+    if (chunks + 2 > h->proof.cap) { HIPCHK(hipStreamSynchronize(s)); int acc[8]; HIPCHK(hipMemcpy(acc, h->proof.ctl + V3_CTL_ACC, sizeof acc, hipMemcpyDeviceToHost));      // (the sums and the shortcut's counters: words 8..15)
                                      WCHK(h->proof.reserve(2 * chunks + 2)); HIPCHK(hipMemcpy(h->proof.ctl + V3_CTL_ACC, acc, sizeof acc, hipMemcpyHostToDevice)); }
     V3Aux ax = h->proof.aux();
     ax.grid0 = g0; ax.carry_in = h->have_carry ? h->carry + h->cur * V3_SLOT : nullptr;
     const long long b0_last = g0 + (chunks - 1) * B;
     ax.carry_rel = (int)((out_hi - b0_last) / V3_BLK) * V3_BLK; ax.carry_out = h->carry + (h->cur ^ 1) * V3_SLOT;
-    launch_viterbi(s, (const uint8_t *)h->c.din.p, o, (const RxState *)nullptr, h->steps, h->vp, in_base, out_lo, produced, &ax, VIT_REPAIR);
+    launch_viterbi(s, (const uint8_t *)h->c.din.p, o, (const RxState *)nullptr, h->steps, h->vp, in_base, out_lo, produced, &ax, VIT_REPAIR, h->walk);
     h->cur ^= 1; h->have_carry = true; h->grid0 = b0_last + ax.carry_rel;
     if (!dev) WCHK(h->c.get(out, h->c.dout.p, (size_t)produced));
   }
@@ -426,6 +427,19 @@ extern "C" int dvbt_viterbi_decoder_proof(dvbt_viterbi_decoder *h, dvbt_viterbi_
   int acc[3] = {0, 0, 0};
   HIPCHK(hipMemcpy(acc, h->proof.ctl + V3_CTL_ACC, sizeof acc, hipMemcpyDeviceToHost));      // (blocking: behind everything the block's stream holds)
   out->chunks = acc[0]; out->decoded_again = acc[1]; out->sequential = acc[2]; out->not_proven = -1;
+  return DVBT_OK;
+}
+// the traceback's shortcut (k_viterbi3.hpp): always != 0 = every chain of the following calls walks all its hops; the counters of shortcut / walked iterations since the block was created
+extern "C" int dvbt_viterbi_decoder_set_walk(dvbt_viterbi_decoder *h, int always)
+{
+  if (!h) return fail(DVBT_ERR_INVALID, "null handle");
+  h->walk = always != 0;
+  return DVBT_OK;
+}
+extern "C" int dvbt_viterbi_decoder_shortcut(dvbt_viterbi_decoder *h, long long out[2])
+{
+  if (!h || !out) return fail(DVBT_ERR_INVALID, "null argument");
+  HIPCHK(hipMemcpy(out, h->proof.ctl + V3_CTL_SHORT, 2 * sizeof(long long), hipMemcpyDeviceToHost));      // (blocking: behind everything the block's stream holds)
   return DVBT_OK;
 }
 extern "C" void dvbt_viterbi_decoder_destroy(dvbt_viterbi_decoder *h) { delete h; }

@@ -217,7 +217,7 @@ constexpr unsigned V3_REPAIR_GRID = 64;   // workgroups of the parallel repair p
 // ax == null or mode == VIT_PLAIN: the chunk decoders alone.  Otherwise the launch that is the streaming decoder by construction: the decoders leave their states, the checker
 // lists the chunks that are not proven, the repair passes decode those again (k_viterbi3.hpp); nothing is read back.
 static void launch_viterbi(hipStream_t s, const uint8_t *in, uint8_t *out, const RxState *st, long long steps_fixed, const VitParams &vp,
-                           long long in_base, long long out_lo, long long max_out_bytes, const V3Aux *ax = nullptr, int mode = VIT_PLAIN)
+                           long long in_base, long long out_lo, long long max_out_bytes, const V3Aux *ax = nullptr, int mode = VIT_PLAIN, bool walk = false)
 {
   const bool proof = ax && mode != VIT_PLAIN;
   const long long grid0 = proof ? ax->grid0 : out_lo;
@@ -225,9 +225,11 @@ static void launch_viterbi(hipStream_t s, const uint8_t *in, uint8_t *out, const
   if (chunks < 1) chunks = 1;
   const dim3 grid((unsigned)((chunks + 4 * V3_WGW - 1) / (4 * V3_WGW))), blk(64 * V3_WGW);
   V3Aux none; memset(&none, 0, sizeof none);
+  if (walk) none.debug |= V3_DEBUG_WALK;                       // (dvbt_rx_set_viterbi_walk: every chain walks its hops)
   if (proof) {
     V3Aux a = *ax;
-    if (mode == VIT_FORCE_CONFLICT) { a.debug = 1; mode = VIT_REPAIR_COUNT; }
+    if (walk) a.debug |= V3_DEBUG_WALK;
+    if (mode == VIT_FORCE_CONFLICT) { a.debug |= 1; mode = VIT_REPAIR_COUNT; }
     const dim3 cgrid((unsigned)((chunks + 255) / 256));
     if (vp.warm == V3_WARM) {
 #define V3_CALL(N) hipLaunchKernelGGL((viterbi3_kernel<N, V3_WARM, 1>), grid, blk, 0, s, in, out, st, steps_fixed, vp, a, in_base, out_lo)
@@ -373,6 +375,7 @@ struct dvbt_rx {
   DevMem<float2> q_sym; DevMem<double> q_mer; DevMem<unsigned long long> q_cnt;   // dvbt_rx_quality (dvbt_quality.inc): MER sums per symbol, their total, the bit counters
   unsigned long long seg_serial = 0, q_eq_serial = 0;   // finished segments so far / their count when dvbt_rx_enable_quality allocated eq (it holds carriers only of a later one)
   DevMem<uint8_t> bd_log; std::vector<dvbt_period_tap> plog; size_t plog_bytes = 0;   // dvbt_rx_enable_taps(h, 2): every lock period's decoder input
+  bool vit_walk = false;                       // dvbt_rx_set_viterbi_walk: the decoder's traceback chains walk every hop (no shortcut over chained best states)
   VitProof vproof; bool vit_checked = false;   // the Viterbi stage's proof + repair passes (dvbt_rx_params.viterbi_verify): the chunk decoders' states, the passes' counters
   size_t vit_cap = 0; DevMem<RsDefer> rs_defer; int rs_defer_cap = 0;
   DevMem<unsigned long long> rs_sync;        // bit w: payload byte 0 of RS word w is 0xB8 (deint_rs_kernel / rs_fix_kernel -> descramble_scan_kernel)
@@ -855,7 +858,7 @@ static int enqueue(dvbt_rx *h, const float2 *iq, size_t nsamples, hipStream_t s,
   // hierarchical modes: the decoder reads the bit de-interleaver's output 0 (HP: what the flowgraphs connect), or its output 1 on request; it unpacks d_m
   // bits of every byte either way (viterbi_decoder_impl.cc:93,236-243: the reference's decoder knows no priority streams)
   launch_viterbi(s, (const uint8_t *)((h->prm.hier_stream && h->bitdeint_lp) ? h->bitdeint_lp : h->bitdeint), h->vit + o.vit_off, (const RxState *)h->st, 0ll, vp, 0ll, 0ll, max_vit,
-                 proof ? &ax : nullptr, h->prm.viterbi_verify);
+                 proof ? &ax : nullptr, h->prm.viterbi_verify, h->vit_walk);
   }
   if (tmv) HIPCHK(hipEventRecord(h->ev[ST_RS], s));
   if (o.tail) { int r = enqueue_tail(h, s, max_vit / 204 + 1, -1); if (r) return r; }
@@ -1515,6 +1518,25 @@ extern "C" int dvbt_rx_viterbi_proof_total(dvbt_rx *h, dvbt_viterbi_proof *out)
   int acc[3] = {0, 0, 0};
   HIPCHK(hipMemcpy(acc, h->vproof.ctl + V3_CTL_ACC, sizeof acc, hipMemcpyDeviceToHost));
   out->chunks = acc[0]; out->decoded_again = acc[1]; out->sequential = acc[2]; out->not_proven = -1;
+  return DVBT_OK;
+}
+// The traceback's shortcut (k_viterbi3.hpp): always != 0 makes every chain of the launches enqueued afterwards walk all its hops -- the same bytes, for tests and measurements
+extern "C" int dvbt_rx_set_viterbi_walk(dvbt_rx *h, int always)
+{
+  if (!h) return fail(DVBT_ERR_INVALID, "null handle");
+  if (h->pending) return fail(DVBT_ERR_STATE, "dvbt_rx_set_viterbi_walk: a segment is in flight (dvbt_rx_segment_finish first)");
+  h->vit_walk = always != 0;
+  drop_graphs(h);
+  return DVBT_OK;
+}
+// out[0], out[1]: iterations (blocks of 24 windows, per wavefront) of the proving decoders whose bytes left by the shortcut / whose chains walked, since the handle was created
+extern "C" int dvbt_rx_viterbi_shortcut(dvbt_rx *h, long long out[2])
+{
+  if (!h || !out) return fail(DVBT_ERR_INVALID, "null argument");
+  if (!h->vproof.ctl) return fail(DVBT_ERR_STATE, "dvbt_rx_viterbi_shortcut: the handle runs the plain chunk decoders (viterbi_verify = -1, or soft decisions)");
+  if (h->pending) return fail(DVBT_ERR_STATE, "dvbt_rx_viterbi_shortcut: a segment is in flight (dvbt_rx_segment_finish first)");
+  HIPCHK(hipSetDevice(h->prm.device));
+  HIPCHK(hipMemcpy(out, h->vproof.ctl + V3_CTL_SHORT, 2 * sizeof(long long), hipMemcpyDeviceToHost));
   return DVBT_OK;
 }
 // (chunks, chunks that are not proven when the launch ends) -- needs the final check, viterbi_verify >= 1

@@ -49,6 +49,19 @@
 // path bytes are read together in the hop slot behind the last hop and the calls' bytes leave where that hop would be merged, under an exec mask without a branch
 // (v3_trace_read / v3_trace_store): as compiled, two s_waitcnt lgkmcnt(0) between the loop header and the first window (the compacted bits, the first window's step words; the batch of look-ups
 // is met by three partial waits, one per wide store) instead of fifteen, and none on the spot behind the last hop instead of two (tests/test_viterbi_isa_staging.py).
+//
+// The traceback's shortcut (round 9).  On a stream the code copes with all chains walk the same path: the chain started at window jj passes window jj - 1 at the state that window's
+// own chain starts from (its best state), and its ntraceback - 1 hops re-derive what bests[] already holds.  With Z(w) = the storage index of window w's best state (trace_init's
+// T.z, low six bits) and link(w) = ((tab[row(w)][Z(w)] & 63) == Z(w - 1)) -- one hop from w's best state lands on w - 1's -- a chain whose links hold for every w in
+// [jj - (ntraceback - 2), jj] stands at Z(jj - (ntraceback - 1)) behind its hops, and the call's byte is what v3_trace_store makes of that window's path byte at its own best state:
+// the very byte the walk reaches, so no decoded byte can change (tests/test_viterbi_shortcut_model.py).  The decision is taken once per iteration of the block loop, wave-uniform,
+// in front of the windows: every link of the block whose chains start (24 windows x the wavefront's live decoders, one ballot) and every link of the block before it (the previous
+// iteration's verdict) -- more than any chain needs, and enough for every ntraceback.  Z(jj - 1) is the neighbouring lane's Z(jj) (one DPP row shift); the first hop's reads ride
+// on staging's waits (link_reads: behind the compacted bits' reads, met by the waits of the table look-ups; LDS returns in order); where the shortcut is taken the path bytes at the
+// best states of the windows the chains end in are read and the calls' bytes leave under the chains' exec masks before the first window, and the iteration runs the hop-free
+// windows.  Where a link fails the chains walk as before; where no chain of the wavefront ends in a call (warm-up, idle tails) nothing is walked at all.  The hop block it replaces is 12 x (96.3 - 88.0) = 100 instructions and
+// 46 + 2 dependent LDS round trips.
+// V3Aux.debug bit 1 (dvbt_rx_set_viterbi_walk) switches the shortcut off; the MODE 1 decoders count both kinds of iteration (ctl[V3_CTL_SHORT]).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -405,6 +418,8 @@ constexpr int V3_CTL_CONFLICT = 2;   //            chunks left to the sequential
 constexpr int V3_CTL_UNPROVEN = 3;   //            chunks that are not proven after the repair (the final check; -1: not run)
 constexpr int V3_CTL_SEQ = 4;        //            chunks the sequential pass decoded
 constexpr int V3_CTL_ACC = 8;        //            [8..10] chunks, mismatches, sequential decodes summed over the launches since the owner cleared them
+constexpr int V3_CTL_SHORT = 12;     //            [12..15] two 64-bit counters, never cleared by a kernel: iterations (blocks of windows, per wavefront) of the MODE 1 decoders whose
+                                     //            calls' bytes left by the shortcut, and iterations whose chains walked
 constexpr int V3_CTL_HDR = 16;       // ... then the list of mismatching chunks (cap words), then the conflict flags (cap words)
 struct V3Aux {
   int *snap;                         // 3 slots per chunk (own, pred, fix), cap + 2 chunks
@@ -414,8 +429,10 @@ struct V3Aux {
   const int *carry_in;               // the streaming decoder's state at grid0 (null: chunk 0 warms up like the others -- it starts the stream)
   int *carry_out; int carry_rel;     // the last chunk's decoder leaves its state carry_rel windows into its chunk (a multiple of V3_BLK; carry_out null: no)
   int debug;                         // test hook (dvbt_rx_params.viterbi_verify = 4): bit 0 = every repaired chunk flags the chunk behind it as if its decoder had not arrived in
-                                     // pred[] (the flag / fix[] hand-over to the sequential pass is otherwise reached only by inputs nobody has seen)
+                                     // pred[] (the flag / fix[] hand-over to the sequential pass is otherwise reached only by inputs nobody has seen);
+                                     // bit 1 (V3_DEBUG_WALK, dvbt_rx_set_viterbi_walk) = every traceback chain walks all its hops, the shortcut over chained best states is never taken
 };
+constexpr int V3_DEBUG_WALK = 2;
 __device__ __forceinline__ int *v3_own(const V3Aux &ax, long long c) { return ax.snap + (3 * c) * V3_SLOT; }
 __device__ __forceinline__ int *v3_pred(const V3Aux &ax, long long c) { return ax.snap + (3 * c + 1) * V3_SLOT; }
 __device__ __forceinline__ int *v3_fix(const V3Aux &ax, long long c) { return ax.snap + (3 * c + 2) * V3_SLOT; }
@@ -444,7 +461,7 @@ __device__ __forceinline__ void v3_init_lut(unsigned *lut, int lane)
 template <int NTB, int WARM, int MODE, int NW>
 __device__ __forceinline__ void v3_decode(const uint8_t *__restrict__ in, uint8_t *__restrict__ out, long long total_steps, long long total_out, const VitParams &vp,
                                           long long in_base, long long out_lo, long long b0, bool dec_active, const V3Lds &S, const V3Lane &L, int (&v)[2], int (&endv)[2],
-                                          int *own, int *predn, const int *inject, int *carry, int carry_rel)
+                                          int *own, int *predn, const int *inject, int *carry, int carry_rel, int debug, unsigned long long *shortcut)
 {
   unsigned char *const tab = S.tab; unsigned *const wbuf = S.wbuf; unsigned char *const bests = S.bests; const unsigned *const lut = S.lut;
   // compacted received bits per decoder (MSB first): V3_CBW words at the head of the decoder's wbuf row.  stage_words reads them (every
@@ -526,7 +543,7 @@ __device__ __forceinline__ void v3_decode(const uint8_t *__restrict__ in, uint8_
     }
   };
   // ---- staging, second half: bit compaction and the step words of block jb
-  auto stage_words = [&](int jb) {
+  auto stage_words = [&](int jb, auto &&mid) {
     {
       const unsigned mk = (1u << m) - 1;
       auto grp = [&](unsigned d) { return ((d & mk) << (3 * m)) | (((d >> 8) & mk) << (2 * m)) | (((d >> 16) & mk) << m) | ((d >> 24) & mk); };
@@ -561,6 +578,7 @@ __device__ __forceinline__ void v3_decode(const uint8_t *__restrict__ in, uint8_
     const unsigned kmask = ((unsigned)(vp.punct_rep >> ph) << (2 * lo)) & (((1u << (2 * hi)) - 1u) & ~((1u << (2 * lo)) - 1u));
     const unsigned *cb = cbits + dd * V3_CBS;
     const unsigned cw0 = cb[pos >> 5], cw1 = cb[(pos >> 5) + 1];
+    mid();                                                         // (LDS returns in order: what is read here has arrived when the look-ups below have)
     unsigned win = (unsigned)(((((unsigned long long)cw0) << 32) | cw1) >> (32 - (pos & 31)));
     // the twelve table indices first (one VALU chain on win), then the twelve look-ups back to back behind ONE wait, then the lane's 48 bytes as three 16-byte stores.  Written as
     // look-up + store per step, the compiler keeps that order (the table and the step words are members of one LDS object) and the wavefront waits out twelve LDS round trips in a row
@@ -585,8 +603,10 @@ __device__ __forceinline__ void v3_decode(const uint8_t *__restrict__ in, uint8_
   // cell = rotr6(state, phase), so z = R ^ 12 * (R bit 4) with R = rotl6(state, 2 - phase) -- one shift by a constant of the lane (tsh, osh: computed once per kernel)
   V3Trace T;
   int tsh[2];                                                      // (phase after the window a chain starts in + 4) % 6, that phase = (8 jj + 8) % 6 = 2 * ((jj + 1) % 3)
+  int tsh_e[2];                                                    // the same for the window the chain ends in (jj - (ntb - 1))
 #pragma unroll
   for (int c = 0; c < 2; c++) {
+    tsh_e[c] = (2 * ((c * 16 + pl + 1 + 3 * ntb - (ntb - 1)) % 3) + 4) % 6;
     T.oend[c] = c * 16 + pl < V3_BLK ? ob_end : INT_MIN; tsh[c] = (2 * ((c * 16 + pl + 1) % 3) + 4) % 6; T.osh[c] = (6 - 2 * ((c * 16 + pl + 3 * ntb - (ntb - 1)) % 3)) % 6;
   }
   static_assert(V3_BLK % 3 == 0, "phases per lane");
@@ -596,6 +616,8 @@ __device__ __forceinline__ void v3_decode(const uint8_t *__restrict__ in, uint8_
 #pragma unroll
     for (int c = 0; c < 2; c++) bb[c] = bests[dd * V3_RINGW + ((jp + c * 16 + pl) & (V3_RINGW - 1))];
   };
+  // storage index of the best state's cell from the byte in bests (63 - best state = ~state in six bits): R = rotl6(bb, .) ^ 63, and 63 ^ 12 * (1 - bit) = 51 ^ 12 * bit
+  auto z_of_best = [](unsigned b, int sh) { const unsigned R = (b | (b << 6)) >> sh; return (R ^ 51u ^ (((R >> 4) & 1u) * 12u)) & 63u; };
   auto trace_init = [&](int jp, const unsigned (&bb)[2]) {
 #pragma unroll
     for (int c = 0; c < 2; c++) {
@@ -603,12 +625,42 @@ __device__ __forceinline__ void v3_decode(const uint8_t *__restrict__ in, uint8_
       T.ob[c] = jj - (warm + ntb - 1);
       T.ok[c] = __builtin_amdgcn_ballot_w64(T.ob[c] >= ob_lo && T.ob[c] < T.oend[c]);          // (a chain that is not ok runs all the same, over whatever the ring holds: every read is masked into the ring)
       T.wsh[c] = jj * V3_ROW<NW> + rowl;
-      // bb = 63 - best state = ~state in six bits: R = rotl6(bb, .) ^ 63, and 63 ^ 12 * (1 - bit) = 51 ^ 12 * bit
-      const unsigned R = (bb[c] | (bb[c] << 6)) >> tsh[c];
-      T.z[c] = (int)((R ^ 51u ^ (((R >> 4) & 1u) * 12u)) & 63u) | (T.wsh[c] & V3_RMASK<NW>);
+      T.z[c] = (int)z_of_best(bb[c], tsh[c]) | (T.wsh[c] & V3_RMASK<NW>);
     }
   };
-  unsigned bb[2];
+  // ---- the shortcut (see the header): the best states of the windows in front of the chains' starts and of the windows the chains end in are read with bb at the top of the
+  // iteration; behind the compacted bits' reads (stage_words' `mid`) the chains are set up and four path bytes are read: the first hop's (tl: it tells whether the hop from
+  // window jj's best state lands on window jj - 1's) and the one at the best state of the window the chain ends in (te: the call's byte when every link holds)
+  unsigned bb[2], be[2], tl[2], te[2];
+  int zp[2], zcarry = 0;                                           // zp: Z(jj - 1) in the low six bits; zcarry (lane 0 of a row): Z of the last window of the block before
+  auto bests_read_ends = [&](int jp) {
+#pragma unroll
+    for (int c = 0; c < 2; c++) be[c] = bests[dd * V3_RINGW + ((jp + c * 16 + pl - (ntb - 1)) & (V3_RINGW - 1))];
+  };
+  // Z(jj - 1) is the neighbouring lane's Z(jj): one row shift.  Lane 0 has no neighbour: its chain 1 (window jp + 16) takes chain 0's lane 15 (row_ror:1 as the value the shift
+  // leaves in place), its chain 0 the Z of window jp - 1 = the previous iteration's chain 1 of lane 7 (row_ror:9, kept in zcarry)
+  auto link_reads = [&](int jp) {
+    trace_init(jp, bb);
+    zp[0] = __builtin_amdgcn_update_dpp(zcarry, T.z[0], 0x111, 0xf, 0xf, false);                     // row_shr:1
+    zp[1] = __builtin_amdgcn_update_dpp(dppb<0x121>(T.z[0]), T.z[1], 0x111, 0xf, 0xf, false);
+#pragma unroll
+    for (int c = 0; c < 2; c++) tl[c] = tab[T.z[c]];
+    zcarry = dppb<0x129>(T.z[1]);
+  };
+  // the path byte at the best state of the window a chain ends in: read only where the shortcut is taken
+  auto end_reads = [&]() {
+#pragma unroll
+    for (int c = 0; c < 2; c++) te[c] = tab[(int)z_of_best(be[c], tsh_e[c]) | ((T.wsh[c] - (ntb - 1) * V3_ROW<NW>) & V3_RMASK<NW>)];
+  };
+  // all 24 links of the block at jp hold in every decoder of the wavefront that still has calls to deliver (chain 1 of the lanes 8..15 has no window in the block).  A decoder
+  // whose block starts behind its last call -- an idle one, or the stream's last chunk beside longer ones: its windows lie past the stream's end and chain up with nothing -- has
+  // none in any later block either, so its links are nobody's
+  auto links_hold = [&](int jp) {
+    const bool fails = jp - (warm + ntb - 1) < ob_end && ((((tl[0] ^ (unsigned)zp[0]) & 63u) != 0) || (pl < V3_BLK - 16 && ((tl[1] ^ (unsigned)zp[1]) & 63u) != 0));
+    return __builtin_amdgcn_ballot_w64(fails) == 0;
+  };
+  bool ok_prev = false;                                            // the links of the block before the one whose chains start now
+  unsigned n_short = 0, n_walk = 0;
 
   stage_load(0);
   for (int jb = 0; jb < J; jb += V3_BLK) {
@@ -623,10 +675,23 @@ __device__ __forceinline__ void v3_decode(const uint8_t *__restrict__ in, uint8_
       if (carry && dec_active && jb == carry_rel) { carry[0] = v[0]; carry[1] = v[1]; }
     }
     bests_read(jb - V3_BLK, bb);                                   // (block 0: whatever the ring holds, unused)
-    if (!(V3_EXP & 8) || jb == 0) stage_words(jb);
+    bests_read_ends(jb - V3_BLK);
+    if (!(V3_EXP & 8) || jb == 0) stage_words(jb, [&]() { link_reads(jb - V3_BLK); });
+    else link_reads(jb - V3_BLK);
     if (jb + V3_BLK < J && !(V3_EXP & 8)) stage_load(jb + V3_BLK);                  // the bytes of the next block travel during this block's forward pass
-    const bool tr = jb > 0 && !(V3_EXP & 1);
-    if (tr) trace_init(jb - V3_BLK, bb);
+    // The decision, once per iteration and wave-uniform.  A chain started at window jj walks through the windows jj - 1 .. jj - (ntb - 1); where every hop lands on the best state
+    // of the window it reaches, the chain ends at the best state of window jj - (ntb - 1) and its byte is te.  The chains of this block need the links of the windows
+    // jj - (ntb - 2) .. jj: this block's and the one's before (more than needed, and enough for every ntraceback).  Nothing is walked either where no chain ends in a call.
+    // (bests_read_ends, trace_init and link_reads run in every iteration, jb == 0 and the switched-off decoder included: over whatever the ring and bests[] hold, every index
+    // masked into the ring; only te is read on the fast branch alone.  Block 0's link(0) compares with a zcarry nobody set and block 0 has no verdict (jb > 0 below), so the first
+    // iteration that can be fast is jb = 72: the blocks at 24 and 48 both seen.)
+    const bool ok_cur = jb > 0 && links_hold(jb - V3_BLK);
+    const bool ends = (T.ok[0] | T.ok[1]) != 0;
+    const bool fast = ok_cur && ok_prev && !(debug & V3_DEBUG_WALK) && !(V3_EXP & 1);
+    ok_prev = ok_cur;
+    const bool tr = jb > 0 && !fast && ends && !(V3_EXP & 1);
+    if (fast && ends) { end_reads(); v3_trace_store<true>(T, te, outb); n_short++; }
+    if (tr) n_walk++;
     const unsigned *wrow = wbuf + dd * (V3_BLK * 8);
     unsigned Wa[8], Wb[8];                                         // the step words of the current and of the next window
     v3_load_words(wrow, Wa);
@@ -648,6 +713,7 @@ __device__ __forceinline__ void v3_decode(const uint8_t *__restrict__ in, uint8_
   trace_init(J - V3_BLK, bb);
   for (int h = 0; h < ntb - 1; h++) v3_hop<NW>(T, tab);
   v3_trace_out(T, tab, outb);
+  if (MODE == 1 && shortcut && lane == 0) { atomicAdd(shortcut, (unsigned long long)n_short); atomicAdd(shortcut + 1, (unsigned long long)n_walk); }
 }
 
 // One object, the ring first: it is the kernel's only LDS variable, so the ring starts at LDS offset 0 and a ring offset IS the ds address (a hop adds no base).  Nothing depends
@@ -693,7 +759,8 @@ template <int NTB, int WARM = V3_WARM, int MODE = 0> __global__ __launch_bounds_
     if (c == 0 && ax.carry_in) inject = ax.carry_in + 2 * pl;
     if (ax.carry_out && b0 + B >= total_out) carry = ax.carry_out + 2 * pl;      // the launch's last chunk
   }
-  v3_decode<NTB, WARM, MODE, V3_WGW>(in, out, total_steps, total_out, vp, in_base, out_lo, b0, dec_active, S, L, v, endv, own, predn, inject, carry, ax.carry_rel);
+  v3_decode<NTB, WARM, MODE, V3_WGW>(in, out, total_steps, total_out, vp, in_base, out_lo, b0, dec_active, S, L, v, endv, own, predn, inject, carry, ax.carry_rel, ax.debug,
+                                     MODE == 1 ? reinterpret_cast<unsigned long long *>(ax.ctl + V3_CTL_SHORT) : nullptr);
 #if V3_EXP & 16
   if (lane == 0) {
     unsigned id, xcc;
@@ -762,7 +829,7 @@ template <int NTB, int NW> __device__ __forceinline__ void v3_repair_rows(const 
     int v[2], endv[2] = {0, 0};
     { const int *p = v3_pred(ax, c) + 2 * pl; v[0] = p[0]; v[1] = p[1]; }
     int *carry = (act && ax.carry_out && b0 + B >= total_out) ? ax.carry_out + 2 * pl : nullptr;
-    v3_decode<NTB, 0, 2, NW>(in, out, total_steps, total_out, vp, in_base, out_lo, b0, act && b0 < total_out, S, L, v, endv, v3_own(ax, c) + 2 * pl, nullptr, nullptr, carry, ax.carry_rel);
+    v3_decode<NTB, 0, 2, NW>(in, out, total_steps, total_out, vp, in_base, out_lo, b0, act && b0 < total_out, S, L, v, endv, v3_own(ax, c) + 2 * pl, nullptr, nullptr, carry, ax.carry_rel, ax.debug, nullptr);
     int pn[2] = {endv[0], endv[1]};
     if (act && c + 1 < nch) { const int *p = v3_pred(ax, c + 1) + 2 * pl; pn[0] = p[0]; pn[1] = p[1]; }
     if (!v3_row_equal(endv, pn, dd) || ((ax.debug & 1) && act && c + 1 < nch)) {   // the repaired decoder does not arrive where the unproven one did: the sequential pass goes on from here
@@ -822,7 +889,7 @@ template <int NTB, int NW> __device__ __forceinline__ void v3_seq_walk(const uin
       int st0[2] = {v[0], v[1]}, endv[2] = {0, 0};
       if (act) { int *p = v3_pred(ax, c) + 2 * pl; p[0] = v[0]; p[1] = v[1]; }
       int *carry = (act && ax.carry_out && b0 + B >= total_out) ? ax.carry_out + 2 * pl : nullptr;
-      v3_decode<NTB, 0, 2, NW>(in, out, total_steps, total_out, vp, in_base, out_lo, b0, act, S, L, st0, endv, v3_own(ax, c) + 2 * pl, nullptr, nullptr, carry, ax.carry_rel);
+      v3_decode<NTB, 0, 2, NW>(in, out, total_steps, total_out, vp, in_base, out_lo, b0, act, S, L, st0, endv, v3_own(ax, c) + 2 * pl, nullptr, nullptr, carry, ax.carry_rel, ax.debug, nullptr);
       __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
       done++;
       if (c + 1 >= nch) { pos = nch; break; }

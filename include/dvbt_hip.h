@@ -212,6 +212,10 @@ int  dvbt_viterbi_decoder_work_device(dvbt_viterbi_decoder *h, int noutput_items
 int  dvbt_viterbi_decoder_set_warm_windows(dvbt_viterbi_decoder *h, int windows);
 /* counters of the block's proof + repair passes, summed over its calls since the last reset (chunks, decoded_again, sequential; not_proven = -1: the block runs no final check) */
 int  dvbt_viterbi_decoder_proof(dvbt_viterbi_decoder *h, dvbt_viterbi_proof *out);
+/* always != 0: the traceback chains of the following calls walk every hop instead of taking the shortcut over chained best states (the same bytes; tests, measurements) */
+int  dvbt_viterbi_decoder_set_walk(dvbt_viterbi_decoder *h, int always);
+/* out[0], out[1]: blocks of 24 windows, per wavefront, whose bytes left by the shortcut / whose chains walked, since the block was created */
+int  dvbt_viterbi_decoder_shortcut(dvbt_viterbi_decoder *h, long long out[2]);
 void dvbt_viterbi_decoder_destroy(dvbt_viterbi_decoder *h);
 
 /* ------------------------------------------------------------------ A8 convolutional_deinterleaver
@@ -573,6 +577,10 @@ typedef struct {
 int  dvbt_rx_viterbi_proof(dvbt_rx *h, dvbt_viterbi_proof *out);
 /* the same counters summed over every launch of the handle's decoder since it was created (a synchronous run launches the decoder once per lock period); not_proven = -1 */
 int  dvbt_rx_viterbi_proof_total(dvbt_rx *h, dvbt_viterbi_proof *out);
+/* always != 0: the Viterbi decoder's traceback chains walk every hop instead of taking the shortcut over chained best states (the same bytes); drops the captured graphs */
+int  dvbt_rx_set_viterbi_walk(dvbt_rx *h, int always);
+/* out[0], out[1]: blocks of 24 windows, per wavefront, whose bytes left by the shortcut / whose chains walked, since the handle was created (viterbi_verify >= 0) */
+int  dvbt_rx_viterbi_shortcut(dvbt_rx *h, long long out[2]);
 /* (chunks, not_proven) of the same; needs the final check (viterbi_verify >= 1) */
 int  dvbt_rx_viterbi_check(dvbt_rx *h, int64_t *chunks, int64_t *unproven);
 int  dvbt_rx_lock_periods(dvbt_rx *h, dvbt_lock_period *out, int cap);

@@ -1,6 +1,8 @@
 // vit_kbench.hip -- viterbi3_kernel alone on synthetic input: launch time vs chunk size / occupancy build, without the rest of
 // the chain.  Experiment tool (not part of the product library).  Build: hipcc --offload-arch=gfx950 -O3 -std=c++17 [-DV3_EXP=bits]
-// -I gr_dvbt_amd/csrc -o tools/vit_kbench tools/vit_kbench.hip ; run: tools/vit_kbench [symbols=17475] [chunk_bytes...]
+// -I gr_dvbt_amd/csrc -o tools/vit_kbench tools/vit_kbench.hip ; run: tools/vit_kbench [clean] [symbols=17475] [chunk_bytes...]
+// clean: the input is a codeword (random bytes through the mother code and the 7/8 puncturing, no bit flipped) instead of random symbols, and the decoded bytes are compared
+// with the transmitted ones -- on random symbols no two best states chain up, so whatever the traceback does where they do is not exercised.
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdlib>
@@ -17,13 +19,35 @@ __global__ void clock_probe(unsigned long long *o, long long spin)
   o[0] = clock64() - c0; o[1] = wall_clock64() - w0;
 }
 
+// K = 7 mother code (171, 133 octal) from the zero state, punctured by d.punct, packed into d.m-bit symbols, first bit the most significant; data = the transmitted bytes
+static void clean_stream(const Dims &d, std::vector<uint8_t> &sym, std::vector<uint8_t> &data)
+{
+  const long long nbits = ((long long)sym.size() * d.m * d.k + d.n - 1) / d.n + 2 * d.k;     // input bits that cover every symbol
+  data.assign((size_t)(nbits + 7) / 8, 0);
+  unsigned x = 2463534242u; for (auto &b : data) { x ^= x << 13; x ^= x >> 17; x ^= x << 5; b = (uint8_t)(x >> 11); }
+  unsigned sr = 0, acc = 0; int have = 0; long long coded = 0; size_t ns = 0;
+  for (long long i = 0; i < nbits && ns < sym.size(); i++) {
+    sr = ((sr << 1) | ((data[(size_t)(i >> 3)] >> (7 - (i & 7))) & 1u)) & 127u;                 // bit 0 = the newest input
+    const unsigned xy[2] = {(unsigned)__builtin_parity(sr & 0x4fu), (unsigned)__builtin_parity(sr & 0x6du)};   // taps 0,1,2,3,6 and 0,2,3,5,6
+    for (int h = 0; h < 2; h++, coded++) {
+      if (!d.punct[coded % d.plen]) continue;
+      acc = (acc << 1) | xy[h];
+      if (++have == d.m) { if (ns < sym.size()) sym[ns++] = (uint8_t)acc; acc = 0; have = 0; }
+    }
+  }
+}
+
 int main(int argc, char **argv)
 {
+  const bool clean = argc > 1 && !strcmp(argv[1], "clean");
+  if (clean) { argc--; argv++; }
   const int nsym = argc > 1 ? atoi(argv[1]) : 17475;
   Dims d = make_dims(2, 0, 4, 0, 1);                            // 8k QAM64 7/8
   const long long nin = (long long)nsym * d.payload / 1024 * 1024, steps = nin / 1024 * 5376, nout = steps / 8 - d.ntb;
   std::vector<uint8_t> h(nin);
-  unsigned x = 12345; for (auto &b : h) { x = x * 1664525u + 1013904223u; b = (x >> 24) & 63; }
+  std::vector<uint8_t> sent;
+  if (clean) clean_stream(d, h, sent);
+  else { unsigned x = 12345; for (auto &b : h) { x = x * 1664525u + 1013904223u; b = (x >> 24) & 63; } }
   uint8_t *din, *dout; (void)hipMalloc((void **)&din, nin + 64); (void)hipMalloc((void **)&dout, nout + 64);
   (void)hipMemcpy(din, h.data(), nin, hipMemcpyHostToDevice);
   int ncu = 256; (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, 0);
@@ -85,7 +109,10 @@ int main(int argc, char **argv)
     std::vector<uint8_t> o(nout); (void)hipMemcpy(o.data(), dout, nout, hipMemcpyDeviceToHost);
     unsigned long long sum = 0; for (long long i = 0; i < nout; i++) sum = sum * 1099511628211ull + o[i];
     if (!sum0) sum0 = sum;
-    printf("{\"exp_bits\": %d, \"shader_mhz_under_load\": %.0f, \"chunk_bytes\": %d, \"wavefronts\": %u, \"waves_per_cu\": %.2f, \"ms\": %.4f, \"decoded_gbit_s\": %.1f, \"same_output\": %s}\n", V3_EXP, mhz, cb, grid.x * V3_WGW,
+    long long wrong = -1;                                          // (clean input: decoded bytes that are not the transmitted ones; V3_EXP = 0 must give 0)
+    if (clean) { wrong = 0; for (long long i = 0; i < nout; i++) wrong += o[i] != sent[i]; }
+    printf("{\"exp_bits\": %d, \"input\": \"%s\", \"wrong_bytes\": %lld, \"shader_mhz_under_load\": %.0f, \"chunk_bytes\": %d, \"wavefronts\": %u, \"waves_per_cu\": %.2f, \"ms\": %.4f, \"decoded_gbit_s\": %.1f, \"same_output\": %s}\n",
+           V3_EXP, clean ? "clean codeword" : "random symbols", wrong, mhz, cb, grid.x * V3_WGW,
            (double)grid.x * V3_WGW / ncu, best, nout * 8 / (best * 1e-3) / 1e9, sum == sum0 ? "true" : "false");
   }
   return 0;
