@@ -18,10 +18,15 @@
 // A 16-bit cell = (2M + bias) << 8 | path byte.
 //  * metric field (8 bits, signed): M in units of half an agreement, bias = 1 when the cell holds an upper state
 //    (i+32): compares are strict and reproduce the reference's tie rule (d_viterbi.c:508-521).  For a K=7 code
-//    the spread of the 64 metrics is bounded by 6 steps x the per-step range: 2M+bias spans <= 49; it drifts by at
-//    most +-4 per step, and every second window the best metric is set back to 48 (the reference subtracts the
-//    minimum at every output only to keep ITS 8-bit metrics from wrapping, :728-732; any common offset is
-//    equivalent), so the field stays within [-65, 113].
+//    the spread of the 64 metrics is bounded by 6 steps x the per-step range: 2M+bias spans <= 49, whenever the offset
+//    was last removed.  The best field never decreases: of the best state's two outgoing branches (complementary
+//    labels) one has delta >= 0; and it rises by at most 4 per step (|delta| <= 4).  Every V3_RENORM_EVERY = 6 windows
+//    the best field is set back to T = V3_RENORM_BEST = -72 (the reference subtracts the minimum at every output only
+//    to keep ITS 8-bit metrics from wrapping, :728-732; any common offset changes no compare), so s steps later every
+//    field lies in [T - 49, T + 1 + 4s] and the candidates X, Y of a step in [T - 53, T + 5 + 4s]: with s <= 48 that
+//    is [-125, 125], inside int8 (the static_asserts at V3_RENORM_BEST; eight windows would need 310 values and do
+//    not fit, so six is the longest cadence that divides V3_BLK).  A decoder starts with every field at T, as if
+//    behind a renormalisation.  tests/test_viterbi_renorm_model.py runs the recurrence in exact integers.
 //  * path byte (8 bits): the content of the reference's path byte of the survivor -- the state at the window start
 //    (kept as that state's cell storage index, bits 5:0) and the two oldest inputs of the window (= top two bits of
 //    the state after step 6, stamped there, bits 7:6).  It rides along with the metric through v_pk_max (metric
@@ -37,11 +42,12 @@
 // pk_sub, exchange, pk_max, and on every second step a v_and_or: 2.75 instructions per cell.
 //
 // The instruction budget, as compiled (tools/vit_window_count.py on the device assembly; tests/test_viterbi_isa_budget.py holds it): a window is 77 VALU instructions for
-// its eight steps, 1 for the path-byte word and 12.5 for its end = 90.5, plus its address arithmetic; a traceback hop is 2 per chain (one row back, one v_bfi).  A block of
+// its eight steps, 1 for the path-byte word and 10.8 for its end (key and argmax 10, the renormalisation's 5 every sixth window; 12.5 = 90.5 in all while it ran every second) = 88.8, plus its address arithmetic; a traceback hop is 2 per chain (one row back, one v_bfi).  A block of
 // V3_BLK windows of viterbi3_kernel<24, 72, 1> is straight-line code: windows 0-11 with the previous block's 2 x 23 hops, the start of its chains' output and the calls' bytes
 // 97.6 per window (106.8 before the ring became one array of the workgroup; 95.7 while the calls' bytes were assembled behind the block), the other blocks of twelve 91.5 and
 // 87.9 (94.0 as a loop of six), staging and the chains' start ~240 per block (~270 with the output before round 8): 2,458 instructions per block of 24 windows measured
-// (SQ_INSTS_VALU; 2,472 in round 7, 2,727 before it).  Every stamp is one v_and_or_b32 (the lane constants are kept opaque, v3_init_lane).
+// (SQ_INSTS_VALU; 2,472 in round 7, 2,727 before it).  Since rounds 9 and 10 (the shortcut below; the renormalisation every sixth window): the hop-free windows 0-11 86.3 per window, with
+// hops 94.7, windows 12-23 90.2 (88.0 / 96.3 / 91.8 with the renormalisation every second window; tests/test_viterbi_isa_renorm.py holds them), 2,361 per block measured (2,400 in round 9).  Every stamp is one v_and_or_b32 (the lane constants are kept opaque, v3_init_lane).
 // What the count alone did not buy, the order of the LDS reads did: a hop's read and its use stand three and five steps apart (v3_fwd_window), and a window's
 // step words are loaded one window ahead (v3_fwd_six) -- the wavefront, one of two on its SIMD, no longer waits out the LDS latency 70 times per block.  The same holds around
 // the windows since round 8: staging computes a lane's twelve table indices first, issues the twelve look-ups back to back behind one wait and stores the words as three
@@ -59,7 +65,7 @@
 // iteration's verdict) -- more than any chain needs, and enough for every ntraceback.  Z(jj - 1) is the neighbouring lane's Z(jj) (one DPP row shift); the first hop's reads ride
 // on staging's waits (link_reads: behind the compacted bits' reads, met by the waits of the table look-ups; LDS returns in order); where the shortcut is taken the path bytes at the
 // best states of the windows the chains end in are read and the calls' bytes leave under the chains' exec masks before the first window, and the iteration runs the hop-free
-// windows.  Where a link fails the chains walk as before; where no chain of the wavefront ends in a call (warm-up, idle tails) nothing is walked at all.  The hop block it replaces is 12 x (96.3 - 88.0) = 100 instructions and
+// windows.  Where a link fails the chains walk as before; where no chain of the wavefront ends in a call (warm-up, idle tails) nothing is walked at all.  The hop block it replaces is 12 x (94.7 - 86.3) = 100 instructions and
 // 46 + 2 dependent LDS round trips.
 // V3Aux.debug bit 1 (dvbt_rx_set_viterbi_walk) switches the shortcut off; the MODE 1 decoders count both kinds of iteration (ctl[V3_CTL_SHORT]).
 #pragma once
@@ -112,7 +118,13 @@ constexpr int V3_WGW = V3_WGW_N;    // wavefronts per workgroup: independent (no
 constexpr int V3_WARM = 72;        // warm-up windows before a chunk's first byte (the default; dvbt_rx_params.viterbi_warm_windows selects the WARM = 0 instantiation, which reads VitParams.warm)
 constexpr int V3_WARM_MAX = 1152;  // the largest warm-up the parameter accepts
 static_assert(V3_WARM == 72, "make_vit_params (above) presets VitParams.warm to the default");
-constexpr int V3_BLK = 24;         // windows per forward block (multiple of 6: phase cycle x renormalisation cadence)
+constexpr int V3_BLK = 24;         // windows per forward block (a multiple of 3, the phase cycle, and of V3_RENORM_EVERY: every block ends right behind a renormalisation)
+constexpr int V3_RENORM_EVERY = 6; // windows between two renormalisations: the last window of every group of six sets the best metric field back to V3_RENORM_BEST
+constexpr int V3_RENORM_BEST = -72; // (even: bit 8 of a cell is the tie-break bit).  The range note in the header, as arithmetic:
+static_assert(V3_BLK % V3_RENORM_EVERY == 0, "a block of windows ends right behind a renormalisation: equal states are equal registers at a block's top (proof, repair, carried state)");
+static_assert(V3_RENORM_BEST % 2 == 0, "the renormalisation leaves bit 8 of the cells alone");
+static_assert(V3_RENORM_BEST - 49 - 4 >= -128, "lowest candidate of a step: the best field never decreases, the spread is at most 49, |delta| <= 4");
+static_assert(V3_RENORM_BEST + 1 + 4 * 8 * V3_RENORM_EVERY + 4 <= 127, "highest candidate of a step: the best field rises by at most 4 per step, 8 steps per window");
 constexpr int V3_RINGW = 64;       // windows kept in the LDS ring (power of two, >= 2*V3_BLK - 12 + max ntraceback - 1: the traceback of a
                                    // block runs during the first 12 windows of the next one).  20 KB of LDS per wavefront = 2 wavefronts
                                    // per SIMD.  A 32-window ring with traceback groups of six windows (3 wavefronts per SIMD) was built and
@@ -250,9 +262,10 @@ template <int PE, bool RENORM> __device__ __forceinline__ int v3_window_end(int 
   k = max_dpp<DPP_XOR1>(k); k = max_dpp<DPP_XOR2>(k); k = max_dpp<DPP_HALF_MIRROR>(k); k = max_dpp<DPP_MIRROR>(k);
   if (RENORM) {
     // any offset common to the 64 metrics will do (the reference subtracts the minimum, d_viterbi.c:728-732, only to keep
-    // its 8-bit metrics from wrapping): the maximum is already here, so the best metric is set to 2*24 -- the spread is
-    // at most 49, so the field restarts inside [-1, 49] and drifts by at most +-64 until the next renormalisation
-    const unsigned sub = (unsigned)((k & ~0x1ff) - (48 << 8));        // (2 M_best - 48) at the metric position; bias and path byte untouched
+    // its 8-bit metrics from wrapping): the maximum is already here, so the best metric is set to V3_RENORM_BEST -- the
+    // spread is at most 49, so the field restarts inside [BEST - 49, BEST + 1], and until the next renormalisation,
+    // 8 * V3_RENORM_EVERY steps on, only its upper end moves: by at most 4 per step (the range note in the header)
+    const unsigned sub = (unsigned)((k & ~0x1ff) - V3_RENORM_BEST * 256);   // (2 M_best - BEST) at the metric position; bias and path byte untouched
     const int mn = (int)__builtin_amdgcn_perm(sub, sub, 0x01000100u);
     v[0] = pk_sub(v[0], mn); v[1] = pk_sub(v[1], mn);
   }
@@ -319,8 +332,8 @@ template <bool MASKED> __device__ __forceinline__ void v3_trace_store(const V3Tr
 }
 __device__ __forceinline__ void v3_trace_out(const V3Trace &T, const unsigned char *tab, uint8_t *outb) { unsigned t[2]; v3_trace_read(T, tab, t); v3_trace_store<false>(T, t, outb); }
 
-// window j0 + V6 of a decoder (j0 % 6 == 0): it starts at phase (8 V6) % 6 = 0,2,4,0,2,4; the minimum is subtracted
-// after every second window.  HOPS: two traceback hops of the previous block's calls ride along (their LDS latency
+// window j0 + V6 of a decoder (j0 % 6 == 0): it starts at phase (8 V6) % 6 = 0,2,4,0,2,4; the last window of the six
+// (V6 == V3_RENORM_EVERY - 1) renormalises.  HOPS: two traceback hops of the previous block's calls ride along (their LDS latency
 // hides under the add-compare-select work).
 // Which hops exist is a compile-time fact (HOP0 + 2 V6 (+1) < NTB - 1 with NTB = ntraceback, a template parameter of the
 // kernel): the window stays one straight-line block, with the dependent LDS reads spread over it (below).
@@ -369,9 +382,10 @@ template <int V6, bool HOPS, int HOP0, int NTB, int NW, bool PREF> __device__ __
   // the four path bytes of this lane's cells = one word of the table (storage index z = 4*lane + 2r + h)
   if (!(V3_EXP & 4)) *reinterpret_cast<unsigned *>(tabw + jr * V3_ROW<NW>) = __builtin_amdgcn_perm((unsigned)raw[1], (unsigned)raw[0], 0x06040200u);
   if (V3_EXP & 2) { if (raw[0] == 0x12345) bests[jr] = 1; return; }
-  const int s = v3_window_end<(P0 + 2) % 6, (V6 & 1) == 1>(v, L);
+  const int s = v3_window_end<(P0 + 2) % 6, V6 == V3_RENORM_EVERY - 1>(v, L);
   bests[dd * V3_RINGW + jr] = (unsigned char)s;                    // low byte of the key (63 - best state in bits 5:0); all 16 lanes of the row write the same byte
 }
+static_assert(V3_RENORM_EVERY == 6, "v3_fwd_six is the group of windows that ends in a renormalisation (V6 = 0..5)");
 // six windows; Wa arrives with the first window's step words and leaves with those of the window behind the six (MORE: there is one in this block)
 template <bool HOPS, int HOP0, int NTB, int NW, bool MORE> __device__ __forceinline__ void v3_fwd_six(int (&v)[2], const V3Lane &L, const unsigned *wrow, unsigned char *tab, unsigned char *tabw,
                                                                                   unsigned char *bests, int j0, int dd, int pl, V3Trace &T, unsigned (&Wa)[8], unsigned (&Wb)[8], uint8_t *outb)
@@ -382,7 +396,7 @@ template <bool HOPS, int HOP0, int NTB, int NW, bool MORE> __device__ __forceinl
 }
 
 // A chunk = vp.chunk_bytes decoded bytes; it is decoded by an independent decoder that starts `warm` windows early
-// from all-zero metrics and runs ntraceback-1 windows past its end.  Per block of 24 windows:
+// from equal metrics (all V3_RENORM_BEST) and runs ntraceback-1 windows past its end.  Per block of 24 windows:
 //   staging   depuncture (viterbi_decoder_impl.cc:241-256) + delta packing for 192 steps x 4 decoders.  The row
 //             loads the input bytes of its decoder (one 16-byte load per lane, issued one block ahead) and compacts
 //             the m valid bits of every byte into a bit stream in LDS; every lane then owns 12 consecutive steps:
@@ -397,7 +411,7 @@ __device__ unsigned long long *v3_dbg;     // tools/vit_kbench.hip: (hw id, star
 #endif
 
 // ---- The chunk decoders ARE the reference's one streaming decoder (viterbi_decoder_impl.cc:192-324, d_viterbi.c:680-735), by construction: proof + repair.
-// A decoder's whole state at the top of a block of windows is its two registers of cells: the block starts at phase 0 right behind a renormalisation (best metric = 48) and the
+// A decoder's whole state at the top of a block of windows is its two registers of cells: the block starts at phase 0 right behind a renormalisation (best metric field = V3_RENORM_BEST) and the
 // low nine bits of a cell are a function of the lane and the phase alone (v3_step, ST == 2) -- two decoders over the same input whose registers are EQUAL there make identical
 // decisions from there on.  With B a multiple of V3_BLK the decoder of chunk c stands at the top of a block when it reaches its chunk's first window (relative window warm) and
 // so does its predecessor, B windows further into its own run: both store their registers (MODE 1).  Per chunk c three slots of 32 words:
@@ -752,7 +766,10 @@ template <int NTB, int WARM = V3_WARM, int MODE = 0> __global__ __launch_bounds_
   const unsigned long long dbg_t0 = wall_clock64();
 #endif
   V3Lane L; v3_init_lane(pl, L);
-  int v[2] = {L.arm_org[0][0], L.arm_org[0][1]}, endv[2];          // all-zero metrics, origin stamp of window 0, tie-break bits of its first three steps
+  // equal metrics, origin stamp of window 0, tie-break bits of its first three steps.  The metric byte of both halves starts at V3_RENORM_BEST, where a renormalisation
+  // would have left the best: the first one comes V3_RENORM_EVERY windows on, and from 0 the field would pass 127 before it
+  constexpr int v3_start = (int)(((unsigned)(V3_RENORM_BEST & 0xff) << 8) * 0x00010001u);
+  int v[2] = {L.arm_org[0][0] | v3_start, L.arm_org[0][1] | v3_start}, endv[2];
   int *own = nullptr, *predn = nullptr, *carry = nullptr; const int *inject = nullptr;
   if (MODE == 1) {
     own = v3_own(ax, c) + 2 * pl; predn = v3_pred(ax, c + 1) + 2 * pl;

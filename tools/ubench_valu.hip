@@ -8,6 +8,7 @@
 // throughput is instructions x waves / (cycles until the LAST wave ends): simd_cycles_per_inst = slowest_wave / waves_per_simd.
 // Its floor over W is the issue cadence of the instruction class.
 // Build: hipcc --offload-arch=gfx950 -O2 -o ubench_valu tools/ubench_valu.hip ; run: ./ubench_valu > profiles/rNN_ubench_valu.json
+// (./ubench_valu mul > profiles/rNN_ubench_valu_mul.json: the 32-bit and 24-bit integer multiplies alone)
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <vector>
@@ -123,13 +124,14 @@
 #define REP8(x) x x x x x x x x
 #define REP64(x) REP8(REP8(x))
 
-enum { K_PK_ADD, K_PK_MAX, K_PERM, K_AND_OR, K_DPP_ROR8, K_DPP_QUAD, K_ALIGNBIT, K_MAX_DPP, K_ADD_U32, K_ACS_MIX, K_ADD_E64, K_AND_E32, K_MAX_I16_E32, K_ADD_LIT, K_HALF_MIX, K_REAL, K_REAL_3K, K_REAL_24K, K_REGS_KERNEL, K_REGS_SPREAD, K_COUNT };
+enum { K_PK_ADD, K_PK_MAX, K_PERM, K_AND_OR, K_DPP_ROR8, K_DPP_QUAD, K_ALIGNBIT, K_MAX_DPP, K_ADD_U32, K_ACS_MIX, K_ADD_E64, K_AND_E32, K_MAX_I16_E32, K_ADD_LIT, K_HALF_MIX, K_REAL, K_REAL_3K, K_REAL_24K, K_REGS_KERNEL, K_REGS_SPREAD, K_MUL_LO_U32, K_MUL_U32_U24, K_MAD_U32_U24, K_COUNT };
 static const char *kNames[] = {"v_pk_add_i16", "v_pk_max_i16", "v_perm_b32", "v_and_or_b32", "v_mov_b32_dpp row_ror:8", "v_mov_b32_dpp quad_perm",
                                "v_alignbit_b32", "v_max_i32_dpp row_mirror", "v_add_u32", "acs mix (perm,pk_add,pk_sub,dpp,pk_max,and_or)",
                                "v_add_u32_e64 (VOP3 encoding, 8 bytes)", "v_and_b32 (VOP2, 4 bytes)", "v_max_i16 (VOP2, 4 bytes)", "v_add_u32 + 32-bit literal (8 bytes)", "alternating v_add_u32 (4 B) / v_pk_add_i16 (8 B)",
                                "4 trellis steps as compiled in viterbi3_kernel (SGPR mask, 4 DPP controls)",
                                "the same, loop body of 3 KB (8 copies)", "the same, straight-line loop body of 24 KB (64 copies)",
-                               "4 steps with the VGPR numbers of the compiled kernel (sources share register banks)", "4 steps with VGPR numbers spread over the 4 banks"};
+                               "4 steps with the VGPR numbers of the compiled kernel (sources share register banks)", "4 steps with VGPR numbers spread over the 4 banks",
+                               "v_mul_lo_u32", "v_mul_u32_u24", "v_mad_u32_u24"};
 
 template <int KIND, bool DEP> __global__ __launch_bounds__(1024) void k(int iters, long long *cycles, int *sink, unsigned *hwid)
 {
@@ -207,6 +209,19 @@ template <int KIND, bool DEP> __global__ __launch_bounds__(1024) void k(int iter
       asm volatile(REP8("v_add_u32 %0, 0x12345678, %0\n v_add_u32 %1, 0x12345678, %1\n v_add_u32 %2, 0x12345678, %2\n v_add_u32 %3, 0x12345678, %3\n"
                         "v_add_u32 %4, 0x12345678, %4\n v_add_u32 %5, 0x12345678, %5\n v_add_u32 %6, 0x12345678, %6\n v_add_u32 %7, 0x12345678, %7\n")
                    : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3), "+v"(a4), "+v"(a5), "+v"(a6), "+v"(a7));
+    } else if (KIND == K_MUL_LO_U32) {
+      // the staging multiplies of k_viterbi3.hpp (stage_load / stage_words): 32-bit against 24-bit, eight independent chains
+      asm volatile(REP8("v_mul_lo_u32 %0, %0, %8\n v_mul_lo_u32 %1, %1, %8\n v_mul_lo_u32 %2, %2, %8\n v_mul_lo_u32 %3, %3, %8\n"
+                        "v_mul_lo_u32 %4, %4, %8\n v_mul_lo_u32 %5, %5, %8\n v_mul_lo_u32 %6, %6, %8\n v_mul_lo_u32 %7, %7, %8\n")
+                   : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3), "+v"(a4), "+v"(a5), "+v"(a6), "+v"(a7) : "v"(b));
+    } else if (KIND == K_MUL_U32_U24) {
+      asm volatile(REP8("v_mul_u32_u24 %0, %0, %8\n v_mul_u32_u24 %1, %1, %8\n v_mul_u32_u24 %2, %2, %8\n v_mul_u32_u24 %3, %3, %8\n"
+                        "v_mul_u32_u24 %4, %4, %8\n v_mul_u32_u24 %5, %5, %8\n v_mul_u32_u24 %6, %6, %8\n v_mul_u32_u24 %7, %7, %8\n")
+                   : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3), "+v"(a4), "+v"(a5), "+v"(a6), "+v"(a7) : "v"(b));
+    } else if (KIND == K_MAD_U32_U24) {
+      asm volatile(REP8("v_mad_u32_u24 %0, %0, %8, %8\n v_mad_u32_u24 %1, %1, %8, %8\n v_mad_u32_u24 %2, %2, %8, %8\n v_mad_u32_u24 %3, %3, %8, %8\n"
+                        "v_mad_u32_u24 %4, %4, %8, %8\n v_mad_u32_u24 %5, %5, %8, %8\n v_mad_u32_u24 %6, %6, %8, %8\n v_mad_u32_u24 %7, %7, %8, %8\n")
+                   : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3), "+v"(a4), "+v"(a5), "+v"(a6), "+v"(a7) : "v"(b));
     } else if (KIND == K_HALF_MIX) {
       asm volatile(REP8("v_add_u32 %0, %0, %8\n v_pk_add_i16 %1, %1, %8\n v_add_u32 %2, %2, %8\n v_pk_add_i16 %3, %3, %8\n"
                         "v_add_u32 %4, %4, %8\n v_pk_add_i16 %5, %5, %8\n v_add_u32 %6, %6, %8\n v_pk_add_i16 %7, %7, %8\n")
@@ -308,8 +323,10 @@ template <int KIND> static void both(int ncu, long long *d_cyc, int *d_sink, uns
   for (int i = 0; i < 6; i++) run<KIND, false>(cfg[i][0], cfg[i][1], ncu, d_cyc, d_sink, d_hw, last && i == 5);
 }
 
-int main()
+// `ubench_valu mul`: only the rows of the integer multiplies (one workgroup per CU, W = 2, eight independent chains), with v_add_u32 beside them as the full-rate yardstick
+int main(int argc, char **argv)
 {
+  const bool mul_only = argc > 1 && std::string(argv[1]) == "mul";
   int ncu = 256; (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, 0);
   int clk = 0; (void)hipDeviceGetAttribute(&clk, hipDeviceAttributeClockRate, 0);
   long long *d_cyc; int *d_sink; unsigned *d_hw;
@@ -317,6 +334,12 @@ int main()
   hipDeviceProp_t pr; (void)hipGetDeviceProperties(&pr, 0);
   printf("{\"device\": \"%s\", \"gcn_arch\": \"%s\", \"cus\": %d, \"clock_khz\": %d, \"timer\": \"s_memtime via clock64()\",\n \"note\": \"simd_cycles_per_inst = slowest wave's cycles / (instructions x waves on its SIMD) = SIMD issue time per wave64 instruction (waves do not share a SIMD evenly: use the slowest, not the mean). waves_per_simd_observed = [min, max] waves per SIMD from HW_ID\",\n \"results\": [\n",
          pr.name, pr.gcnArchName, ncu, clk);
+  if (mul_only) {
+    run<K_ADD_U32, false>(1, 2, ncu, d_cyc, d_sink, d_hw, false); run<K_MUL_LO_U32, false>(1, 2, ncu, d_cyc, d_sink, d_hw, false);
+    run<K_MUL_U32_U24, false>(1, 2, ncu, d_cyc, d_sink, d_hw, false); run<K_MAD_U32_U24, false>(1, 2, ncu, d_cyc, d_sink, d_hw, true);
+    printf("]}\n");
+    return 0;
+  }
   both<K_ADD_U32>(ncu, d_cyc, d_sink, d_hw, false); both<K_ADD_E64>(ncu, d_cyc, d_sink, d_hw, false, false); both<K_ADD_LIT>(ncu, d_cyc, d_sink, d_hw, false, false);
   both<K_AND_E32>(ncu, d_cyc, d_sink, d_hw, false, false); both<K_MAX_I16_E32>(ncu, d_cyc, d_sink, d_hw, false, false); both<K_HALF_MIX>(ncu, d_cyc, d_sink, d_hw, false, false);
   both<K_PK_ADD>(ncu, d_cyc, d_sink, d_hw, false); both<K_PK_MAX>(ncu, d_cyc, d_sink, d_hw, false, false); both<K_PERM>(ncu, d_cyc, d_sink, d_hw, false);
