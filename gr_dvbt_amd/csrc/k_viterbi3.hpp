@@ -38,8 +38,10 @@
 //    and differ in bit 6, whichever wins carries the right bits 8 and 7 into the next step, where bit 7 decides and the stale
 //    bit 6 below it cannot; and so on.  The deltas have zeros in bits 8:0, so the adds leave the three bits alone.  A window of 8
 //    steps re-arms after steps 3, 6 (with the stamp), 7 and 8 (with the origin of the next window): 4 v_and_or instead of 8.
-// Per step and VGPR (two cells): v_perm (both branch-metric deltas from ONE word of four class deltas), pk_add,
-// pk_sub, exchange, pk_max, and on every second step a v_and_or: 2.75 instructions per cell.
+// Per step (two VGPRs, four cells): ONE v_perm (the branch-metric deltas of all four cells out of one word of four class deltas: register 1 has register 0's deltas, their
+// negatives, or -- phases 1 and 5, where a register's two cells share a class -- the other half of the permuted word, read through op_sel; v3_step), and per VGPR pk_add,
+// pk_sub, the exchange (a v_mov_dpp at four of the six phases, free at the other two), pk_max, and on every second step a v_and_or: 9.33 instructions per step, 2.33 per cell
+// (the second v_perm that phases 1 and 5 issued until round 11 made it 9.67).
 //
 // The instruction budget, as compiled (tools/vit_window_count.py on the device assembly; tests/test_viterbi_isa_budget.py holds it): a window is 77 VALU instructions for
 // its eight steps, 1 for the path-byte word and 10.8 for its end (key and argmax 10, the renormalisation's 5 every sixth window; 12.5 = 90.5 in all while it ran every second) = 88.8, plus its address arithmetic; a traceback hop is 2 per chain (one row back, one v_bfi).  A block of
@@ -47,7 +49,8 @@
 // 97.6 per window (106.8 before the ring became one array of the workgroup; 95.7 while the calls' bytes were assembled behind the block), the other blocks of twelve 91.5 and
 // 87.9 (94.0 as a loop of six), staging and the chains' start ~240 per block (~270 with the output before round 8): 2,458 instructions per block of 24 windows measured
 // (SQ_INSTS_VALU; 2,472 in round 7, 2,727 before it).  Since rounds 9 and 10 (the shortcut below; the renormalisation every sixth window): the hop-free windows 0-11 86.3 per window, with
-// hops 94.7, windows 12-23 90.2 (88.0 / 96.3 / 91.8 with the renormalisation every second window; tests/test_viterbi_isa_renorm.py holds them), 2,361 per block measured (2,400 in round 9).  Every stamp is one v_and_or_b32 (the lane constants are kept opaque, v3_init_lane).
+// hops 94.7, windows 12-23 90.2 (88.0 / 96.3 / 91.8 with the renormalisation every second window; tests/test_viterbi_isa_renorm.py holds them), 2,361 per block measured (2,400 in round 9).  Since round 11 (one v_perm per step at every phase: 74.7 for a window's eight steps instead of 77.3; the ring's row masked once per
+// group of eight windows instead of once per window, v3_fwd_window): 83.7 / 92.0 / 85.8 (tests/test_viterbi_isa_perm.py), 2,275 per block measured.  Every stamp is one v_and_or_b32 (the lane constants are kept opaque, v3_init_lane).
 // What the count alone did not buy, the order of the LDS reads did: a hop's read and its use stand three and five steps apart (v3_fwd_window), and a window's
 // step words are loaded one window ahead (v3_fwd_six) -- the wavefront, one of two on its SIMD, no longer waits out the LDS latency 70 times per block.  The same holds around
 // the windows since round 8: staging computes a lane's twelve table indices first, issues the twelve look-ups back to back behind one wait and stores the words as three
@@ -147,9 +150,26 @@ template <int CTRL> __device__ __forceinline__ int dppb(int v) { return __builti
 __device__ __forceinline__ int vconst(int c) { int x; asm("v_mov_b32 %0, %1" : "=v"(x) : "s"(c)); return x; }
 // max of a's halves with b's halves SWAPPED (the half exchange of phase 1 rides on the op_sel of the VOP3P encoding)
 __device__ __forceinline__ int pk_max_swap(int a, int b) { int r; asm("v_pk_max_i16 %0, %1, %2 op_sel:[0,1] op_sel_hi:[1,0]" : "=v"(r) : "v"(a), "v"(b)); return r; }
+// a's halves plus / minus ONE half of b, the same for both (HI: b's high half, else its low one): the phases 1 and 5 keep the deltas of the two registers in the two halves of
+// one word (v3_step).  No clamp; not volatile, the scheduler moves them like the compiler's own packed adds
+template <bool HI> __device__ __forceinline__ int pk_add_half(int a, int b)
+{
+  int r;
+  if (HI) asm("v_pk_add_u16 %0, %1, %2 op_sel:[0,1] op_sel_hi:[1,1]" : "=v"(r) : "v"(a), "v"(b));
+  else asm("v_pk_add_u16 %0, %1, %2 op_sel:[0,0] op_sel_hi:[1,0]" : "=v"(r) : "v"(a), "v"(b));
+  return r;
+}
+template <bool HI> __device__ __forceinline__ int pk_sub_half(int a, int b)
+{
+  int r;
+  if (HI) asm("v_pk_sub_i16 %0, %1, %2 op_sel:[0,1] op_sel_hi:[1,1]" : "=v"(r) : "v"(a), "v"(b));
+  else asm("v_pk_sub_i16 %0, %1, %2 op_sel:[0,0] op_sel_hi:[1,0]" : "=v"(r) : "v"(a), "v"(b));
+  return r;
+}
 
 struct V3Lane {
-  unsigned sel[6][2];   // v_perm selectors: [0, d(class of lo cell), 0, d(class of hi cell)] out of the step word
+  unsigned sel[6];      // v_perm selectors out of the step word: [0, d(class of register 0's lo cell), 0, d(class of its hi cell)], register 1 lives on the same word (v3_step);
+                        // at the phases 1 and 5, where a register's halves share their class: [0, d(class of register 0), 0, d(class of register 1)]
   int bias8[6][2];      // tie-break bit of phase P at bit 8 of both halves (1 = the cell holds an upper state at that phase)
   int kc[3][2];         // (63 - state of the two cells) | (the cell holds a LOWER state) << 8, at window ends (phase 0,2,4)
   int org[2];           // storage index of the two cells, at the path-byte position (bits 5:0)
@@ -166,21 +186,25 @@ __device__ __forceinline__ int v3_z_of_cell(int c) { return v3_phys(c & 15) * 4 
 
 // 1 when cell (r, h, a) holds an upper state (state bit 5 set) at phase P: the state is rotl6(cell, P), its bit 5 is cell bit (5 - P)
 __device__ __forceinline__ int v3_upper(int P, int r, int h, int a) { const int c = (r << 5) | (h << 4) | a; return (c >> (5 - P)) & 1; }
+// label class of cell (r, h, a) at phase P = the byte of the step word its delta comes from
+__device__ __forceinline__ unsigned v3_class(int P, int r, int h, int a)
+{
+  const int c = (r << 5) | (h << 4) | a, i = rotl6(c, P) & 31;
+  const int c0 = ((i >> 2) ^ (i >> 1) ^ i) & 1;                       // parity(2i & 0x4f)
+  const int c1 = ((i >> 4) ^ (i >> 2) ^ (i >> 1)) & 1;                // parity(2i & 0x6d)
+  return (unsigned)(c0 | (c1 << 1));
+}
 __device__ inline void v3_init_lane(int pl, V3Lane &L)
 {
   const int a = v3_log(pl);
+  for (int P = 0; P < 6; P++) {
+    // the two bytes of the selector: register 0's two halves -- or, at the phases 1 and 5, the two registers: cell bit 4 (the half) sits on state bit 5 resp. 3 there, which
+    // neither parity reads, so a register's halves share their class, and register 1's is register 0's ^ 1 resp. ^ 2 (tests/test_viterbi_opsel_model.py)
+    const bool regs = P == 1 || P == 5;
+    L.sel[P] = 0x0c | (v3_class(P, 0, 0, a) << 8) | (0x0cu << 16) | ((regs ? v3_class(P, 1, 0, a) : v3_class(P, 0, 1, a)) << 24);
+  }
   for (int r = 0; r < 2; r++) {
-    for (int P = 0; P < 6; P++) {
-      unsigned idx[2];
-      for (int h = 0; h < 2; h++) {
-        const int c = (r << 5) | (h << 4) | a, i = rotl6(c, P) & 31;
-        const int c0 = ((i >> 2) ^ (i >> 1) ^ i) & 1;                 // parity(2i & 0x4f)
-        const int c1 = ((i >> 4) ^ (i >> 2) ^ (i >> 1)) & 1;          // parity(2i & 0x6d)
-        idx[h] = (unsigned)(c0 | (c1 << 1));                          // byte of the step word = label class
-      }
-      L.sel[P][r] = 0x0c | (idx[0] << 8) | (0x0cu << 16) | (idx[1] << 24);
-      L.bias8[P][r] = (v3_upper(P, r, 0, a) << 8) | (v3_upper(P, r, 1, a) << 24);
-    }
+    for (int P = 0; P < 6; P++) L.bias8[P][r] = (v3_upper(P, r, 0, a) << 8) | (v3_upper(P, r, 1, a) << 24);
     L.org[r] = (pl * 4 + 2 * r) | ((pl * 4 + 2 * r + 1) << 16);     // bits 5:0 of the path byte
     for (int e = 0; e < 3; e++) {
       const int P0 = 2 * e;
@@ -211,14 +235,17 @@ template <int P, int ST> __device__ __forceinline__ void v3_step(int (&v)[2], un
   int X[2], Y[2], mx[2];
   // The label class of a cell depends on bits 0,1,2,4 of its state (parity taps 0x4f, 0x6d without the MSB).  The
   // VGPR index is cell bit 5 = state bit (5+P)%6: at phases 0 and 4 (state bits 5, 3) both VGPRs have the same
-  // deltas, at phases 2 and 3 (state bits 1, 2: both parities flip) VGPR 1 has the negated ones.
-  const int D0 = (int)__builtin_amdgcn_perm(0u, W, L.sel[P][0]);
-  X[0] = pk_add(v[0], D0); Y[0] = pk_sub(v[0], D0);
-  if (P == 0 || P == 4) { X[1] = pk_add(v[1], D0); Y[1] = pk_sub(v[1], D0); }
-  else if (P == 2 || P == 3) { X[1] = pk_sub(v[1], D0); Y[1] = pk_add(v[1], D0); }
-  else {
-    const int D1 = (int)__builtin_amdgcn_perm(0u, W, L.sel[P][1]);
-    X[1] = pk_add(v[1], D1); Y[1] = pk_sub(v[1], D1);
+  // deltas, at phases 2 and 3 (state bits 1, 2: both parities flip) VGPR 1 has the negated ones.  At phases 1 and 5 (state bits 0, 4: one parity flips) VGPR 1 has
+  // another class, but there the two cells of a VGPR share theirs (the half, cell bit 4, is state bit 5 resp. 3): the one permute delivers [0, d(VGPR 0), 0, d(VGPR 1)]
+  // and each VGPR's add and subtract read their half of it for both cells (op_sel) -- one v_perm per step at every phase.
+  const int D0 = (int)__builtin_amdgcn_perm(0u, W, L.sel[P]);
+  if (P == 1 || P == 5) {
+    X[0] = pk_add_half<false>(v[0], D0); Y[0] = pk_sub_half<false>(v[0], D0);
+    X[1] = pk_add_half<true>(v[1], D0); Y[1] = pk_sub_half<true>(v[1], D0);
+  } else {
+    X[0] = pk_add(v[0], D0); Y[0] = pk_sub(v[0], D0);
+    if (P == 0 || P == 4) { X[1] = pk_add(v[1], D0); Y[1] = pk_sub(v[1], D0); }
+    else { X[1] = pk_sub(v[1], D0); Y[1] = pk_add(v[1], D0); }
   }
   if (P == 0) { mx[0] = pk_max(X[0], Y[1]); mx[1] = pk_max(X[1], Y[0]); }
   else if (P == 1) { mx[0] = pk_max_swap(X[0], Y[0]); mx[1] = pk_max_swap(X[1], Y[1]); }
@@ -332,7 +359,7 @@ template <bool MASKED> __device__ __forceinline__ void v3_trace_store(const V3Tr
 }
 __device__ __forceinline__ void v3_trace_out(const V3Trace &T, const unsigned char *tab, uint8_t *outb) { unsigned t[2]; v3_trace_read(T, tab, t); v3_trace_store<false>(T, t, outb); }
 
-// window j0 + V6 of a decoder (j0 % 6 == 0): it starts at phase (8 V6) % 6 = 0,2,4,0,2,4; the last window of the six
+// window jb + W0 + V6 of a decoder (jb: the block's first window, W0 = 0, 6, 12, 18 the group of six): it starts at phase (8 V6) % 6 = 0,2,4,0,2,4; the last window of the six
 // (V6 == V3_RENORM_EVERY - 1) renormalises.  HOPS: two traceback hops of the previous block's calls ride along (their LDS latency
 // hides under the add-compare-select work).
 // Which hops exist is a compile-time fact (HOP0 + 2 V6 (+1) < NTB - 1 with NTB = ntraceback, a template parameter of the
@@ -347,8 +374,8 @@ __device__ __forceinline__ void v3_load_words(const unsigned *wp_, unsigned (&W)
 // W = the window's eight step words, already in registers; PREF: the next window's (they follow in wrow) are loaded into Wn at the start of this one, a window ahead of their use
 // The read of the chains' last path byte takes the slot of the hop that would follow the last one (FINA / FINB), and the calls' bytes are assembled and written where that hop
 // would be merged, three or five steps later (outb: v3_trace_store)
-template <int V6, bool HOPS, int HOP0, int NTB, int NW, bool PREF> __device__ __forceinline__ void v3_fwd_window(int (&v)[2], const V3Lane &L, const unsigned *wrow, unsigned char *tab, unsigned char *tabw,
-                                                                                           unsigned char *bests, int j0, int dd, int pl, V3Trace &T, unsigned (&W)[8], unsigned (&Wn)[8], uint8_t *outb)
+template <int V6, int W0, bool HOPS, int HOP0, int NTB, int NW, bool PREF> __device__ __forceinline__ void v3_fwd_window(int (&v)[2], const V3Lane &L, const unsigned *wrow, unsigned char *tab, unsigned char *tabw,
+                                                                                           unsigned char *bests, int jb, int dd, int pl, V3Trace &T, unsigned (&W)[8], unsigned (&Wn)[8], uint8_t *outb)
 {
   // a window's two hops are dependent LDS reads: the first is issued here and used behind the window's 3rd step, where the second is issued, which is used behind the last step
   // (the compiler keeps the source order: written as read + use in one place they end up 1 to 5 instructions apart, and the wavefront waits out the LDS latency 46 times a block)
@@ -357,9 +384,14 @@ template <int V6, bool HOPS, int HOP0, int NTB, int NW, bool PREF> __device__ __
   unsigned th[2], tout[2];
   if (HOPA) v3_hop_read(T, tab, th);
   if (FINA) v3_trace_read(T, tab, tout);
-  const int jr = (j0 + V6) & (V3_RINGW - 1);
+  // The window's row of the ring.  A block starts at a multiple of eight windows and the ring holds a multiple of eight, so the ring can wrap only between two groups of eight
+  // windows of the block: one masked row per group, the window's place in its group a constant (an immediate offset of the ds_write).  Written as (jb + WB) & (V3_RINGW - 1) the
+  // compiler masks every window behind the block's eighth on its own and pays two address instructions per window (the path-byte word's, the best state's)
+  constexpr int WB = W0 + V6;
+  static_assert(V3_BLK % 8 == 0 && V3_RINGW % 8 == 0, "jb % 8 == 0: the ring's wrap falls between two groups of eight windows");
+  const int jr = ((jb + (WB & ~7)) & (V3_RINGW - 1)) + (WB & 7);
 #if V3_EXP & 256
-  for (int i = 0; i < 8; i++) { W[i] = (unsigned)(j0 * 0x01010101 + i * 0x00020406 + pl); asm volatile("" : "+v"(W[i])); }   // no LDS read in the loop
+  for (int i = 0; i < 8; i++) { W[i] = (unsigned)((jb + W0) * 0x01010101 + i * 0x00020406 + pl); asm volatile("" : "+v"(W[i])); }   // no LDS read in the loop
 #else
   if (PREF) v3_load_words(wrow + (V6 + 1) * 8, Wn);
 #endif
@@ -387,12 +419,12 @@ template <int V6, bool HOPS, int HOP0, int NTB, int NW, bool PREF> __device__ __
 }
 static_assert(V3_RENORM_EVERY == 6, "v3_fwd_six is the group of windows that ends in a renormalisation (V6 = 0..5)");
 // six windows; Wa arrives with the first window's step words and leaves with those of the window behind the six (MORE: there is one in this block)
-template <bool HOPS, int HOP0, int NTB, int NW, bool MORE> __device__ __forceinline__ void v3_fwd_six(int (&v)[2], const V3Lane &L, const unsigned *wrow, unsigned char *tab, unsigned char *tabw,
-                                                                                  unsigned char *bests, int j0, int dd, int pl, V3Trace &T, unsigned (&Wa)[8], unsigned (&Wb)[8], uint8_t *outb)
+template <int W0, bool HOPS, int HOP0, int NTB, int NW, bool MORE> __device__ __forceinline__ void v3_fwd_six(int (&v)[2], const V3Lane &L, const unsigned *wrow, unsigned char *tab, unsigned char *tabw,
+                                                                                  unsigned char *bests, int jb, int dd, int pl, V3Trace &T, unsigned (&Wa)[8], unsigned (&Wb)[8], uint8_t *outb)
 {
-  v3_fwd_window<0, HOPS, HOP0, NTB, NW, true>(v, L, wrow, tab, tabw, bests, j0, dd, pl, T, Wa, Wb, outb); v3_fwd_window<1, HOPS, HOP0, NTB, NW, true>(v, L, wrow, tab, tabw, bests, j0, dd, pl, T, Wb, Wa, outb);
-  v3_fwd_window<2, HOPS, HOP0, NTB, NW, true>(v, L, wrow, tab, tabw, bests, j0, dd, pl, T, Wa, Wb, outb); v3_fwd_window<3, HOPS, HOP0, NTB, NW, true>(v, L, wrow, tab, tabw, bests, j0, dd, pl, T, Wb, Wa, outb);
-  v3_fwd_window<4, HOPS, HOP0, NTB, NW, true>(v, L, wrow, tab, tabw, bests, j0, dd, pl, T, Wa, Wb, outb); v3_fwd_window<5, HOPS, HOP0, NTB, NW, MORE>(v, L, wrow, tab, tabw, bests, j0, dd, pl, T, Wb, Wa, outb);
+  v3_fwd_window<0, W0, HOPS, HOP0, NTB, NW, true>(v, L, wrow, tab, tabw, bests, jb, dd, pl, T, Wa, Wb, outb); v3_fwd_window<1, W0, HOPS, HOP0, NTB, NW, true>(v, L, wrow, tab, tabw, bests, jb, dd, pl, T, Wb, Wa, outb);
+  v3_fwd_window<2, W0, HOPS, HOP0, NTB, NW, true>(v, L, wrow, tab, tabw, bests, jb, dd, pl, T, Wa, Wb, outb); v3_fwd_window<3, W0, HOPS, HOP0, NTB, NW, true>(v, L, wrow, tab, tabw, bests, jb, dd, pl, T, Wb, Wa, outb);
+  v3_fwd_window<4, W0, HOPS, HOP0, NTB, NW, true>(v, L, wrow, tab, tabw, bests, jb, dd, pl, T, Wa, Wb, outb); v3_fwd_window<5, W0, HOPS, HOP0, NTB, NW, MORE>(v, L, wrow, tab, tabw, bests, jb, dd, pl, T, Wb, Wa, outb);
 }
 
 // A chunk = vp.chunk_bytes decoded bytes; it is decoded by an independent decoder that starts `warm` windows early
@@ -710,16 +742,16 @@ __device__ __forceinline__ void v3_decode(const uint8_t *__restrict__ in, uint8_
     unsigned Wa[8], Wb[8];                                         // the step words of the current and of the next window
     v3_load_words(wrow, Wa);
     if (tr) {
-      v3_fwd_six<true, 0, NTB, NW, true>(v, L, wrow, tab, tabw, bests, jb, dd, pl, T, Wa, Wb, outb);
-      v3_fwd_six<true, 12, NTB, NW, true>(v, L, wrow + 48, tab, tabw, bests, jb + 6, dd, pl, T, Wa, Wb, outb);
+      v3_fwd_six<0, true, 0, NTB, NW, true>(v, L, wrow, tab, tabw, bests, jb, dd, pl, T, Wa, Wb, outb);
+      v3_fwd_six<6, true, 12, NTB, NW, true>(v, L, wrow + 48, tab, tabw, bests, jb, dd, pl, T, Wa, Wb, outb);
     } else {
-      v3_fwd_six<false, 0, NTB, NW, true>(v, L, wrow, tab, tabw, bests, jb, dd, pl, T, Wa, Wb, outb);
-      v3_fwd_six<false, 0, NTB, NW, true>(v, L, wrow + 48, tab, tabw, bests, jb + 6, dd, pl, T, Wa, Wb, outb);
+      v3_fwd_six<0, false, 0, NTB, NW, true>(v, L, wrow, tab, tabw, bests, jb, dd, pl, T, Wa, Wb, outb);
+      v3_fwd_six<6, false, 0, NTB, NW, true>(v, L, wrow + 48, tab, tabw, bests, jb, dd, pl, T, Wa, Wb, outb);
     }
     static_assert(V3_BLK == 24, "the second half of the block is written out: two groups of six windows, straight-line like the first half");
     static_assert(NTB - 1 < 24, "the chains' last read takes a hop slot of the first twelve windows");
-    v3_fwd_six<false, 0, NTB, NW, true>(v, L, wrow + 96, tab, tabw, bests, jb + 12, dd, pl, T, Wa, Wb, outb);
-    v3_fwd_six<false, 0, NTB, NW, false>(v, L, wrow + 144, tab, tabw, bests, jb + 18, dd, pl, T, Wa, Wb, outb);
+    v3_fwd_six<12, false, 0, NTB, NW, true>(v, L, wrow + 96, tab, tabw, bests, jb, dd, pl, T, Wa, Wb, outb);
+    v3_fwd_six<18, false, 0, NTB, NW, false>(v, L, wrow + 144, tab, tabw, bests, jb, dd, pl, T, Wa, Wb, outb);
   }
   // the last block's calls
   __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
