@@ -98,6 +98,24 @@ class RxCut(C.Structure):
     _fields_ = [("stream_symbol_offset", C.c_int64), ("start_delay_symbols", C.c_int32), ("descr_call_phase", C.c_int32)]
 
 
+class SymMetaRec(C.Structure):
+    """dvbt_sym_meta: what the acquisition leaves per symbol (test hook dvbt_debug_acquire)"""
+    _fields_ = [("cp_start", C.c_int32), ("sw", C.c_int32), ("eps", C.c_float), ("ph_base", C.c_float), ("incA", C.c_double), ("incB", C.c_double)]
+
+
+class AcquireReport(C.Structure):
+    """dvbt_acquire_report"""
+    _fields_ = [("status", C.c_int32), ("call0", C.c_int32), ("cp_start0", C.c_int32), ("n_symbols", C.c_int32),
+                ("avg", C.c_float), ("eps_init", C.c_float), ("avg_lost", C.c_float), ("small_viol", C.c_int32), ("drift_known_off", C.c_int32),
+                ("changed", C.c_int32 * 4), ("need_seq", C.c_int32), ("need_heavy", C.c_int32), ("ncalls", C.c_int32), ("cap_symbols", C.c_int32),
+                ("small_passes", C.c_int32), ("general_passes", C.c_int32), ("reserved", C.c_int32)]
+
+
+# dvbt_debug_acquire's arguments (the tests set them on the loaded library: an A/B build of an older commit has no such entry)
+ACQUIRE_ARGTYPES = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int,
+                    C.POINTER(AcquireReport), C.c_void_p, C.c_int] + [C.c_void_p] * 7
+
+
 class Dims(C.Structure):
     _fields_ = [("fft_length", C.c_int), ("cp_length", C.c_int), ("Kmax", C.c_int), ("payload_length", C.c_int),
                 ("zeros_on_left", C.c_int), ("m", C.c_int), ("cr_k", C.c_int), ("cr_n", C.c_int),

@@ -745,6 +745,54 @@ static int launch_frames(dvbt_rx *h, hipStream_t s, const FrontParams &fp, int C
   return DVBT_OK;
 }
 
+// the acquisition of one lock period (enqueue and dvbt_debug_acquire both call it): the initial search over `init_tries` windows, then either acq_small_kernel (an
+// acquisition-only pass of at most ACQ_SMALL_MAX_CALLS calls, unless no_small) or the general kernels: anchors, centres, the tracking metric, the Jacobi placement,
+// its bookkeeping and the two sequential walks behind their flag words.  reset_tps: the search's reset also clears the pilot engine's state.  force (test hook only,
+// 0 in enqueue): 1 = need_seq is set behind acq_finalize_kernel, so the light walk runs on a period the placement settled; 2 = need_heavy too
+static int launch_acquisition(dvbt_rx *h, hipStream_t s, const float2 *iq, const FrontParams &fp, int init_tries, bool acq_only, bool no_small, bool reset_tps,
+                              bool use_carry, float carry_avg, int force, unsigned char *flags_out = nullptr)
+{
+  const Dims &d = h->d;
+  const int C = fp.ncalls, N = d.N;
+  const AcqState *carry = nullptr;
+  int tries = C < init_tries ? C : init_tries;
+  // initial search: the metric of all `tries` windows in one launch (32 workgroups per window: four windows cost the latency of one), then ONE launch of the
+  // state machine, which examines them in order and stops at the first peak -- window 0 on a stream that is there, so the later windows' metric is rarely
+  // looked at; computing it unasked costs nothing on an otherwise idle device and saves two launches per lock period
+  // (the FSM launch also clears the trackers' flag words, the symbol kernel's ticket and, for a period that starts the pilot engine afresh, its state)
+  hipLaunchKernelGGL(acq_metric_kernel, dim3((N + 255) / 256, tries), dim3(256), 0, s, iq, fp, (const RxState *)h->st, 0, h->g_init, h->l_init, 0);
+  const AcqReset rz = {h->trk_flags, h->sym_ticket, !reset_tps ? nullptr : reinterpret_cast<int *>(h->tps_state.get()),(int)(sizeof(TpsState) / 4),
+                       carry_avg, use_carry ? 1 : 0, flags_out};
+  hipLaunchKernelGGL(acq_init_fsm_kernel, dim3(1), dim3(1024), (size_t)N * 5, s, fp, h->st, (const float2 *)h->g_init, (const float *)h->l_init, carry, 0, tries, rz);
+  if (acq_only && !no_small && C <= ACQ_SMALL_MAX_CALLS) {
+    // the lock-period walk's short look-ahead windows: everything behind the initial search in one launch, work in proportion to the symbols the lock holds
+    const int cpc = acq_small_cpc(d.cp);
+    h->n_small++;
+    hipLaunchKernelGGL(acq_small_kernel, dim3(1), dim3(64 * (1 + cpc / 2)), (size_t)cpc * 2 * (d.cp + 2 * ACQ_R) * sizeof(float2), s, iq, fp, h->st, h->meta, cpc, h->drift.flags);
+  } else {
+  if (acq_only) h->n_general++;
+  {   // where the tracking metric is computed: CP position predicted per call from coarse estimates every ACQ_ANCHOR calls (sample-clock drift)
+    const int n_anchors = (C - 1) / ACQ_ANCHOR;
+    if (n_anchors > 0) hipLaunchKernelGGL(acq_anchor_kernel, dim3(n_anchors), dim3(1024), acq_anchor_lds_bytes(N, d.cp), s, iq, fp, (const RxState *)h->st, h->anchor_pos);
+    hipLaunchKernelGGL(acq_centre_kernel, dim3((C + 1023) / 1024), dim3(1024), 0, s, fp, (const RxState *)h->st, (const int *)h->anchor_pos, n_anchors, h->centre);
+  }
+  hipLaunchKernelGGL(acq_track_metric_kernel, dim3((C + ACQ_TM_CALLS - 1) / ACQ_TM_CALLS), dim3(256), 0, s, iq, fp, (const RxState *)h->st, (const int *)h->centre, h->g_trk, h->l_trk);
+  constexpr int kIters = TRK_ROUNDS;            // Jacobi iterations of the window placement (one launch); flags[kIters] = need_seq
+  hipLaunchKernelGGL(acq_track_fused_kernel, dim3((C + TRK_OWN - 1) / TRK_OWN), dim3(256), 0, s, fp, (const RxState *)h->st, (const float2 *)h->g_trk,
+                     (const float *)h->l_trk, h->trk_cp_a, h->trk_eps, h->trk_flags, (const int *)h->centre);
+  hipLaunchKernelGGL(acq_finalize_kernel, dim3((C + 1023) / 1024), dim3(1024), 0, s, fp, h->st, (const int *)h->trk_cp_a, (const float *)h->trk_eps,
+                     (const int *)h->trk_flags, kIters - 1, h->meta, h->trk_flags + kIters, (const float *)h->l_trk, (const int *)h->centre);
+  // not settled: the sequential walk, positions and epsilon only (flags[kIters] = need_seq); flags[kIters + 1] = need_heavy, which it raises for a period
+  // outside the closed form of the phase -- that one goes through the float-faithful tracker of the block API
+  if (force) HIPCHK(hipMemsetD32Async((hipDeviceptr_t)(h->trk_flags + kIters), 1, force >= 2 ? 2 : 1, s));
+  hipLaunchKernelGGL(acq_track_light_kernel, dim3(1), dim3(64), 0, s, fp, h->st, (const float2 *)h->g_trk, (const float *)h->l_trk, h->meta,
+                     (const int *)(h->trk_flags + kIters), h->trk_flags + kIters + 1, (const int *)h->centre, iq);
+  hipLaunchKernelGGL(acq_track_kernel, dim3(1), dim3(64), 0, s, fp, h->st, (const float2 *)h->g_trk, (const float *)h->l_trk, h->meta,
+                     (const int *)(h->trk_flags + kIters + 1), (AcqState *)nullptr, (const int *)h->centre, iq);
+  }
+  return DVBT_OK;
+}
+
 // one lock period of the chain, iq at the OFDM elementary rate
 static int enqueue(dvbt_rx *h, const float2 *iq, size_t nsamples, hipStream_t s, const EnqOpt &o = EnqOpt())
 {
@@ -771,41 +819,7 @@ static int enqueue(dvbt_rx *h, const float2 *iq, size_t nsamples, hipStream_t s,
     // what acq_init_fsm_kernel's reset would have done on top of the acq_only run's (tracker flags and the symbol ticket are still clear)
     if (!o.continuation && !o.tps_init) HIPCHK(reset_tps_state(h, s));
   } else {
-  const AcqState *carry = nullptr;
-  int tries = C < o.init_tries ? C : o.init_tries;
-  // initial search: the metric of all `tries` windows in one launch (32 workgroups per window: four windows cost the latency of one), then ONE launch of the
-  // state machine, which examines them in order and stops at the first peak -- window 0 on a stream that is there, so the later windows' metric is rarely
-  // looked at; computing it unasked costs nothing on an otherwise idle device and saves two launches per lock period
-  // (the FSM launch also clears the trackers' flag words, the symbol kernel's ticket and, for a period that starts the pilot engine afresh, its state)
-  hipLaunchKernelGGL(acq_metric_kernel, dim3((N + 255) / 256, tries), dim3(256), 0, s, iq, fp, (const RxState *)h->st, 0, h->g_init, h->l_init, 0);
-  const AcqReset rz = {h->trk_flags, h->sym_ticket, (o.acq_only || o.continuation || o.tps_init) ? nullptr : reinterpret_cast<int *>(h->tps_state.get()),(int)(sizeof(TpsState) / 4),
-                       o.carry_avg, o.use_carry ? 1 : 0};
-  hipLaunchKernelGGL(acq_init_fsm_kernel, dim3(1), dim3(1024), (size_t)N * 5, s, fp, h->st, (const float2 *)h->g_init, (const float *)h->l_init, carry, 0, tries, rz);
-  if (o.acq_only && !o.no_small && C <= ACQ_SMALL_MAX_CALLS) {
-    // the lock-period walk's short look-ahead windows: everything behind the initial search in one launch, work in proportion to the symbols the lock holds
-    const int cpc = acq_small_cpc(d.cp);
-    h->n_small++;
-    hipLaunchKernelGGL(acq_small_kernel, dim3(1), dim3(64 * (1 + cpc / 2)), (size_t)cpc * 2 * (d.cp + 2 * ACQ_R) * sizeof(float2), s, iq, fp, h->st, h->meta, cpc, h->drift.flags);
-  } else {
-  if (o.acq_only) h->n_general++;
-  {   // where the tracking metric is computed: CP position predicted per call from coarse estimates every ACQ_ANCHOR calls (sample-clock drift)
-    const int n_anchors = (C - 1) / ACQ_ANCHOR;
-    if (n_anchors > 0) hipLaunchKernelGGL(acq_anchor_kernel, dim3(n_anchors), dim3(1024), acq_anchor_lds_bytes(N, d.cp), s, iq, fp, (const RxState *)h->st, h->anchor_pos);
-    hipLaunchKernelGGL(acq_centre_kernel, dim3((C + 1023) / 1024), dim3(1024), 0, s, fp, (const RxState *)h->st, (const int *)h->anchor_pos, n_anchors, h->centre);
-  }
-  hipLaunchKernelGGL(acq_track_metric_kernel, dim3((C + ACQ_TM_CALLS - 1) / ACQ_TM_CALLS), dim3(256), 0, s, iq, fp, (const RxState *)h->st, (const int *)h->centre, h->g_trk, h->l_trk);
-  constexpr int kIters = TRK_ROUNDS;            // Jacobi iterations of the window placement (one launch); flags[kIters] = need_seq
-  hipLaunchKernelGGL(acq_track_fused_kernel, dim3((C + TRK_OWN - 1) / TRK_OWN), dim3(256), 0, s, fp, (const RxState *)h->st, (const float2 *)h->g_trk,
-                     (const float *)h->l_trk, h->trk_cp_a, h->trk_eps, h->trk_flags, (const int *)h->centre);
-  hipLaunchKernelGGL(acq_finalize_kernel, dim3((C + 1023) / 1024), dim3(1024), 0, s, fp, h->st, (const int *)h->trk_cp_a, (const float *)h->trk_eps,
-                     (const int *)h->trk_flags, kIters - 1, h->meta, h->trk_flags + kIters, (const float *)h->l_trk, (const int *)h->centre);
-  // not settled: the sequential walk, positions and epsilon only (flags[kIters] = need_seq); flags[kIters + 1] = need_heavy, which it raises for a period
-  // outside the closed form of the phase -- that one goes through the float-faithful tracker of the block API
-  hipLaunchKernelGGL(acq_track_light_kernel, dim3(1), dim3(64), 0, s, fp, h->st, (const float2 *)h->g_trk, (const float *)h->l_trk, h->meta,
-                     (const int *)(h->trk_flags + kIters), h->trk_flags + kIters + 1, (const int *)h->centre, iq);
-  hipLaunchKernelGGL(acq_track_kernel, dim3(1), dim3(64), 0, s, fp, h->st, (const float2 *)h->g_trk, (const float *)h->l_trk, h->meta,
-                     (const int *)(h->trk_flags + kIters + 1), (AcqState *)nullptr, (const int *)h->centre, iq);
-  }
+  { int r = launch_acquisition(h, s, iq, fp, o.init_tries, o.acq_only, o.no_small, !(o.acq_only || o.continuation || o.tps_init), o.use_carry, o.carry_avg, 0); if (r) return r; }
   if (o.acq_only) {
     HIPCHK(hipMemcpyAsync(h->st_host, h->st, sizeof(RxState), hipMemcpyDeviceToHost, s));
     HIPCHK(hipGetLastError());
@@ -1918,6 +1932,76 @@ extern "C" int dvbt_debug_frames(dvbt_rx *h, int n_symbols, int keep_last, const
   HIPCHK(hipMemcpy(bitdeint, h->bitdeint, C * P + 64, hipMemcpyDeviceToHost));
   if (bitdeint_lp && h->bitdeint_lp) HIPCHK(hipMemcpy(bitdeint_lp, h->bitdeint_lp, C * P + 64, hipMemcpyDeviceToHost));
   if (symdeint && h->symdeint_tap) HIPCHK(hipMemcpy(symdeint, h->symdeint_tap, C * P + 64, hipMemcpyDeviceToHost));
+  return DVBT_OK;
+}
+
+// test hook: the acquisition kernels alone on host-supplied samples (include/dvbt_hip.h).  The launches are launch_acquisition, enqueue's own, as an acquisition-only
+// pass: path 1 through acq_small_kernel, path 0 through the general kernels.  iq_host holds hist + nsamples samples, the segment begins at sample `hist` of it
+static_assert(sizeof(dvbt_sym_meta) == sizeof(SymMeta) && offsetof(dvbt_sym_meta, incB) == offsetof(SymMeta, incB), "dvbt_sym_meta is SymMeta");
+extern "C" int dvbt_debug_acquire(dvbt_rx *h, const void *iq_host, size_t nsamples, int64_t hist, int64_t avail, int init_tries, int use_carry, float carry_avg,
+                                  int path, int force, dvbt_acquire_report *rep, dvbt_sym_meta *meta, int nread, void *g_init, float *l_init, int32_t *anchor_pos,
+                                  int32_t *centre, void *g_trk, float *l_trk, uint8_t *init_flags)
+{
+  if (!iq_host || !rep || !meta) return fail(DVBT_ERR_INVALID, "null argument");
+  if (nsamples == 0 || nsamples > ((size_t)1 << 31)) return fail(DVBT_ERR_INVALID, "nsamples must lie in (0, 2^31]");
+  if (hist < 0 || hist > (1 << 20)) return fail(DVBT_ERR_INVALID, "hist must lie in [0, 2^20]");
+  if (avail <= 0 || (uint64_t)avail > nsamples) return fail(DVBT_ERR_INVALID, "avail must lie in (0, nsamples]");
+  if (init_tries < 1 || init_tries > ACQ_INIT_TRIES_MAX) return fail(DVBT_ERR_INVALID, "init_tries must lie in [1, ACQ_INIT_TRIES_MAX]");
+  if (path != 0 && path != 1) return fail(DVBT_ERR_INVALID, "unknown path");
+  if (force < 0 || force > 2 || (path == 1 && force)) return fail(DVBT_ERR_INVALID, "force must be 0, 1 or 2, and 0 on path 1");
+  if (use_carry && !std::isfinite(carry_avg)) return fail(DVBT_ERR_INVALID, "non-finite carry_avg");
+  if (nread < 0) return fail(DVBT_ERR_INVALID, "nread must not be negative");
+  { int nd = need_device(); if (nd) return nd; }                   // (a handle exists only where a device does)
+  if (!h) return fail(DVBT_ERR_INVALID, "null handle");
+  if (h->pending) return fail(DVBT_ERR_STATE, "dvbt_debug_acquire: a segment is in flight (dvbt_rx_segment_finish first)");
+  const Dims &d = h->d;
+  const size_t C = (size_t)h->max_calls, N = (size_t)d.N, W = 2 * ACQ_R;
+  if (nsamples < (size_t)(2 * d.N + d.cp + 16)) return fail(DVBT_ERR_INVALID, "segment shorter than one acquisition window");
+  FrontParams fp = h->fp;
+  fp.ncalls = (int)((nsamples - (2 * d.N + d.cp + 16)) / (d.N + d.cp) + 1);
+  if ((size_t)fp.ncalls > C) return fail(DVBT_ERR_INVALID, "more calls than the handle's buffers hold (max_samples)");
+  if (path == 1 && fp.ncalls > ACQ_SMALL_MAX_CALLS) return fail(DVBT_ERR_INVALID, "path 1: more than ACQ_SMALL_MAX_CALLS calls");
+  if ((size_t)nread > C) return fail(DVBT_ERR_INVALID, "nread beyond the symbols the handle's buffers hold");
+  fp.hist = hist; fp.keep_last = 0; fp.avail = avail;
+  HIPCHK(hipSetDevice(h->prm.device));
+  hipStream_t s = h->own_stream;
+  DevMem<float2> iq; HIPCHK(iq.alloc((size_t)hist + nsamples));
+  // every buffer the kernels write: 0xA5 up to its capacity
+  HIPCHK(hipMemsetAsync(h->g_init, 0xA5, sizeof(float2) * ACQ_INIT_TRIES_MAX * N, s)); HIPCHK(hipMemsetAsync(h->l_init, 0xA5, sizeof(float) * ACQ_INIT_TRIES_MAX * N, s));
+  HIPCHK(hipMemsetAsync(h->anchor_pos, 0xA5, sizeof(int) * (C / ACQ_ANCHOR + 4), s)); HIPCHK(hipMemsetAsync(h->centre, 0xA5, sizeof(int) * (C + 1), s));
+  HIPCHK(hipMemsetAsync(h->g_trk, 0xA5, sizeof(float2) * C * W, s)); HIPCHK(hipMemsetAsync(h->l_trk, 0xA5, sizeof(float) * C * W, s));
+  HIPCHK(hipMemsetAsync(h->trk_cp_a, 0xA5, sizeof(int) * C, s)); HIPCHK(hipMemsetAsync(h->trk_eps, 0xA5, sizeof(float) * C, s));
+  HIPCHK(hipMemsetAsync(h->meta, 0xA5, sizeof(SymMeta) * C, s)); HIPCHK(hipMemsetAsync(h->trk_flags, 0xA5, sizeof(int) * 16, s));
+  HIPCHK(hipMemsetAsync(h->st, 0xA5, sizeof(RxState), s));
+  HIPCHK(hipMemcpyAsync(iq, iq_host, sizeof(float2) * ((size_t)hist + nsamples), hipMemcpyHostToDevice, s));
+  HIPCHK(hipStreamSynchronize(s));                                 // (the source is the caller's memory)
+  DevMem<unsigned char> dflags;
+  if (init_flags) { HIPCHK(dflags.alloc((size_t)ACQ_INIT_TRIES_MAX * N)); HIPCHK(hipMemsetAsync(dflags, 0xA5, (size_t)ACQ_INIT_TRIES_MAX * N, s)); HIPCHK(hipStreamSynchronize(s)); }
+  const long long small0 = h->n_small, general0 = h->n_general;
+  { int r = launch_acquisition(h, s, (const float2 *)iq + hist, fp, init_tries, true, path == 0, false, use_carry != 0, carry_avg, force, init_flags ? (unsigned char *)dflags : nullptr); if (r) return r; }
+  HIPCHK(hipGetLastError());
+  int fl[16];
+  HIPCHK(hipMemcpyAsync(h->st_host, h->st, sizeof(RxState), hipMemcpyDeviceToHost, s));
+  HIPCHK(hipMemcpyAsync(fl, h->trk_flags, sizeof fl, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  const RxState f = *h->st_host;
+  memset(rep, 0, sizeof *rep);
+  rep->status = f.status; rep->call0 = f.call0; rep->cp_start0 = f.cp_start0; rep->n_symbols = f.n_symbols; rep->avg = f.avg; rep->eps_init = f.eps_init;
+  rep->avg_lost = f.avg_lost; rep->small_viol = f.small_viol; rep->drift_known_off = f.drift_known_off;
+  for (int i = 0; i < TRK_ROUNDS; i++) rep->changed[i] = fl[i];
+  rep->need_seq = fl[TRK_ROUNDS]; rep->need_heavy = fl[TRK_ROUNDS + 1];
+  rep->ncalls = fp.ncalls; rep->cap_symbols = (int32_t)C; rep->small_passes = (int32_t)(h->n_small - small0); rep->general_passes = (int32_t)(h->n_general - general0);
+  const size_t R = (size_t)nread, T = (size_t)(fp.ncalls < init_tries ? fp.ncalls : init_tries);
+  if (R) HIPCHK(hipMemcpy(meta, h->meta, sizeof(SymMeta) * R, hipMemcpyDeviceToHost));
+  if (g_init) HIPCHK(hipMemcpy(g_init, h->g_init, sizeof(float2) * T * N, hipMemcpyDeviceToHost));
+  if (l_init) HIPCHK(hipMemcpy(l_init, h->l_init, sizeof(float) * T * N, hipMemcpyDeviceToHost));
+  if (anchor_pos) HIPCHK(hipMemcpy(anchor_pos, h->anchor_pos, sizeof(int) * (C / ACQ_ANCHOR + 4), hipMemcpyDeviceToHost));
+  if (centre && R) HIPCHK(hipMemcpy(centre, h->centre, sizeof(int) * R, hipMemcpyDeviceToHost));
+  if (g_trk && R) HIPCHK(hipMemcpy(g_trk, h->g_trk, sizeof(float2) * R * W, hipMemcpyDeviceToHost));
+  if (l_trk && R) HIPCHK(hipMemcpy(l_trk, h->l_trk, sizeof(float) * R * W, hipMemcpyDeviceToHost));
+  if (init_flags) HIPCHK(hipMemcpy(init_flags, dflags, T * N, hipMemcpyDeviceToHost));
+  // the handle as a fresh one's: a segment that follows inherits nothing of the fill (the state block's fields and flag words the search's reset does not rewrite)
+  HIPCHK(hipMemset(h->st, 0, sizeof(RxState))); HIPCHK(hipMemset(h->trk_flags, 0, sizeof(int) * 16)); memset(h->st_host, 0, sizeof(RxState));
   return DVBT_OK;
 }
 

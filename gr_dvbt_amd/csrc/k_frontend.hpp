@@ -273,7 +273,9 @@ __global__ __launch_bounds__(256) void acq_track_metric_kernel(const float2 *__r
         const bool okc = cl < p.ncalls && cl >= st->call0;
         const int lag0c = centre[okc ? cl : st->call0] - p.R;
         const long long idx = (long long)cl * (N + cp) + lag0c - j0 - (T - 1) + i;   // sample x[lag0 + q - j] for q - (j - j0) = i - (T - 1)
-        const bool oka = okc && idx >= -p.hist && idx < p.avail, okb = okc && idx - N >= -p.hist && idx - N < p.avail;
+        // a tap whose partner x[i - N] lies in front of the stream's first sample is skipped whole, as the reference's restatement skips it (oracle/o_acq.c, ml_sync):
+        // neither its product nor its energy pair is added, and a lag at the very left of the stream is an ordinary partial sum
+        const bool okl = okc && idx - N >= -p.hist, oka = okl && idx < p.avail, okb = okl && idx - N < p.avail;
         av[k] = iq[oka ? idx : 0]; bv[k] = iq[okb ? idx - N : 0];
         if (!oka) av[k] = make_float2(0.f, 0.f);
         if (!okb) bv[k] = make_float2(0.f, 0.f);
@@ -308,7 +310,6 @@ __global__ __launch_bounds__(256) void acq_track_metric_kernel(const float2 *__r
 #pragma unroll
   for (int u = 0; u < 4; u++) {
     const int q = g4 + u, oidx = call * 2 * p.R + q;
-    if ((long long)call * (N + cp) + lag0 + q - cp + 1 - N < -p.hist) { gamma[oidx] = make_float2(0.f, 0.f); lambda[oidx] = -3.0e38f; continue; }   // before the stream's first sample
     gamma[oidx] = make_float2(gr[u], gi[u]);
     lambda[oidx] = sqrtf(gr[u] * gr[u] + gi[u] * gi[u]) - phi[u] * p.half_rho;
   }
@@ -426,9 +427,10 @@ __device__ __forceinline__ float wrap_pi(double ph)
 // reset (segment path, first launch of a lock period): the flag words of the trackers (trk_flags[0..15]; [8], [9] = first superframe-start candidate, need_seq of the
 // TPS bookkeeping), the symbol kernel's ticket and -- for a period that starts the pilot engine afresh -- its state: three memset / copy launches less
 __host__ __device__ inline int trk_flag_reset(int i) { return i == 8 ? 0x7fffffff : 0; }   // what the reset leaves in trk_flags[i]
-struct AcqReset { int *trk_flags; int *ticket; int *tps_state; int tps_state_words; float carry_avg; int has_carry; };   // carry_avg: d_avg carried in from the call that lost the previous lock
+struct AcqReset { int *trk_flags; int *ticket; int *tps_state; int tps_state_words; float carry_avg; int has_carry;   // carry_avg: d_avg carried in from the call that lost the previous lock
+                  unsigned char *flags_out; };   // test hook only (null in a segment): the rise (bit 0) / keep (bit 1) decision of every sample of every window examined, [try][N]
 __global__ __launch_bounds__(1024) void acq_init_fsm_kernel(FrontParams p, RxState *st, const float2 *gamma, const float *lambda, const AcqState *as,
-                                                          int t_begin, int t_end, AcqReset rz = AcqReset{nullptr, nullptr, nullptr, 0, 0.f, 0})
+                                                          int t_begin, int t_end, AcqReset rz = AcqReset{nullptr, nullptr, nullptr, 0, 0.f, 0, nullptr})
 {
   if (t_begin == 0) {
     if (rz.trk_flags && threadIdx.x < 16) rz.trk_flags[threadIdx.x] = trk_flag_reset((int)threadIdx.x);
@@ -475,7 +477,7 @@ __global__ __launch_bounds__(1024) void acq_init_fsm_kernel(FrontParams p, RxSta
         for (int j = 0; j < i; j++) avg = alpha * lam[j] + (1 - alpha) * avg;
       }
       unsigned f = 0;
-      if (i < N) { const float v = lam[i]; f = (v > avg * rise ? 1u : 0u) | (v > avg * fall ? 2u : 0u); flg[i] = (unsigned char)f; }
+      if (i < N) { const float v = lam[i]; f = (v > avg * rise ? 1u : 0u) | (v > avg * fall ? 2u : 0u); flg[i] = (unsigned char)f; if (rz.flags_out) rz.flags_out[(size_t)t * N + i] = (unsigned char)f; }
       else s_avg = avg;
       const unsigned long long rb = __ballot(i < N && (f & 1u));    // the wavefront's 64 samples are consecutive and 64-aligned
       if ((tid & 63) == 0 && i < N) s_rise[i >> 6] = rb;
@@ -634,22 +636,19 @@ __global__ __launch_bounds__(64) void acq_track_kernel(FrontParams p, RxState *s
       const long long lo = (long long)call * (N + cp) + cur - 8 - (cp - 1);
       __syncthreads();
       for (int t = lane; t < cp + 15; t += 64) {
-        s_xa[t] = lo + t >= -p.hist && lo + t < p.avail ? iq[lo + t] : make_float2(0.f, 0.f);
+        s_xa[t] = lo - N + t >= -p.hist && lo + t < p.avail ? iq[lo + t] : make_float2(0.f, 0.f);                // (no partner in front of the stream: the tap is skipped whole)
         s_xb[t] = lo - N + t >= -p.hist && lo - N + t < p.avail ? iq[lo - N + t] : make_float2(0.f, 0.f);
       }
       __syncthreads();
       if (lane < 16) {
         const int lag = cur - 8 + lane;
         float gr = 0.f, gi = 0.f, phi = 0.f;
-        if ((long long)call * (N + cp) + lag - cp + 1 - N < -p.hist) { s_lam[lane] = -3.0e38f; s_gam[lane] = make_float2(0.f, 0.f); }
-        else {
-          const float2 *xa = s_xa + (cp - 1) + lane, *xb = s_xb + (cp - 1) + lane;
-          for (int j = 0; j < cp; j++) {                            // the expressions and the order of acq_track_metric_kernel
-            const float2 a = xa[-j], b = xb[-j];
-            gr += a.x * b.x + a.y * b.y; gi += a.y * b.x - a.x * b.y; phi += (a.x * a.x + a.y * a.y) + (b.x * b.x + b.y * b.y);
-          }
-          s_gam[lane] = make_float2(gr, gi); s_lam[lane] = sqrtf(gr * gr + gi * gi) - phi * p.half_rho;
+        const float2 *xa = s_xa + (cp - 1) + lane, *xb = s_xb + (cp - 1) + lane;
+        for (int j = 0; j < cp; j++) {                              // the expressions and the order of acq_track_metric_kernel
+          const float2 a = xa[-j], b = xb[-j];
+          gr += a.x * b.x + a.y * b.y; gi += a.y * b.x - a.x * b.y; phi += (a.x * a.x + a.y * a.y) + (b.x * b.x + b.y * b.y);
         }
+        s_gam[lane] = make_float2(gr, gi); s_lam[lane] = sqrtf(gr * gr + gi * gi) - phi * p.half_rho;
       }
       __syncthreads();
       rel0 = 0;
@@ -716,22 +715,19 @@ __global__ __launch_bounds__(64) void acq_track_light_kernel(FrontParams p, RxSt
       const long long lo = (long long)call * L + cur - 8 - (cp - 1);
       __syncthreads();
       for (int t = lane; t < cp + 15; t += 64) {
-        s_xa[t] = lo + t >= -p.hist && lo + t < p.avail ? iq[lo + t] : make_float2(0.f, 0.f);
+        s_xa[t] = lo - N + t >= -p.hist && lo + t < p.avail ? iq[lo + t] : make_float2(0.f, 0.f);                // (no partner in front of the stream: the tap is skipped whole)
         s_xb[t] = lo - N + t >= -p.hist && lo - N + t < p.avail ? iq[lo - N + t] : make_float2(0.f, 0.f);
       }
       __syncthreads();
       if (lane < 16) {
         const int lag = cur - 8 + lane;
         float gr = 0.f, gi = 0.f, phi = 0.f;
-        if ((long long)call * L + lag - cp + 1 - N < -p.hist) { s_lam[lane] = -3.0e38f; s_gam[lane] = make_float2(0.f, 0.f); }
-        else {
-          const float2 *xa = s_xa + (cp - 1) + lane, *xb = s_xb + (cp - 1) + lane;
-          for (int j = 0; j < cp; j++) {                            // the expressions and the order of acq_track_metric_kernel
-            const float2 a = xa[-j], b = xb[-j];
-            gr += a.x * b.x + a.y * b.y; gi += a.y * b.x - a.x * b.y; phi += (a.x * a.x + a.y * a.y) + (b.x * b.x + b.y * b.y);
-          }
-          s_gam[lane] = make_float2(gr, gi); s_lam[lane] = sqrtf(gr * gr + gi * gi) - phi * p.half_rho;
+        const float2 *xa = s_xa + (cp - 1) + lane, *xb = s_xb + (cp - 1) + lane;
+        for (int j = 0; j < cp; j++) {                              // the expressions and the order of acq_track_metric_kernel
+          const float2 a = xa[-j], b = xb[-j];
+          gr += a.x * b.x + a.y * b.y; gi += a.y * b.x - a.x * b.y; phi += (a.x * a.x + a.y * a.y) + (b.x * b.x + b.y * b.y);
         }
+        s_gam[lane] = make_float2(gr, gi); s_lam[lane] = sqrtf(gr * gr + gi * gi) - phi * p.half_rho;
       }
       __syncthreads();
       rel0 = 0;
@@ -798,7 +794,7 @@ __global__ __launch_bounds__(576) void acq_small_kernel(const float2 *__restrict
 #pragma unroll
       for (int u = 0; u < 5; u++) {
         const int t = t0 + 32 * u; const bool in = t < span;
-        ra[u] = in && lo + t >= -p.hist && lo + t < p.avail ? iq[lo + t] : make_float2(0.f, 0.f);
+        ra[u] = in && lo - N + t >= -p.hist && lo + t < p.avail ? iq[lo + t] : make_float2(0.f, 0.f);             // (no partner in front of the stream: the tap is skipped whole)
         rb[u] = in && lo - N + t >= -p.hist && lo - N + t < p.avail ? iq[lo - N + t] : make_float2(0.f, 0.f);
       }
 #pragma unroll
@@ -823,9 +819,8 @@ __global__ __launch_bounds__(576) void acq_small_kernel(const float2 *__restrict
       for (int u = 0; u < 8; u++) { gr += cv[u].x; gi += cv[u].y; phi += ev[u]; }
     }
     for (; j < cp; j++) { gr += xc[-j].x; gi += xc[-j].y; phi += xe[-j]; }
-    const bool before = (long long)call * L + (cen - R + q) - cp + 1 - N < -p.hist;   // the lag reaches in front of the stream's first sample
-    s_lam[k & 1][slot][q] = before ? -3.0e38f : sqrtf(gr * gr + gi * gi) - phi * p.half_rho;
-    s_gam[k & 1][slot][q] = before ? make_float2(0.f, 0.f) : make_float2(gr, gi);
+    s_lam[k & 1][slot][q] = sqrtf(gr * gr + gi * gi) - phi * p.half_rho;
+    s_gam[k & 1][slot][q] = make_float2(gr, gi);
   };
   if (tid == 0) s_cen[0] = c0;
   metric_chunk(0, c0);
@@ -854,14 +849,12 @@ __global__ __launch_bounds__(576) void acq_small_kernel(const float2 *__restrict
             const int lag = cur - 8 + lane;
             const long long at = (long long)call * L + lag;
             float gr = 0.f, gi = 0.f, phi = 0.f;
-            if (at - cp + 1 - N < -p.hist) { s_dl[lane] = -3.0e38f; s_dg[lane] = make_float2(0.f, 0.f); }
-            else {
-              for (int j = 0; j < cp; j++) {
-                const float2 a = at - j < p.avail ? iq[at - j] : make_float2(0.f, 0.f), b = at - j - N < p.avail ? iq[at - j - N] : make_float2(0.f, 0.f);
-                gr += a.x * b.x + a.y * b.y; gi += a.y * b.x - a.x * b.y; phi += (a.x * a.x + a.y * a.y) + (b.x * b.x + b.y * b.y);
-              }
-              s_dg[lane] = make_float2(gr, gi); s_dl[lane] = sqrtf(gr * gr + gi * gi) - phi * p.half_rho;
+            for (int j = 0; j < cp; j++) {
+              const bool okl = at - j - N >= -p.hist;                // (no partner in front of the stream: the tap is skipped whole)
+              const float2 a = okl && at - j < p.avail ? iq[at - j] : make_float2(0.f, 0.f), b = okl && at - j - N < p.avail ? iq[at - j - N] : make_float2(0.f, 0.f);
+              gr += a.x * b.x + a.y * b.y; gi += a.y * b.x - a.x * b.y; phi += (a.x * a.x + a.y * a.y) + (b.x * b.x + b.y * b.y);
             }
+            s_dg[lane] = make_float2(gr, gi); s_dl[lane] = sqrtf(gr * gr + gi * gi) - phi * p.half_rho;
           }
           __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
           rel0 = 0;

@@ -916,6 +916,34 @@ int dvbt_debug_frames(dvbt_rx *h, int n_symbols, int keep_last, const int32_t *m
                       const uint8_t *labels, int64_t sym_off, int start_delay_symbols, dvbt_frames_report *report, int32_t *maj, int32_t *sym_index,
                       dvbt_tps_state *final_state, uint8_t *bitdeint, uint8_t *bitdeint_lp, uint8_t *symdeint);
 
+/* the acquisition kernels of the segment path alone (csrc/k_frontend.hpp: initial search, anchors, centres, tracking metric, the Jacobi placement and its
+ * bookkeeping, the light and the float-faithful sequential walk, acq_small_kernel) through the segment path's own launch routine (launch_acquisition of
+ * csrc/dvbt_hip.hip, which enqueue calls), as an acquisition-only pass on the handle's buffers.  iq_host: hist + nsamples complex64 samples; the segment begins at
+ * sample `hist` of it, the `hist` samples in front are the stream's history (FrontParams.hist); avail as in FrontParams (reads at or beyond it return zeros);
+ * init_tries windows for the initial search; use_carry / carry_avg the peak detector's average carried in; path 0 = the general kernels, 1 = acq_small_kernel;
+ * force (path 0): 1 = need_seq is set behind acq_finalize_kernel (the light walk runs on a period the placement settled), 2 = need_heavy too (the float-faithful
+ * walk).  Every buffer the kernels write -- both metrics, anchors, centres, the placement's peaks and estimates, the SymMeta rows, the 16 flag words, the state
+ * block -- is 0xA5 up to its capacity before the launches.  Outputs: the report; meta[nread] (more than n_symbols shows what lies behind the last symbol); and, each
+ * NULL or: g_init cfloat / l_init float [min(init_tries, ncalls)][N]; anchor_pos int32[cap_symbols / 256 + 4]; centre int32[nread]; g_trk cfloat / l_trk float
+ * [nread][32]; init_flags uint8 [min(init_tries, ncalls)][N]: bit 0 the rise, bit 1 the keep decision of acq_init_fsm_kernel for every sample of every window it
+ * examined (0xA5 behind the window that held the peak).  Behind the call the state block and the flag words are zero, as a fresh handle's.  cap_symbols = (max_samples - (2 N + cp + 16)) / (N + cp) + 1.  DVBT_ERR_INVALID, nothing allocated or launched, for: a null required pointer;
+ * nsamples outside (0, 2^31]; hist outside [0, 2^20]; avail outside (0, nsamples]; init_tries outside [1, 64]; an unknown path; force outside [0, 2] or non-zero on
+ * path 1; a non-finite carried average; a negative nread; and -- behind DVBT_ERR_NO_DEVICE without a GPU -- a null handle, fewer samples than one acquisition
+ * window, more calls or a larger nread than the handle's buffers hold, path 1 with more than 768 calls.  tests/test_gpu_acquire.py */
+typedef struct { int32_t cp_start, sw; float eps, ph_base; double incA, incB; } dvbt_sym_meta;
+typedef struct {
+  int32_t status, call0, cp_start0, n_symbols;
+  float avg, eps_init, avg_lost;
+  int32_t small_viol, drift_known_off;
+  int32_t changed[4], need_seq, need_heavy;   /* the flag words behind the launches */
+  int32_t ncalls, cap_symbols;
+  int32_t small_passes, general_passes;       /* what this call added to the walk counters of dvbt_rx_walk_stats */
+  int32_t reserved;
+} dvbt_acquire_report;
+int dvbt_debug_acquire(dvbt_rx *h, const void *iq_host, size_t nsamples, int64_t hist, int64_t avail, int init_tries, int use_carry, float carry_avg,
+                       int path, int force, dvbt_acquire_report *report, dvbt_sym_meta *meta, int nread, void *g_init, float *l_init, int32_t *anchor_pos,
+                       int32_t *centre, void *g_trk, float *l_trk, uint8_t *init_flags);
+
 /* the channel-error kernel alone (csrc/k_quality.hpp) on host bytes: in_host = n_in decoder input bytes (m bits each), vit_host = n_vit decoded bytes; counts as
  * dvbt_rx_quality's channel_bits / channel_bit_errors (n_vit < 2: both 0).  Sizes outside [0, 2^30] are refused before the device is asked for. */
 int dvbt_debug_quality_channel(int constellation, int code_rate, const uint8_t *in_host, int64_t n_in, const uint8_t *vit_host, int64_t n_vit, int64_t *bits, int64_t *errors);

@@ -109,6 +109,14 @@ def test_no_cpu_fallback(g):
         assert L.dvbt_debug_frames(*bad) == -1, (i, v)
     assert L.dvbt_debug_frames(*ok) == -2
     assert all(x == 0 for x in frep) and all(x == 0 for x in st)
+    # dvbt_debug_acquire: null pointers, sizes, an unknown path or force before it asks for the device; what needs the handle is in tests/test_gpu_acquire.py
+    L.dvbt_debug_acquire.argtypes = g.binding.ACQUIRE_ARGTYPES
+    ok = [None, iq, 4096, 0, 4096, 4, 0, 0.0, 0, 0, C.byref(g.binding.AcquireReport()), lab, 4] + [None] * 7
+    for i, v in ((1, None), (10, None), (11, None), (2, 0), (3, -1), (4, 0), (4, 4097), (5, 0), (5, 65), (8, 2), (9, 3), (12, -1)):
+        bad = list(ok)
+        bad[i] = v
+        assert L.dvbt_debug_acquire(*bad) == -1, (i, v)
+    assert L.dvbt_debug_acquire(*ok) == -2
 
 
 def test_product_does_not_import_oracle():

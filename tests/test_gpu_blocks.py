@@ -341,7 +341,8 @@ def test_wave_peak_detector(g):
     """the sequential trackers' wavefront-wide peak detector (k_frontend.hpp::peak_detect16_wave: IIR average as the one recurrence, threshold tests as ballots,
     the state machine on 16-bit masks with DPP prefix maxima) against the sample-by-sample restatement of peak_detect_process
     (lib/ofdm_sym_acquisition_impl.cc:72-146) on 60,000 windows: noise around a carried average of either sign, triangles like a CP peak, plateaus and
-    exact ties (quantised values), windows that end inside an open peak, several peaks per window, the -3e38 sentinel of lags in front of the stream."""
+    exact ties (quantised values), windows that end inside an open peak, several peaks per window, and windows that begin with values of -3e38 (what the metric kernels
+    once wrote for lags in front of the stream; they sum the taps that exist now, but the two detectors must agree on such values all the same)."""
     rng = np.random.RandomState(11)
     n = 60000
     lam = np.empty((n, 16), np.float32)
@@ -359,7 +360,7 @@ def test_wave_peak_detector(g):
             x = np.round((base + rng.randn(16) * 20) / 16) * 16
         elif t == 3:                                                     # positive values, several peaks
             x = np.abs(rng.randn(16)) * rng.choice([1, 50]) * (rng.rand(16) > 0.4)
-        elif t == 4:                                                     # lags in front of the stream's first sample
+        elif t == 4:                                                     # huge negative values at the window's start
             x = base + rng.randn(16) * 10; x[:rng.randint(1, 16)] = -3.0e38
         else:                                                            # ramps: a window that ends inside an open peak
             x = base + np.arange(16) * rng.uniform(-30, 30) + rng.randn(16) * 3
