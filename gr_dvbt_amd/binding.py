@@ -615,6 +615,78 @@ class Channel:
             pass
 
 
+class ClockParams(C.Structure):
+    _fields_ = [("ppm", C.c_double), ("start", C.c_double), ("taps", C.c_int), ("first_out", C.c_int64), ("first_in", C.c_int64), ("device", C.c_int)]
+
+
+def _clock_lib():
+    L = lib()
+    if not getattr(L, "_clock_typed", False):
+        L.dvbt_clock_outputs.argtypes = [C.POINTER(ClockParams), C.c_int64, C.POINTER(C.c_int64)]
+        L.dvbt_clock_create.argtypes = [C.POINTER(ClockParams), C.POINTER(C.c_void_p)]
+        L.dvbt_clock_outputs_for.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
+        L.dvbt_clock_run.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
+        L.dvbt_clock_run_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p]
+        L.dvbt_clock_reset.argtypes = [C.c_void_p]
+        L.dvbt_clock_destroy.argtypes = [C.c_void_p]
+        L._clock_typed = True
+    return L
+
+
+def clock_outputs(params, n_in_total):
+    """dvbt_clock_outputs: the outputs a stream with these ClockParams has emitted once n_in_total inputs have been pushed (host arithmetic, needs no GPU)"""
+    n = C.c_int64()
+    _chk(_clock_lib().dvbt_clock_outputs(C.byref(params), int(n_in_total), C.byref(n)))
+    return n.value
+
+
+class ClockOffset:
+    """dvbt_clock_*: complex64 baseband as a receiver whose sample clock is off by `ppm` sees it, y[m] = x(start + m (1 + ppm 1e-6)) by windowed-sinc
+    interpolation over `taps` samples, on the GPU.  start=None: taps // 2, the alignment of the test oracle's resampler.  One stream, delivered over any
+    number of run() / run_device() calls of any size; the concatenated outputs are bit for bit those of one call.  first_out / first_in: the absolute numbers of
+    the stream's first output and input (a piece of a cut stream)."""
+
+    def __init__(self, ppm, start=None, taps=16, first_out=0, first_in=0, device=0):
+        self.L = _clock_lib()
+        self.p = ClockParams(float(ppm), float(taps // 2 if start is None else start), int(taps), int(first_out), int(first_in), int(device))
+        self.h = C.c_void_p()
+        _chk(self.L.dvbt_clock_create(C.byref(self.p), C.byref(self.h)))
+
+    def outputs_for(self, n_in):
+        """samples the NEXT call with n_in input samples will emit"""
+        n = C.c_size_t()
+        _chk(self.L.dvbt_clock_outputs_for(self.h, n_in, C.byref(n)))
+        return n.value
+
+    def run(self, iq):
+        """complex64 samples in, the outputs they complete out; continues the stream"""
+        iq = np.ascontiguousarray(iq, dtype=np.complex64).reshape(-1)
+        out = np.empty(self.outputs_for(len(iq)), np.complex64)
+        n = C.c_size_t()
+        _chk(self.L.dvbt_clock_run(self.h, iq.ctypes.data_as(C.c_void_p), len(iq), out.ctypes.data_as(C.c_void_p), len(out), C.byref(n)))
+        return out[:n.value]
+
+    def run_device(self, in_ptr, n_in, out_ptr, out_cap, stream=None):
+        """device pointers (ints), not overlapping: enqueues on `stream` (a hipStream_t as int, None: the default stream) and returns the output count at once"""
+        n = C.c_size_t()
+        _chk(self.L.dvbt_clock_run_device(self.h, C.c_void_p(in_ptr), n_in, C.c_void_p(out_ptr), out_cap, C.byref(n), C.c_void_p(stream) if stream else None))
+        return n.value
+
+    def reset(self):
+        _chk(self.L.dvbt_clock_reset(self.h))
+
+    def close(self):
+        if self.h:
+            self.L.dvbt_clock_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 # ------------------------------------------------------------------ per-block C ABI (one triple per reference block)
 TAG_SYNC_START, TAG_SUPERFRAME_START, TAG_SYMBOL_INDEX = 1, 2, 3
 

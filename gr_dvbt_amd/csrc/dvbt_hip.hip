@@ -27,6 +27,7 @@
 #include "k_tx.hpp"
 #include "k_txblocks.hpp"
 #include "k_channel.hpp"
+#include "k_clock.hpp"
 
 using namespace dvbt;
 using hip_own::DevMem; using hip_own::PinMem; using hip_own::Stream; using hip_own::Event;
@@ -2012,3 +2013,4 @@ extern "C" int dvbt_debug_acquire(dvbt_rx *h, const void *iq_host, size_t nsampl
 #include "dvbt_tx.inc"
 #include "dvbt_txblocks.inc"
 #include "dvbt_channel.inc"
+#include "dvbt_clock.inc"

@@ -987,6 +987,35 @@ int  dvbt_channel_power(dvbt_channel *h, const void *iq_device, size_t n, void *
 int  dvbt_channel_reset(dvbt_channel *h);   /* back to first_sample, history cleared */
 void dvbt_channel_destroy(dvbt_channel *h);
 
+/* ------------------------------------------------------------------ the sample-clock offset: windowed-sinc resampling by ppm
+ * The stream as a receiver whose sample clock is off by `ppm` sees it (oracle/pyoracle.py::clock_offset on the device, csrc/k_clock.hpp), on complex64
+ * baseband, as a block of its own in front of or behind the channel: the sample count changes, which the channel's in = out contract does not allow.
+ * Positions are integers.  With H = taps / 2, S = 2^64 + rint(ppm 1e-6 2^64) (ties to even) and P0 = trunc(start 2^64), output m of the stream samples the
+ * input at P(m) = P0 + m S in units of 2^-64 input samples (a 128-bit integer): base = P >> 64, f = P mod 2^64, and
+ *   y[m] = sum_{k = -(H-1)}^{H} h(k - f / 2^64) x[base + k]      h(a) = sinc(a) (0.54 + 0.46 cos(pi a / (H + 1)))      x[i] = 0 for i < first_in
+ * m and the x index are absolute: the stream's first input sample is x[first_in], its first output y[first_out].  f == 0 gives x[base] bit for bit.  The sum
+ * runs in a fixed order (k ascending) in float, so an output's bits depend on m and its taps inputs alone: a stream cut into calls of any size (0 and 1
+ * included) gives bit for bit what one call gives, and a handle with first_out = M, first_in = base(M) - (H - 1) continues a cut stream at output M.
+ * Counts: E(N) = the smallest m >= 0 with base(m) + H >= N.  With N = first_in + the inputs pushed so far, the outputs emitted so far are those in front of
+ * E(N), from first_out on; a call emits every output it can complete, max(E(N_after), first_out) - max(E(N_before), first_out), a number the host computes in
+ * integer arithmetic (dvbt_clock_outputs_for, dvbt_clock_outputs) without waiting for the device.  Every input sample is consumed; the handle keeps the last
+ * 64 on the device.  There is no flush: the outputs whose support reaches behind the last input are never emitted.
+ * Parameters: |ppm| <= 1000; 0 <= start < 2^31 (input samples; taps / 2 is the oracle's alignment); taps 16, 32 or 64 (0: 16); first_out, first_in in
+ * [0, 2^48]; at most 2^56 input samples per stream.  Buffers: n_in <= 2^31 complex64 per call, 8-byte aligned; input and output ranges that overlap are
+ * DVBT_ERR_INVALID; out_cap below the call's count is DVBT_ERR_CAPACITY.  A failed call leaves the stream position and the history as they were.
+ * dvbt_clock_run_device only enqueues on `stream`; calls on different streams are ordered by the handle (an event).  One thread per handle.  Every parameter
+ * is checked before the device is asked for: a bad struct is DVBT_ERR_INVALID everywhere, a good one DVBT_ERR_NO_DEVICE without a GPU -- there is no CPU path. */
+typedef struct { double ppm, start; int taps; int64_t first_out, first_in; int device; } dvbt_clock_params;
+typedef struct dvbt_clock dvbt_clock;
+/* outputs emitted once n_in_total (<= 2^56) inputs have been pushed: host arithmetic, needs no device */
+int  dvbt_clock_outputs(const dvbt_clock_params *p, int64_t n_in_total, int64_t *n_out_total);
+int  dvbt_clock_create(const dvbt_clock_params *p, dvbt_clock **out);
+int  dvbt_clock_outputs_for(const dvbt_clock *h, size_t n_in, size_t *n_out);   /* what the NEXT call of n_in samples emits */
+int  dvbt_clock_run(dvbt_clock *h, const void *iq_host, size_t n_in, void *out_host, size_t out_cap, size_t *n_out);
+int  dvbt_clock_run_device(dvbt_clock *h, const void *iq_device, size_t n_in, void *out_device, size_t out_cap, size_t *n_out, void *stream);
+int  dvbt_clock_reset(dvbt_clock *h);   /* back to first_in / first_out, history cleared */
+void dvbt_clock_destroy(dvbt_clock *h);
+
 #ifdef __cplusplus
 }
 #endif
