@@ -687,6 +687,110 @@ class ClockOffset:
             pass
 
 
+FADING_MAX_PATHS, FADING_MAX_DELAY, FADING_MAX_SINUSOIDS, FADING_KNOT = 24, 8192, 32, 64
+TU6_DELAYS_US = (0.0, 0.2, 0.5, 1.6, 2.3, 5.0)          # COST 207 TU6
+TU6_POWERS_DB = (-3.0, 0.0, -2.0, -6.0, -8.0, -10.0)
+
+
+class FadingParams(C.Structure):
+    _fields_ = [("n_paths", C.c_int), ("delay", C.c_int * 24), ("los_re", C.c_float * 24), ("los_im", C.c_float * 24), ("sigma", C.c_float * 24),
+                ("doppler", C.c_double), ("n_sinusoids", C.c_int), ("seed", C.c_uint64), ("first_sample", C.c_int64), ("device", C.c_int)]
+
+    @classmethod
+    def of(cls, paths, doppler=0.0, n_sinusoids=16, seed=0, first_sample=0, device=0):
+        """paths: ((delay in samples, fixed part (complex), sigma of the scattered part), ...)"""
+        paths = tuple(paths)
+        if len(paths) > FADING_MAX_PATHS:
+            raise ValueError(f"at most {FADING_MAX_PATHS} paths")
+        p = cls()
+        p.n_paths = len(paths)
+        for i, (d, los, sg) in enumerate(paths):
+            p.delay[i], p.los_re[i], p.los_im[i], p.sigma[i] = int(d), float(np.real(los)), float(np.imag(los)), float(sg)
+        p.doppler, p.n_sinusoids = float(doppler), int(n_sinusoids)
+        p.seed, p.first_sample, p.device = int(seed) & 0xffffffffffffffff, int(first_sample), int(device)
+        return p
+
+
+def _fading_lib():
+    L = lib()
+    if not getattr(L, "_fading_typed", False):
+        L.dvbt_fading_table.argtypes = [C.POINTER(FadingParams), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        L.dvbt_fading_create.argtypes = [C.POINTER(FadingParams), C.POINTER(C.c_void_p)]
+        L.dvbt_fading_run.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+        L.dvbt_fading_run_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+        L.dvbt_fading_reset.argtypes = [C.c_void_p]
+        L.dvbt_fading_destroy.argtypes = [C.c_void_p]
+        L._fading_typed = True
+    return L
+
+
+def fading_table(params):
+    """dvbt_fading_table: (inc, phase) of these FadingParams, two uint64 arrays [n_paths][M] (host arithmetic, needs no GPU)"""
+    np_, M = max(int(params.n_paths), 0), int(params.n_sinusoids) or 16
+    n = max(np_ * M, 1) if 0 <= M <= FADING_MAX_SINUSOIDS and np_ <= FADING_MAX_PATHS else 1      # a bad struct is refused before anything is written
+    inc, ph = np.zeros(n, np.uint64), np.zeros(n, np.uint64)
+    _chk(_fading_lib().dvbt_fading_table(C.byref(params), inc.ctypes.data_as(C.POINTER(C.c_uint64)), ph.ctypes.data_as(C.POINTER(C.c_uint64))))
+    return inc.reshape(np_, M), ph.reshape(np_, M)
+
+
+def tu6_paths(doppler_hz, sample_rate=64e6 / 7, rice_k_db=None):
+    """COST 207 TU6 as (paths, doppler in cycles per sample): delays rounded to samples, powers normalised to a total of 1.  With rice_k_db (K in dB) the
+    scatter is scaled by 1 / (1 + K) in power and a fixed part sqrt(K / (1 + K)) stands on path 0."""
+    pw = [10.0 ** (d / 10.0) for d in TU6_POWERS_DB]
+    tot = sum(pw)
+    K = None if rice_k_db is None else 10.0 ** (rice_k_db / 10.0)
+    scat = 1.0 if K is None else 1.0 / (1.0 + K)
+    paths = []
+    for i, (us, w) in enumerate(zip(TU6_DELAYS_US, pw)):
+        los = float(np.sqrt(K / (1.0 + K))) if (K is not None and i == 0) else 0.0
+        paths.append((int(round(us * 1e-6 * sample_rate)), complex(los), float(np.sqrt(w / tot * scat))))
+    return tuple(paths), float(doppler_hz) / float(sample_rate)
+
+
+class Fading:
+    """dvbt_fading_*: time-varying multipath on complex64 baseband, on the GPU.  paths: ((delay in samples, fixed part, sigma), ...): every path's gain is
+    its fixed part plus a sum of n_sinusoids sinusoids of rms sigma whose frequencies follow Clarke's spectrum up to `doppler` cycles per sample.  One stream,
+    delivered over any number of run() / run_device() calls of any size; the concatenated outputs are bit for bit those of one call.  The gain of a sample
+    depends on (paths, doppler, n_sinusoids, seed, first_sample + its index) alone.  No noise, no carrier offset: put a Channel behind it."""
+
+    def __init__(self, paths=((0, 1.0, 0.0),), doppler=0.0, n_sinusoids=16, seed=0, first_sample=0, device=0):
+        self.L = _fading_lib()
+        self.p = FadingParams.of(paths, doppler, n_sinusoids, seed, first_sample, device)
+        self.h = C.c_void_p()
+        _chk(self.L.dvbt_fading_create(C.byref(self.p), C.byref(self.h)))
+
+    @classmethod
+    def tu6(cls, doppler_hz, sample_rate=64e6 / 7, rice_k_db=None, **kw):
+        """COST 207 TU6 at a largest Doppler shift of doppler_hz; rice_k_db: a Ricean first path (tu6_paths); kw: n_sinusoids, seed, first_sample, device"""
+        paths, doppler = tu6_paths(doppler_hz, sample_rate, rice_k_db)
+        return cls(paths, doppler, **kw)
+
+    def run(self, iq):
+        """complex64 samples in, as many out; continues the stream"""
+        iq = np.ascontiguousarray(iq, dtype=np.complex64).reshape(-1)
+        out = np.empty_like(iq)
+        _chk(self.L.dvbt_fading_run(self.h, iq.ctypes.data_as(C.c_void_p), len(iq), out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def run_device(self, in_ptr, nsamples, out_ptr, stream=None):
+        """device pointers (ints) to nsamples complex64 each, not overlapping: enqueues on `stream` (a hipStream_t as int, None: the default stream)"""
+        _chk(self.L.dvbt_fading_run_device(self.h, C.c_void_p(in_ptr), nsamples, C.c_void_p(out_ptr), C.c_void_p(stream) if stream else None))
+
+    def reset(self):
+        _chk(self.L.dvbt_fading_reset(self.h))
+
+    def close(self):
+        if self.h:
+            self.L.dvbt_fading_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 # ------------------------------------------------------------------ per-block C ABI (one triple per reference block)
 TAG_SYNC_START, TAG_SUPERFRAME_START, TAG_SYMBOL_INDEX = 1, 2, 3
 

@@ -1016,6 +1016,48 @@ int  dvbt_clock_run_device(dvbt_clock *h, const void *iq_device, size_t n_in, vo
 int  dvbt_clock_reset(dvbt_clock *h);   /* back to first_in / first_out, history cleared */
 void dvbt_clock_destroy(dvbt_clock *h);
 
+/* ------------------------------------------------------------------ fading: time-varying multipath with a Doppler spectrum
+ * What a moving receiver sees: a tapped delay line whose taps fade as sums of sinusoids (Clarke's spectrum, optionally with a fixed part: Rice), on complex64
+ * baseband, in one kernel (csrc/k_fading.hpp).  For the stream's absolute sample index n:
+ *   y[n] = sum_{i < n_paths} g_i(n) x[n - d_i]          x[k] = 0 in front of the stream's first sample; i ascending, the first path's product starts the sum
+ * Sinusoid table (host, double, the same bits everywhere; dvbt_fading_table): for path i and sinusoid m < M = n_sinusoids, w = Philox4x32-10 with key (seed low
+ * 32, seed high 32) and counter (m, i, 0, 0x46414445) -- disjoint from the channel's noise counters (P lo, P hi, 0, 0), so the same seed in a dvbt_channel
+ * behind this block is independent; u = (w0 + 0.5) 2^-32; angle of arrival alpha = (m + u) / M turns (stratified: one sinusoid per M-th of the circle);
+ * f = doppler cos(2 pi alpha), the cosine by quarter-turn reduction and a Taylor polynomial in plain double arithmetic; inc = nearbyint(f 2^64) mod 2^64;
+ * ph = (w1 << 32) | w2.
+ * Knots (float32, each operation rounded on its own): every DVBT_FADING_KNOT absolute samples, S_i(k) = sum_m cis(top 32 bits of (ph + inc 64 k mod 2^64)),
+ * m ascending from 0; G_i(k) = los_i + s_i S_i(k), s_i = (float)(sigma_i / sqrt(M)).
+ * Gain: k = n >> 6, t = (n & 63) 2^-6, g_i(n) = G_i(k) + t (G_i(k + 1) - G_i(k)) per component.  The piecewise-linear gain IS the specification; its distance
+ * from the sum of sinusoids taken at every sample is at most sigma_i sqrt(M) (2 pi 64 doppler)^2 / 8 (the chord error of a unit phasor, per sinusoid 9.7e-6
+ * at 200 Hz and 64/7 Msps, 1.2e-3 at the largest doppler).  Product: (ar x.re - ai x.im, ar x.im + ai x.re).
+ * The block adds no noise and no carrier offset (a dvbt_channel without echoes behind it does both) and does not normalise the mean power: sum_i (|los_i|^2 +
+ * sigma_i^2) is the caller's.  A path with sigma == 0 is static; one path (0, 1, 0) gives the input as values.
+ * The handle keeps the last DVBT_FADING_MAX_DELAY input samples on the device, so calls of any size (0 and 1 included) continue the stream, and a stream cut
+ * into calls gives bit for bit what one call gives; a handle with first_sample = s fed the stream from s on gives, from s + DVBT_FADING_MAX_DELAY on, the
+ * bits of the handle that began at 0.
+ * Buffers: n <= 2^31 complex64 each per call, 8-byte aligned; input and output ranges that overlap are DVBT_ERR_INVALID.  A failed call leaves the stream
+ * position and the history as they were.  dvbt_fading_run_device only enqueues on `stream`; calls on different streams are ordered by the handle (an event).
+ * One thread per handle.  Every parameter is checked before the device is asked for: a bad struct is DVBT_ERR_INVALID everywhere, a good one
+ * DVBT_ERR_NO_DEVICE without a GPU -- there is no CPU path, except dvbt_fading_table, which is host arithmetic. */
+enum { DVBT_FADING_MAX_PATHS = 24, DVBT_FADING_MAX_DELAY = 8192, DVBT_FADING_MAX_SINUSOIDS = 32, DVBT_FADING_KNOT = 64 };
+typedef struct {
+  int n_paths;                                   /* 1 .. 24 */
+  int delay[24];                                 /* 0 .. 8192 samples; equal delays allowed */
+  float los_re[24], los_im[24];                  /* the path's fixed part */
+  float sigma[24];                               /* rms of its scattered part, >= 0; 0: the path is static */
+  double doppler;                                /* largest Doppler shift in cycles per sample, 0 .. 2^-12 (2.2 kHz at 64/7 Msps) */
+  int n_sinusoids;                               /* 0 = 16; 1 .. 32 */
+  uint64_t seed; int64_t first_sample; int device;
+} dvbt_fading_params;
+typedef struct dvbt_fading dvbt_fading;
+/* the sinusoid table of a valid struct, n_paths x M words each (row i, column m): host arithmetic, needs no device */
+int  dvbt_fading_table(const dvbt_fading_params *p, uint64_t *inc, uint64_t *phase);
+int  dvbt_fading_create(const dvbt_fading_params *p, dvbt_fading **out);
+int  dvbt_fading_run(dvbt_fading *h, const void *iq_host, size_t n, void *out_host);
+int  dvbt_fading_run_device(dvbt_fading *h, const void *iq_device, size_t n, void *out_device, void *stream);
+int  dvbt_fading_reset(dvbt_fading *h);   /* back to first_sample, history cleared */
+void dvbt_fading_destroy(dvbt_fading *h);
+
 #ifdef __cplusplus
 }
 #endif
