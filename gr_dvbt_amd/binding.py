@@ -791,6 +791,119 @@ class Fading:
             pass
 
 
+RF_MAX_TONES, RF_MAX_MASK_POINTS = 32, 8
+
+
+class RfParams(C.Structure):
+    _fields_ = [("sat_amplitude", C.c_float), ("smoothness", C.c_float), ("n_tones", C.c_int), ("tone_inc", C.c_uint64 * 32),
+                ("tone_phase", C.c_uint64 * 32), ("tone_amp", C.c_float * 32), ("mu_re", C.c_float), ("mu_im", C.c_float), ("nu_re", C.c_float),
+                ("nu_im", C.c_float), ("dc_re", C.c_float), ("dc_im", C.c_float), ("first_sample", C.c_int64), ("device", C.c_int)]
+
+    @classmethod
+    def of(cls, sat_amplitude=0.0, smoothness=2.0, tones=None, mu=1, nu=0, dc=0, first_sample=0, device=0):
+        """tones: (inc, phase, amp), three sequences of equal length (phase_noise_tones, or a measured spur list), or None"""
+        p = cls()
+        p.sat_amplitude, p.smoothness = float(sat_amplitude), float(smoothness)
+        if tones is not None:
+            inc, ph, amp = tones
+            if not len(inc) == len(ph) == len(amp):
+                raise ValueError("tones: three sequences of equal length")
+            if len(inc) > RF_MAX_TONES:
+                raise ValueError(f"at most {RF_MAX_TONES} tones")
+            p.n_tones = len(inc)
+            for m in range(len(inc)):
+                p.tone_inc[m], p.tone_phase[m], p.tone_amp[m] = int(inc[m]) & 0xffffffffffffffff, int(ph[m]) & 0xffffffffffffffff, float(amp[m])
+        p.mu_re, p.mu_im, p.nu_re, p.nu_im = float(np.real(mu)), float(np.imag(mu)), float(np.real(nu)), float(np.imag(nu))
+        p.dc_re, p.dc_im = float(np.real(dc)), float(np.imag(dc))
+        p.first_sample, p.device = int(first_sample), int(device)
+        return p
+
+
+class RfMask(C.Structure):
+    _fields_ = [("n_points", C.c_int), ("offset_hz", C.c_double * 8), ("dbc_hz", C.c_double * 8), ("sample_rate", C.c_double)]
+
+
+def _rf_lib():
+    L = lib()
+    if not getattr(L, "_rf_typed", False):
+        L.dvbt_rf_phase_noise_tones.argtypes = [C.POINTER(RfMask), C.c_int, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_float)]
+        L.dvbt_rf_create.argtypes = [C.POINTER(RfParams), C.POINTER(C.c_void_p)]
+        L.dvbt_rf_run.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+        L.dvbt_rf_run_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+        L.dvbt_rf_reset.argtypes = [C.c_void_p]
+        L.dvbt_rf_destroy.argtypes = [C.c_void_p]
+        L._rf_typed = True
+    return L
+
+
+def phase_noise_tones(points, n_tones=32, seed=0, sample_rate=64e6 / 7):
+    """dvbt_rf_phase_noise_tones: the tone table (inc, phase: uint64 arrays; amp: float32 radians) of a phase-noise mask ((offset in Hz, level in dBc/Hz),
+    ...), 2 to 8 points, linear in dB over log f between them: n_tones tones, one drawn per n_tones-th of the log axis, whose powers add up to the mask's
+    integral whatever n_tones is.  Host arithmetic, needs no GPU.  The result is RfFrontend's `tones`."""
+    points = tuple(points)
+    if len(points) > RF_MAX_MASK_POINTS:
+        raise ValueError(f"at most {RF_MAX_MASK_POINTS} mask points")
+    mk = RfMask()
+    mk.n_points, mk.sample_rate = len(points), float(sample_rate)
+    for k, (f, d) in enumerate(points):
+        mk.offset_hz[k], mk.dbc_hz[k] = float(f), float(d)
+    n = min(max(int(n_tones), 1), RF_MAX_TONES)                    # a bad count is refused before anything is written
+    inc, ph, amp = np.zeros(n, np.uint64), np.zeros(n, np.uint64), np.zeros(n, np.float32)
+    _chk(_rf_lib().dvbt_rf_phase_noise_tones(C.byref(mk), int(n_tones), int(seed) & 0xffffffffffffffff, inc.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                             ph.ctypes.data_as(C.POINTER(C.c_uint64)), amp.ctypes.data_as(C.POINTER(C.c_float))))
+    return inc, ph, amp
+
+
+class RfFrontend:
+    """dvbt_rf_*: what the radio hardware does to complex64 baseband, on the GPU, in this order: the transmitter's amplifier (Rapp AM/AM with saturation
+    amplitude sat_amplitude and smoothness p; 0: off), oscillator phase noise as a sum of `tones` (phase_noise_tones; None: off), the tuner's IQ imbalance
+    v = mu r + nu conj(r) (iq_imbalance) and its DC offset.  One stream, delivered over any number of run() / run_device() calls of any size; the
+    concatenated outputs are bit for bit those of one call.  A sample's output depends on (the parameters, first_sample + its index, the sample) alone."""
+
+    def __init__(self, sat_amplitude=0.0, smoothness=2.0, tones=None, mu=1, nu=0, dc=0, first_sample=0, device=0):
+        self.L = _rf_lib()
+        self.p = RfParams.of(sat_amplitude, smoothness, tones, mu, nu, dc, first_sample, device)
+        self.h = C.c_void_p()
+        _chk(self.L.dvbt_rf_create(C.byref(self.p), C.byref(self.h)))
+
+    @staticmethod
+    def saturation(ibo_db, ref_power):
+        """the sat_amplitude of an input back-off of ibo_db relative to the mean power ref_power (Channel.power)"""
+        return float(np.sqrt(ref_power * 10.0 ** (ibo_db / 10.0)))
+
+    @staticmethod
+    def iq_imbalance(gain_db, phase_deg):
+        """(mu, nu) of a tuner whose arms differ by gain_db in gain and phase_deg in phase: image rejection |mu|^2 / |nu|^2"""
+        g, psi = 10.0 ** (gain_db / 20.0), np.deg2rad(phase_deg)
+        return complex((1.0 + g * np.exp(-1j * psi)) / 2.0), complex((1.0 - g * np.exp(1j * psi)) / 2.0)
+
+    def run(self, iq):
+        """complex64 samples in, as many out; continues the stream"""
+        iq = np.ascontiguousarray(iq, dtype=np.complex64).reshape(-1)
+        out = np.empty_like(iq)
+        _chk(self.L.dvbt_rf_run(self.h, iq.ctypes.data_as(C.c_void_p), len(iq), out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def run_device(self, in_ptr, nsamples, out_ptr, stream=None):
+        """device pointers (ints) to nsamples complex64 each, the same buffer (in place) or not overlapping: enqueues on `stream` (a hipStream_t as int,
+        None: the default stream)"""
+        _chk(self.L.dvbt_rf_run_device(self.h, C.c_void_p(in_ptr), nsamples, C.c_void_p(out_ptr), C.c_void_p(stream) if stream else None))
+
+    def reset(self):
+        _chk(self.L.dvbt_rf_reset(self.h))
+
+    def close(self):
+        if self.h:
+            self.L.dvbt_rf_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 # ------------------------------------------------------------------ per-block C ABI (one triple per reference block)
 TAG_SYNC_START, TAG_SUPERFRAME_START, TAG_SYMBOL_INDEX = 1, 2, 3
 

@@ -54,14 +54,15 @@ inline int channel_rewind(dvbt_channel *h)
   return DVBT_OK;
 }
 
-inline int channel_check_call(const void *in, size_t n, const void *out)
+// in_place_ok: a memoryless block (dvbt_rf) takes one buffer as input and output; ranges that overlap in any other way are refused everywhere
+inline int channel_check_call(const void *in, size_t n, const void *out, bool in_place_ok = false)
 {
   if (n == 0) return DVBT_OK;
   if (!in || !out) return fail(DVBT_ERR_INVALID, "null buffer");
   if (n > (size_t)1 << 31) return fail(DVBT_ERR_INVALID, "n must be <= 2^31 per call (a longer stream continues over calls)");
   if (((uintptr_t)in & 7) || ((uintptr_t)out & 7)) return fail(DVBT_ERR_INVALID, "the sample buffers must be 8-byte aligned");
   const uintptr_t a = (uintptr_t)in, b = (uintptr_t)out, bytes = n * sizeof(float2);
-  if (a < b + bytes && b < a + bytes) return fail(DVBT_ERR_INVALID, "the input and output ranges overlap");
+  if (a < b + bytes && b < a + bytes && !(in_place_ok && a == b)) return fail(DVBT_ERR_INVALID, "the input and output ranges overlap");
   return DVBT_OK;
 }
 

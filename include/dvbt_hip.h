@@ -1058,6 +1058,54 @@ int  dvbt_fading_run_device(dvbt_fading *h, const void *iq_device, size_t n, voi
 int  dvbt_fading_reset(dvbt_fading *h);   /* back to first_sample, history cleared */
 void dvbt_fading_destroy(dvbt_fading *h);
 
+/* ------------------------------------------------------------------ rf: the transmitter's amplifier, oscillator phase noise, the tuner's IQ imbalance and DC
+ * What the radio hardware on either side of a channel does to complex64 baseband, in one kernel (csrc/k_rf.hpp).  For the stream's absolute sample index n
+ * (first_sample + the samples the handle has seen), four stages in this order, each off by default:
+ *   1. amplifier, Rapp AM/AM   u = x (1 + (|x|^2 / A^2)^p)^(-1/(2p))       A = sat_amplitude (0: off), p = smoothness in [0.5, 16] (0 = 2).  The phase is
+ *      untouched, |u| < A, x = 0 gives 0; right for every finite x (above |x| = A the kernel uses t^(-1/2) (1 + t^(-p))^(-1/(2p)), t = |x|^2 / A^2).
+ *   2. phase noise             r = u (cos phi, sin phi)    phi(n) = sum_{m < n_tones} a_m sin(2 pi theta_m(n)), m ascending in float32;  theta_m(n) = the
+ *      top 32 bits of (tone_phase[m] + tone_inc[m] n mod 2^64) times 2^-32: an integer product, as exact at n = 2^40 as at 0.  n_tones == 0: off.
+ *      a_m = tone_amp[m] >= 0, and their sum must not exceed pi.  Product: (ar x.re - ai x.im, ar x.im + ai x.re).
+ *   3. IQ imbalance            v = mu r + nu conj(r)       mu == (0, 0) stands for (1, 0), so a zeroed struct is the identity; off where mu == 1 and nu == 0.
+ *   4. DC offset               y = v + dc                  off where dc == 0.
+ * With every stage off the output is the input bit for bit.  The block is memoryless: a sample's output bits depend on (the struct, n, x[n]) alone, so calls
+ * of any size (0 and 1 included) continue the stream, a stream cut into calls gives bit for bit what one call gives, and a handle with first_sample = s gives
+ * the bits of the handle that began at 0 from s on.
+ * Tones from a phase-noise mask (dvbt_rf_phase_noise_tones; host arithmetic in double, needs no device): the mask is 2 to 8 points (offset_hz[k], dbc_hz[k]),
+ * offsets > 0 and strictly ascending, the last <= sample_rate / 2; L(f) is linear in dB over log f between them.  With rho = f_last / f_0, M = n_tones:
+ * edges e_m = f_0 exp(ln rho m / M), e_M = f_last; w = Philox4x32-10 with key (seed low 32, seed high 32) and counter (m, 0, 0, 0x5246504E) -- disjoint from
+ * the channel's noise counters and from the fading table's; u = (w0 + 0.5) 2^-32; f_m = f_0 exp(ln rho (m + u) / M) (one tone per M-th of the log axis);
+ * inc = nearbyint(f_m / sample_rate 2^64); ph = (w1 << 32) | w2; a_m = (float)(2 sqrt(B_m)), B_m = the integral of L over [e_m, e_m+1] in closed form, so
+ * that sum a_m^2 / 2 = 2 integral L df (both sidebands) for every M.  A caller with a measured spur list fills the three arrays itself.
+ * Buffers: n <= 2^31 complex64 each per call, 8-byte aligned.  Input and output may be the SAME buffer (in place); ranges that overlap in any other way are
+ * DVBT_ERR_INVALID.  A failed call leaves the stream position as it was.  dvbt_rf_run_device only enqueues on `stream`; calls on different streams are ordered
+ * by the handle (an event).  One thread per handle.  Every parameter is checked before the device is asked for: a bad struct is DVBT_ERR_INVALID everywhere, a
+ * good one DVBT_ERR_NO_DEVICE without a GPU -- there is no CPU path. */
+enum { DVBT_RF_MAX_TONES = 32, DVBT_RF_MAX_MASK_POINTS = 8 };
+typedef struct {
+  float sat_amplitude;                           /* A; 0: no amplifier */
+  float smoothness;                              /* p: 0 = 2; 0.5 .. 16 */
+  int n_tones;                                   /* 0 .. 32; 0: no phase noise */
+  uint64_t tone_inc[32], tone_phase[32];         /* per sample in units of 2^-64 turns; the phase at n = 0 */
+  float tone_amp[32];                            /* radians, >= 0, sum <= pi */
+  float mu_re, mu_im, nu_re, nu_im;              /* mu == (0, 0): (1, 0) */
+  float dc_re, dc_im;
+  int64_t first_sample; int device;
+} dvbt_rf_params;
+typedef struct {
+  int n_points;                                  /* 2 .. 8 */
+  double offset_hz[8], dbc_hz[8];
+  double sample_rate;                            /* Hz */
+} dvbt_rf_mask;
+typedef struct dvbt_rf dvbt_rf;
+/* n_tones (1 .. 32) words each; on refusal nothing is written */
+int  dvbt_rf_phase_noise_tones(const dvbt_rf_mask *mask, int n_tones, uint64_t seed, uint64_t *inc, uint64_t *phase, float *amp);
+int  dvbt_rf_create(const dvbt_rf_params *p, dvbt_rf **out);
+int  dvbt_rf_run(dvbt_rf *h, const void *iq_host, size_t n, void *out_host);
+int  dvbt_rf_run_device(dvbt_rf *h, const void *iq_device, size_t n, void *out_device, void *stream);
+int  dvbt_rf_reset(dvbt_rf *h);   /* back to first_sample */
+void dvbt_rf_destroy(dvbt_rf *h);
+
 #ifdef __cplusplus
 }
 #endif
