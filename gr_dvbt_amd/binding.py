@@ -904,6 +904,180 @@ class RfFrontend:
             pass
 
 
+SPECTRUM_HIST_BINS = 2048
+SPECTRUM_WINDOWS = {"rect": 0, "rectangular": 0, "hann": 1, "blackman-harris": 2, "blackmanharris": 2}
+
+
+class SpectrumParams(C.Structure):
+    _fields_ = [("device", C.c_int), ("fft_size", C.c_int), ("hop", C.c_int), ("window", C.c_int)]
+
+
+class SpectrumResult(C.Structure):
+    _fields_ = [("segments", C.c_longlong), ("samples_pushed", C.c_longlong), ("samples_counted", C.c_longlong), ("nonfinite", C.c_longlong),
+                ("sum_power", C.c_double), ("peak_power", C.c_float)]
+
+
+def _spectrum_lib():
+    L = lib()
+    if not getattr(L, "_spectrum_typed", False):
+        L.dvbt_spectrum_create.argtypes = [C.POINTER(SpectrumParams), C.POINTER(C.c_void_p)]
+        L.dvbt_spectrum_push.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+        L.dvbt_spectrum_push_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+        L.dvbt_spectrum_read.argtypes = [C.c_void_p, C.POINTER(SpectrumResult), C.POINTER(C.c_double), C.POINTER(C.c_ulonglong)]
+        L.dvbt_spectrum_reset.argtypes = [C.c_void_p]
+        L.dvbt_spectrum_destroy.argtypes = [C.c_void_p]
+        L._spectrum_typed = True
+    return L
+
+
+def spectrum_window(fft_size, window):
+    """the float32 table of window 0 (rectangular), 1 (Hann) or 2 (4-term Blackman-Harris): periodic, computed in double"""
+    t = 2.0 * np.pi * np.arange(fft_size, dtype=np.float64) / fft_size
+    if window == 0:
+        w = np.ones(fft_size)
+    elif window == 1:
+        w = 0.5 - 0.5 * np.cos(t)
+    elif window == 2:
+        w = 0.35875 - 0.48829 * np.cos(t) + 0.14128 * np.cos(2.0 * t) - 0.01168 * np.cos(3.0 * t)
+    else:
+        raise ValueError("window must be 0, 1 or 2")
+    return w.astype(np.float32)
+
+
+class SpectrumReading:
+    """What Spectrum.read() returns: `psd` (fft_size doubles, fft-shifted, power per bin), `hist` (2048 uint64 counts of |x|^2 by float_bits >> 20) and the
+    fields of dvbt_spectrum_result.  The helpers are numpy in double on the host and need no GPU; frequencies are in Hz for `sample_rate`."""
+
+    def __init__(self, psd, hist, segments, samples_pushed, samples_counted, nonfinite, sum_power, peak_power, fft_size, hop, window, sample_rate=64e6 / 7):
+        self.psd = np.asarray(psd, dtype=np.float64)
+        self.hist = np.asarray(hist, dtype=np.uint64)
+        self.segments, self.samples_pushed, self.samples_counted, self.nonfinite = int(segments), int(samples_pushed), int(samples_counted), int(nonfinite)
+        self.sum_power, self.peak_power = float(sum_power), np.float32(peak_power)
+        self.fft_size, self.hop, self.window, self.sample_rate = int(fft_size), int(hop), int(window), float(sample_rate)
+        assert self.psd.shape == (self.fft_size,) and self.hist.shape == (SPECTRUM_HIST_BINS,)
+
+    def freqs(self, sample_rate=None):
+        fs = self.sample_rate if sample_rate is None else float(sample_rate)
+        return (np.arange(self.fft_size, dtype=np.float64) - self.fft_size // 2) * (fs / self.fft_size)
+
+    @property
+    def mean_power(self):
+        return self.sum_power / self.samples_counted if self.samples_counted else 0.0
+
+    @property
+    def enbw(self):
+        """equivalent noise bandwidth of the window in bins: an on-bin tone of amplitude A reads A^2 / enbw"""
+        w = spectrum_window(self.fft_size, self.window).astype(np.float64)
+        return self.fft_size * float((w * w).sum()) / float(w.sum()) ** 2
+
+    def band_power(self, f_lo, f_hi):
+        f = self.freqs()
+        return float(self.psd[(f >= f_lo) & (f <= f_hi)].sum())
+
+    def occupied_bandwidth(self, fraction=0.99):
+        """width in Hz of the narrowest band centred on 0 Hz (2 m + 1 bins) that holds `fraction` of the power"""
+        c, total = self.fft_size // 2, float(self.psd.sum())
+        for m in range(c + 1):
+            if float(self.psd[max(c - m, 0):c + m + 1].sum()) >= fraction * total:
+                return (2 * m + 1) * self.sample_rate / self.fft_size
+        return self.sample_rate
+
+    def _inband(self, half_bandwidth):
+        f = self.freqs()
+        return float(self.psd[np.abs(f) <= 0.9 * half_bandwidth].mean())
+
+    def shoulder_db(self, half_bandwidth, lo=300e3, hi=700e3):
+        """(lower, upper): 10 log10 of the mean PSD over |f| <= 0.9 half_bandwidth divided by the largest PSD bin whose distance from the band edge on that
+        side is in [lo, hi]"""
+        if half_bandwidth + hi > self.sample_rate / 2:
+            raise ValueError("the shoulder's band lies beyond Nyquist")
+        f, inband = self.freqs(), self._inband(half_bandwidth)
+        up = self.psd[(f - half_bandwidth >= lo) & (f - half_bandwidth <= hi)]
+        dn = self.psd[(-f - half_bandwidth >= lo) & (-f - half_bandwidth <= hi)]
+        if not len(up) or not len(dn):
+            raise ValueError("no bin in the shoulder's band")
+        return 10.0 * np.log10(inband / float(dn.max())), 10.0 * np.log10(inband / float(up.max()))
+
+    def ccdf(self):
+        """(levels, prob): the lower edges of histogram bins 1 .. 2039 in dB above the mean power, and the share of the counted samples at or above each"""
+        edges = (np.arange(1, 2040, dtype=np.uint32) << np.uint32(20)).view(np.float32).astype(np.float64)
+        above = np.cumsum(self.hist[::-1].astype(np.float64))[::-1]
+        return 10.0 * np.log10(edges / self.mean_power), above[1:2040] / float(self.samples_counted)
+
+    def papr_db(self, prob=None):
+        """peak over mean in dB; with `prob`, the level that a sample exceeds with that probability (linear in dB between the histogram's bin edges)"""
+        if prob is None:
+            return 10.0 * np.log10(float(self.peak_power) / self.mean_power)
+        lev, p = self.ccdf()
+        j = int(np.argmax(p <= prob))
+        if p[j] > prob:
+            raise ValueError("no level is exceeded that rarely")
+        if j == 0:
+            return float(lev[0])
+        return float(lev[j - 1] + (lev[j] - lev[j - 1]) * (p[j - 1] - prob) / (p[j - 1] - p[j]))
+
+    def mask_margin(self, points, half_bandwidth):
+        """the smallest of (mask - PSD) in dB over a mask of (offset from the centre in Hz, dB relative to the in-band mean) points, linear in Hz between
+        them, applied to both sides; negative where the mask is broken"""
+        pts = sorted((float(o), float(d)) for o, d in points)
+        off, db = np.array([o for o, _ in pts]), np.array([d for _, d in pts])
+        if len(pts) < 2 or off[0] < 0 or off[-1] > self.sample_rate / 2:
+            raise ValueError("a mask is two or more points between 0 and Nyquist")
+        f = np.abs(self.freqs())
+        sel = (f >= off[0]) & (f <= off[-1])
+        with np.errstate(divide="ignore"):
+            rel = 10.0 * np.log10(self.psd[sel] / self._inband(half_bandwidth))
+        return float((np.interp(f[sel], off, db) - rel).min())
+
+
+class Spectrum:
+    """dvbt_spectrum_*: a spectrum analyser on the GPU.  It consumes complex64 baseband as one stream over any number of push() / push_device() calls of any
+    size and accumulates Welch's averaged periodogram (fft_size a power of two in 64..8192, hop in [fft_size / 8, fft_size], None: fft_size / 2; window
+    "rect", "hann" or "blackman-harris") and the statistics of |x|^2 over the first hop samples of every complete segment.  read() synchronises and returns
+    a SpectrumReading; it does not disturb the accumulation.  A stream cut into calls gives the bits of one call."""
+
+    def __init__(self, fft_size=2048, hop=None, window="hann", device=0, sample_rate=64e6 / 7):
+        self.L = _spectrum_lib()
+        if isinstance(window, str):
+            if window.lower() not in SPECTRUM_WINDOWS:
+                raise DvbtError(f"window must be one of {sorted(SPECTRUM_WINDOWS)}")
+            window = SPECTRUM_WINDOWS[window.lower()]
+        self.p = SpectrumParams(int(device), int(fft_size), 0 if hop is None else int(hop), int(window))
+        self.sample_rate = float(sample_rate)
+        self.h = C.c_void_p()
+        _chk(self.L.dvbt_spectrum_create(C.byref(self.p), C.byref(self.h)))
+
+    def push(self, iq):
+        """complex64 samples from the host; continues the stream"""
+        iq = np.ascontiguousarray(iq, dtype=np.complex64).reshape(-1)
+        _chk(self.L.dvbt_spectrum_push(self.h, iq.ctypes.data_as(C.c_void_p), len(iq)))
+
+    def push_device(self, ptr, nsamples, stream=None):
+        """a device pointer (int) to nsamples complex64: enqueues on `stream` (a hipStream_t as int, None: the default stream)"""
+        _chk(self.L.dvbt_spectrum_push_device(self.h, C.c_void_p(ptr), nsamples, C.c_void_p(stream) if stream else None))
+
+    def read(self):
+        r = SpectrumResult()
+        psd, hist = np.zeros(self.p.fft_size, np.float64), np.zeros(SPECTRUM_HIST_BINS, np.uint64)
+        _chk(self.L.dvbt_spectrum_read(self.h, C.byref(r), psd.ctypes.data_as(C.POINTER(C.c_double)), hist.ctypes.data_as(C.POINTER(C.c_ulonglong))))
+        return SpectrumReading(psd, hist, r.segments, r.samples_pushed, r.samples_counted, r.nonfinite, r.sum_power, r.peak_power, self.p.fft_size,
+                               self.p.hop or self.p.fft_size // 2, self.p.window, self.sample_rate)
+
+    def reset(self):
+        _chk(self.L.dvbt_spectrum_reset(self.h))
+
+    def close(self):
+        if self.h:
+            self.L.dvbt_spectrum_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 # ------------------------------------------------------------------ per-block C ABI (one triple per reference block)
 TAG_SYNC_START, TAG_SUPERFRAME_START, TAG_SYMBOL_INDEX = 1, 2, 3
 

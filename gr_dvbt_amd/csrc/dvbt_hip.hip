@@ -30,6 +30,7 @@
 #include "k_clock.hpp"
 #include "k_fading.hpp"
 #include "k_rf.hpp"
+#include "k_spectrum.hpp"
 
 using namespace dvbt;
 using hip_own::DevMem; using hip_own::PinMem; using hip_own::Stream; using hip_own::Event;
@@ -2018,3 +2019,4 @@ extern "C" int dvbt_debug_acquire(dvbt_rx *h, const void *iq_host, size_t nsampl
 #include "dvbt_clock.inc"
 #include "dvbt_fading.inc"
 #include "dvbt_rf.inc"
+#include "dvbt_spectrum.inc"

@@ -1106,6 +1106,41 @@ int  dvbt_rf_run_device(dvbt_rf *h, const void *iq_device, size_t n, void *out_d
 int  dvbt_rf_reset(dvbt_rf *h);   /* back to first_sample */
 void dvbt_rf_destroy(dvbt_rf *h);
 
+/* ------------------------------------------------------------------ spectrum: Welch's averaged periodogram, power sum, peak and a histogram of |x|^2
+ * A measurement block (csrc/k_spectrum.hpp): it consumes complex64 baseband as a stream, changes nothing and accumulates on the device, in one pass.
+ *   Segments   segment k is the stream's samples [k hop, k hop + N), counted from the first sample pushed since create or reset.  N = fft_size, a power of
+ *              two in 64..8192; hop in [N / 8, N], 0 = N / 2.  S = the number of complete segments.
+ *   Window     0 rectangular, 1 Hann, 2 four-term Blackman-Harris (0.35875, 0.48829, 0.14128, 0.01168); periodic (the argument is n / N), computed in
+ *              double and rounded to a float table w.
+ *   PSD        psd[b] = sum_k |X_k[(b - N/2) mod N]|^2 / (S N sum w^2),  X_k = FFT(w x_k): fft-shifted as dvbt_fft, power per bin, so that sum_b psd[b]
+ *              is the mean power of a stationary signal.  The equivalent noise bandwidth is N sum w^2 / (sum w)^2 bins: an on-bin tone of amplitude A
+ *              reads A^2 / ENBW.  S = 0 reads a zero PSD.
+ *   Statistics cover exactly the samples [0, S hop) -- the first hop samples of every complete segment -- once each: sum_power = sum |x|^2 (double),
+ *              peak_power = max |x|^2, hist[float_bits(|x|^2) >> 20]++ with |x|^2 = fmaf(re, re, im im) in float and the sign bit (which only a NaN can
+ *              carry) dropped: 8 bins per octave over the whole float range, no scale and no clamping.  Bins 2040.. hold inf and NaN (`nonfinite`); a NaN
+ *              in the counted range makes sum_power NaN and peak_power a NaN.
+ * A stream cut into calls of any sizes (1 and 0 included, shorter than hop, 8-byte aligned only) gives the PSD, sums and histogram of one call, bit for
+ * bit, through either entry, on any device: sums are formed in an order fixed by the stream (groups of 32 segments in float, the groups in ascending order in
+ * double), never by atomics in floating point.  dvbt_spectrum_read synchronises and does not disturb the accumulation.  dvbt_spectrum_push_device only
+ * enqueues on `stream`; calls on different streams are ordered by the handle (an event).  n <= 2^31 per call, 2^56 per stream.  One thread per handle.  Every
+ * parameter is checked before the device is asked for: a bad struct is DVBT_ERR_INVALID everywhere, a good one DVBT_ERR_NO_DEVICE without a GPU -- there is
+ * no CPU path.  A failed call leaves the state as it was. */
+enum { DVBT_SPECTRUM_HIST_BINS = 2048 };
+typedef struct { int device, fft_size, hop, window; } dvbt_spectrum_params;
+typedef struct {
+  long long segments, samples_pushed, samples_counted, nonfinite;
+  double sum_power;
+  float peak_power;
+} dvbt_spectrum_result;
+typedef struct dvbt_spectrum dvbt_spectrum;
+int  dvbt_spectrum_create(const dvbt_spectrum_params *p, dvbt_spectrum **out);
+int  dvbt_spectrum_push(dvbt_spectrum *h, const void *iq_host, size_t n);
+int  dvbt_spectrum_push_device(dvbt_spectrum *h, const void *iq_device, size_t n, void *stream);
+int  dvbt_spectrum_read(dvbt_spectrum *h, dvbt_spectrum_result *result, double *psd /* fft_size, may be NULL */,
+                        unsigned long long *hist /* DVBT_SPECTRUM_HIST_BINS, may be NULL */);
+int  dvbt_spectrum_reset(dvbt_spectrum *h);   /* back to the state after create */
+void dvbt_spectrum_destroy(dvbt_spectrum *h);
+
 #ifdef __cplusplus
 }
 #endif
