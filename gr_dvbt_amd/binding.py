@@ -453,6 +453,56 @@ class RxStream:
             pass
 
 
+def _typed_once(set_types):
+    """set_types(L) declares a block's argtypes; the decorated name returns the library with them declared, once per load"""
+    mark = "_typed" + set_types.__name__
+
+    def get():
+        L = lib()
+        if not getattr(L, mark, False):
+            set_types(L)
+            setattr(L, mark, True)
+        return L
+    return get
+
+
+class _Handle:
+    """What the streaming handles share: the library self.L, the handle self.h (both set by the subclass's __init__) and the C prefix of its entries."""
+    _prefix = None
+
+    def _fn(self, name):
+        return getattr(self.L, f"{self._prefix}_{name}")
+
+    def reset(self):
+        _chk(self._fn("reset")(self.h))
+
+    def close(self):
+        if self.h:
+            self._fn("destroy")(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class _SampleBlock(_Handle):
+    """a handle whose call takes n complex64 and returns n"""
+
+    def run(self, iq):
+        """complex64 samples in, as many out; continues the stream"""
+        iq = np.ascontiguousarray(iq, dtype=np.complex64).reshape(-1)
+        out = np.empty_like(iq)
+        _chk(self._fn("run")(self.h, iq.ctypes.data_as(C.c_void_p), len(iq), out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def run_device(self, in_ptr, nsamples, out_ptr, stream=None):
+        """device pointers (ints) to nsamples complex64 each, not overlapping: enqueues on `stream` (a hipStream_t as int, None: the default stream)"""
+        _chk(self._fn("run_device")(self.h, C.c_void_p(in_ptr), nsamples, C.c_void_p(out_ptr), C.c_void_p(stream) if stream else None))
+
+
 TX_SCALE = 0.0022097087      # multiply_const behind the cyclic prefixer in apps/dvbt_tx_demo*.grc
 
 
@@ -462,25 +512,23 @@ class TxParams(C.Structure):
                 ("max_packets", C.c_size_t), ("first_packet", C.c_int64), ("keep_carriers", C.c_int), ("device", C.c_int)]
 
 
-def _tx_lib():
-    L = lib()
-    if not getattr(L, "_tx_typed", False):
-        L.dvbt_tx_create.argtypes = [C.POINTER(TxParams), C.POINTER(C.c_void_p)]
-        L.dvbt_tx_samples_for.restype = C.c_int64
-        L.dvbt_tx_samples_for.argtypes = [C.c_void_p, C.c_size_t]
-        L.dvbt_tx_run.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
-        L.dvbt_tx_run_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(C.c_size_t)]
-        L.dvbt_tx_read_carriers.restype = C.c_int64
-        L.dvbt_tx_read_carriers.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
-        L.dvbt_tx_reset.argtypes = [C.c_void_p]
-        L.dvbt_tx_destroy.argtypes = [C.c_void_p]
-        L._tx_typed = True
-    return L
+@_typed_once
+def _tx_lib(L):
+    L.dvbt_tx_create.argtypes = [C.POINTER(TxParams), C.POINTER(C.c_void_p)]
+    L.dvbt_tx_samples_for.restype = C.c_int64
+    L.dvbt_tx_samples_for.argtypes = [C.c_void_p, C.c_size_t]
+    L.dvbt_tx_run.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
+    L.dvbt_tx_run_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(C.c_size_t)]
+    L.dvbt_tx_read_carriers.restype = C.c_int64
+    L.dvbt_tx_read_carriers.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+    L.dvbt_tx_reset.argtypes = [C.c_void_p]
+    L.dvbt_tx_destroy.argtypes = [C.c_void_p]
 
 
-class Tx:
+class Tx(_Handle):
     """dvbt_tx_*: the modulator of apps/dvbt_tx_demo*.grc on the GPU.  One transport stream, delivered over any number of run() /
     run_device() calls of any number of 188-byte packets; the concatenated outputs are those of one run over the whole stream."""
+    _prefix = "dvbt_tx"
 
     def __init__(self, constellation, code_rate, mode, guard=G1_32, hierarchy=NH, include_cell_id=0, cell_id=0, scale=TX_SCALE,
                  max_packets=1 << 16, first_packet=0, keep_carriers=False, device=0):
@@ -521,20 +569,6 @@ class Tx:
             _chk(self.L.dvbt_tx_read_carriers(self.h, out.ctypes.data_as(C.c_void_p), nbytes))
         return out.reshape(-1, self.dims.fft_length)
 
-    def reset(self):
-        _chk(self.L.dvbt_tx_reset(self.h))
-
-    def close(self):
-        if self.h:
-            self.L.dvbt_tx_destroy(self.h)
-            self.h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 CHANNEL_MAX_PATHS, CHANNEL_MAX_DELAY = 8, 8192
 
@@ -544,24 +578,22 @@ class ChannelParams(C.Structure):
                 ("fft_length", C.c_int), ("noise_sigma", C.c_float), ("seed", C.c_uint64), ("first_sample", C.c_int64), ("device", C.c_int)]
 
 
-def _channel_lib():
-    L = lib()
-    if not getattr(L, "_channel_typed", False):
-        L.dvbt_channel_create.argtypes = [C.POINTER(ChannelParams), C.POINTER(C.c_void_p)]
-        L.dvbt_channel_run.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
-        L.dvbt_channel_run_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
-        L.dvbt_channel_power.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(C.c_double)]
-        L.dvbt_channel_reset.argtypes = [C.c_void_p]
-        L.dvbt_channel_destroy.argtypes = [C.c_void_p]
-        L._channel_typed = True
-    return L
+@_typed_once
+def _channel_lib(L):
+    L.dvbt_channel_create.argtypes = [C.POINTER(ChannelParams), C.POINTER(C.c_void_p)]
+    L.dvbt_channel_run.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+    L.dvbt_channel_run_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+    L.dvbt_channel_power.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(C.c_double)]
+    L.dvbt_channel_reset.argtypes = [C.c_void_p]
+    L.dvbt_channel_destroy.argtypes = [C.c_void_p]
 
 
-class Channel:
+class Channel(_SampleBlock):
     """dvbt_channel_*: static echoes, a carrier offset and seeded AWGN on complex64 baseband, on the GPU.  echoes: ((delay in samples, complex amplitude), ...)
     of the extra paths; cfo in subcarrier spacings of an fft_length-point symbol; noise_sigma per component (Channel.sigma for an SNR).  One stream, delivered
     over any number of run() / run_device() calls of any size; the concatenated outputs are bit for bit those of one call.  The noise of a sample depends on
     (seed, first_sample + its index) alone."""
+    _prefix = "dvbt_channel"
 
     def __init__(self, echoes=(), cfo=0.0, fft_length=0, noise_sigma=0.0, seed=0, first_sample=0, device=0):
         self.L = _channel_lib()
@@ -583,54 +615,26 @@ class Channel:
         """the noise's standard deviation per component for an SNR of snr_db relative to ref_power (power())"""
         return float(np.sqrt(ref_power / 10.0 ** (snr_db / 10.0) / 2.0))
 
-    def run(self, iq):
-        """complex64 samples in, as many out; continues the stream"""
-        iq = np.ascontiguousarray(iq, dtype=np.complex64).reshape(-1)
-        out = np.empty_like(iq)
-        _chk(self.L.dvbt_channel_run(self.h, iq.ctypes.data_as(C.c_void_p), len(iq), out.ctypes.data_as(C.c_void_p)))
-        return out
-
-    def run_device(self, in_ptr, nsamples, out_ptr, stream=None):
-        """device pointers (ints) to nsamples complex64 each, not overlapping: enqueues on `stream` (a hipStream_t as int, None: the default stream)"""
-        _chk(self.L.dvbt_channel_run_device(self.h, C.c_void_p(in_ptr), nsamples, C.c_void_p(out_ptr), C.c_void_p(stream) if stream else None))
-
     def power(self, ptr, nsamples, stream=None):
         """mean |x|^2 of nsamples complex64 at the device pointer `ptr`: the ref_power of sigma().  Synchronises `stream`."""
         v = C.c_double()
         _chk(self.L.dvbt_channel_power(self.h, C.c_void_p(ptr), nsamples, C.c_void_p(stream) if stream else None, C.byref(v)))
         return v.value
 
-    def reset(self):
-        _chk(self.L.dvbt_channel_reset(self.h))
-
-    def close(self):
-        if self.h:
-            self.L.dvbt_channel_destroy(self.h)
-            self.h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 class ClockParams(C.Structure):
     _fields_ = [("ppm", C.c_double), ("start", C.c_double), ("taps", C.c_int), ("first_out", C.c_int64), ("first_in", C.c_int64), ("device", C.c_int)]
 
 
-def _clock_lib():
-    L = lib()
-    if not getattr(L, "_clock_typed", False):
-        L.dvbt_clock_outputs.argtypes = [C.POINTER(ClockParams), C.c_int64, C.POINTER(C.c_int64)]
-        L.dvbt_clock_create.argtypes = [C.POINTER(ClockParams), C.POINTER(C.c_void_p)]
-        L.dvbt_clock_outputs_for.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
-        L.dvbt_clock_run.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
-        L.dvbt_clock_run_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p]
-        L.dvbt_clock_reset.argtypes = [C.c_void_p]
-        L.dvbt_clock_destroy.argtypes = [C.c_void_p]
-        L._clock_typed = True
-    return L
+@_typed_once
+def _clock_lib(L):
+    L.dvbt_clock_outputs.argtypes = [C.POINTER(ClockParams), C.c_int64, C.POINTER(C.c_int64)]
+    L.dvbt_clock_create.argtypes = [C.POINTER(ClockParams), C.POINTER(C.c_void_p)]
+    L.dvbt_clock_outputs_for.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
+    L.dvbt_clock_run.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
+    L.dvbt_clock_run_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p]
+    L.dvbt_clock_reset.argtypes = [C.c_void_p]
+    L.dvbt_clock_destroy.argtypes = [C.c_void_p]
 
 
 def clock_outputs(params, n_in_total):
@@ -640,11 +644,12 @@ def clock_outputs(params, n_in_total):
     return n.value
 
 
-class ClockOffset:
+class ClockOffset(_Handle):
     """dvbt_clock_*: complex64 baseband as a receiver whose sample clock is off by `ppm` sees it, y[m] = x(start + m (1 + ppm 1e-6)) by windowed-sinc
     interpolation over `taps` samples, on the GPU.  start=None: taps // 2, the alignment of the test oracle's resampler.  One stream, delivered over any
     number of run() / run_device() calls of any size; the concatenated outputs are bit for bit those of one call.  first_out / first_in: the absolute numbers of
     the stream's first output and input (a piece of a cut stream)."""
+    _prefix = "dvbt_clock"
 
     def __init__(self, ppm, start=None, taps=16, first_out=0, first_in=0, device=0):
         self.L = _clock_lib()
@@ -672,20 +677,6 @@ class ClockOffset:
         _chk(self.L.dvbt_clock_run_device(self.h, C.c_void_p(in_ptr), n_in, C.c_void_p(out_ptr), out_cap, C.byref(n), C.c_void_p(stream) if stream else None))
         return n.value
 
-    def reset(self):
-        _chk(self.L.dvbt_clock_reset(self.h))
-
-    def close(self):
-        if self.h:
-            self.L.dvbt_clock_destroy(self.h)
-            self.h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 FADING_MAX_PATHS, FADING_MAX_DELAY, FADING_MAX_SINUSOIDS, FADING_KNOT = 24, 8192, 32, 64
 TU6_DELAYS_US = (0.0, 0.2, 0.5, 1.6, 2.3, 5.0)          # COST 207 TU6
@@ -711,17 +702,14 @@ class FadingParams(C.Structure):
         return p
 
 
-def _fading_lib():
-    L = lib()
-    if not getattr(L, "_fading_typed", False):
-        L.dvbt_fading_table.argtypes = [C.POINTER(FadingParams), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
-        L.dvbt_fading_create.argtypes = [C.POINTER(FadingParams), C.POINTER(C.c_void_p)]
-        L.dvbt_fading_run.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
-        L.dvbt_fading_run_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
-        L.dvbt_fading_reset.argtypes = [C.c_void_p]
-        L.dvbt_fading_destroy.argtypes = [C.c_void_p]
-        L._fading_typed = True
-    return L
+@_typed_once
+def _fading_lib(L):
+    L.dvbt_fading_table.argtypes = [C.POINTER(FadingParams), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    L.dvbt_fading_create.argtypes = [C.POINTER(FadingParams), C.POINTER(C.c_void_p)]
+    L.dvbt_fading_run.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+    L.dvbt_fading_run_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+    L.dvbt_fading_reset.argtypes = [C.c_void_p]
+    L.dvbt_fading_destroy.argtypes = [C.c_void_p]
 
 
 def fading_table(params):
@@ -747,11 +735,12 @@ def tu6_paths(doppler_hz, sample_rate=64e6 / 7, rice_k_db=None):
     return tuple(paths), float(doppler_hz) / float(sample_rate)
 
 
-class Fading:
+class Fading(_SampleBlock):
     """dvbt_fading_*: time-varying multipath on complex64 baseband, on the GPU.  paths: ((delay in samples, fixed part, sigma), ...): every path's gain is
     its fixed part plus a sum of n_sinusoids sinusoids of rms sigma whose frequencies follow Clarke's spectrum up to `doppler` cycles per sample.  One stream,
     delivered over any number of run() / run_device() calls of any size; the concatenated outputs are bit for bit those of one call.  The gain of a sample
     depends on (paths, doppler, n_sinusoids, seed, first_sample + its index) alone.  No noise, no carrier offset: put a Channel behind it."""
+    _prefix = "dvbt_fading"
 
     def __init__(self, paths=((0, 1.0, 0.0),), doppler=0.0, n_sinusoids=16, seed=0, first_sample=0, device=0):
         self.L = _fading_lib()
@@ -764,31 +753,6 @@ class Fading:
         """COST 207 TU6 at a largest Doppler shift of doppler_hz; rice_k_db: a Ricean first path (tu6_paths); kw: n_sinusoids, seed, first_sample, device"""
         paths, doppler = tu6_paths(doppler_hz, sample_rate, rice_k_db)
         return cls(paths, doppler, **kw)
-
-    def run(self, iq):
-        """complex64 samples in, as many out; continues the stream"""
-        iq = np.ascontiguousarray(iq, dtype=np.complex64).reshape(-1)
-        out = np.empty_like(iq)
-        _chk(self.L.dvbt_fading_run(self.h, iq.ctypes.data_as(C.c_void_p), len(iq), out.ctypes.data_as(C.c_void_p)))
-        return out
-
-    def run_device(self, in_ptr, nsamples, out_ptr, stream=None):
-        """device pointers (ints) to nsamples complex64 each, not overlapping: enqueues on `stream` (a hipStream_t as int, None: the default stream)"""
-        _chk(self.L.dvbt_fading_run_device(self.h, C.c_void_p(in_ptr), nsamples, C.c_void_p(out_ptr), C.c_void_p(stream) if stream else None))
-
-    def reset(self):
-        _chk(self.L.dvbt_fading_reset(self.h))
-
-    def close(self):
-        if self.h:
-            self.L.dvbt_fading_destroy(self.h)
-            self.h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 RF_MAX_TONES, RF_MAX_MASK_POINTS = 32, 8
@@ -823,17 +787,14 @@ class RfMask(C.Structure):
     _fields_ = [("n_points", C.c_int), ("offset_hz", C.c_double * 8), ("dbc_hz", C.c_double * 8), ("sample_rate", C.c_double)]
 
 
-def _rf_lib():
-    L = lib()
-    if not getattr(L, "_rf_typed", False):
-        L.dvbt_rf_phase_noise_tones.argtypes = [C.POINTER(RfMask), C.c_int, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_float)]
-        L.dvbt_rf_create.argtypes = [C.POINTER(RfParams), C.POINTER(C.c_void_p)]
-        L.dvbt_rf_run.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
-        L.dvbt_rf_run_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
-        L.dvbt_rf_reset.argtypes = [C.c_void_p]
-        L.dvbt_rf_destroy.argtypes = [C.c_void_p]
-        L._rf_typed = True
-    return L
+@_typed_once
+def _rf_lib(L):
+    L.dvbt_rf_phase_noise_tones.argtypes = [C.POINTER(RfMask), C.c_int, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_float)]
+    L.dvbt_rf_create.argtypes = [C.POINTER(RfParams), C.POINTER(C.c_void_p)]
+    L.dvbt_rf_run.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+    L.dvbt_rf_run_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+    L.dvbt_rf_reset.argtypes = [C.c_void_p]
+    L.dvbt_rf_destroy.argtypes = [C.c_void_p]
 
 
 def phase_noise_tones(points, n_tones=32, seed=0, sample_rate=64e6 / 7):
@@ -854,11 +815,12 @@ def phase_noise_tones(points, n_tones=32, seed=0, sample_rate=64e6 / 7):
     return inc, ph, amp
 
 
-class RfFrontend:
+class RfFrontend(_SampleBlock):
     """dvbt_rf_*: what the radio hardware does to complex64 baseband, on the GPU, in this order: the transmitter's amplifier (Rapp AM/AM with saturation
     amplitude sat_amplitude and smoothness p; 0: off), oscillator phase noise as a sum of `tones` (phase_noise_tones; None: off), the tuner's IQ imbalance
     v = mu r + nu conj(r) (iq_imbalance) and its DC offset.  One stream, delivered over any number of run() / run_device() calls of any size; the
     concatenated outputs are bit for bit those of one call.  A sample's output depends on (the parameters, first_sample + its index, the sample) alone."""
+    _prefix = "dvbt_rf"
 
     def __init__(self, sat_amplitude=0.0, smoothness=2.0, tones=None, mu=1, nu=0, dc=0, first_sample=0, device=0):
         self.L = _rf_lib()
@@ -877,31 +839,10 @@ class RfFrontend:
         g, psi = 10.0 ** (gain_db / 20.0), np.deg2rad(phase_deg)
         return complex((1.0 + g * np.exp(-1j * psi)) / 2.0), complex((1.0 - g * np.exp(1j * psi)) / 2.0)
 
-    def run(self, iq):
-        """complex64 samples in, as many out; continues the stream"""
-        iq = np.ascontiguousarray(iq, dtype=np.complex64).reshape(-1)
-        out = np.empty_like(iq)
-        _chk(self.L.dvbt_rf_run(self.h, iq.ctypes.data_as(C.c_void_p), len(iq), out.ctypes.data_as(C.c_void_p)))
-        return out
-
     def run_device(self, in_ptr, nsamples, out_ptr, stream=None):
         """device pointers (ints) to nsamples complex64 each, the same buffer (in place) or not overlapping: enqueues on `stream` (a hipStream_t as int,
         None: the default stream)"""
-        _chk(self.L.dvbt_rf_run_device(self.h, C.c_void_p(in_ptr), nsamples, C.c_void_p(out_ptr), C.c_void_p(stream) if stream else None))
-
-    def reset(self):
-        _chk(self.L.dvbt_rf_reset(self.h))
-
-    def close(self):
-        if self.h:
-            self.L.dvbt_rf_destroy(self.h)
-            self.h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        super().run_device(in_ptr, nsamples, out_ptr, stream)
 
 
 SPECTRUM_HIST_BINS = 2048
@@ -917,17 +858,14 @@ class SpectrumResult(C.Structure):
                 ("sum_power", C.c_double), ("peak_power", C.c_float)]
 
 
-def _spectrum_lib():
-    L = lib()
-    if not getattr(L, "_spectrum_typed", False):
-        L.dvbt_spectrum_create.argtypes = [C.POINTER(SpectrumParams), C.POINTER(C.c_void_p)]
-        L.dvbt_spectrum_push.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
-        L.dvbt_spectrum_push_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
-        L.dvbt_spectrum_read.argtypes = [C.c_void_p, C.POINTER(SpectrumResult), C.POINTER(C.c_double), C.POINTER(C.c_ulonglong)]
-        L.dvbt_spectrum_reset.argtypes = [C.c_void_p]
-        L.dvbt_spectrum_destroy.argtypes = [C.c_void_p]
-        L._spectrum_typed = True
-    return L
+@_typed_once
+def _spectrum_lib(L):
+    L.dvbt_spectrum_create.argtypes = [C.POINTER(SpectrumParams), C.POINTER(C.c_void_p)]
+    L.dvbt_spectrum_push.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+    L.dvbt_spectrum_push_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+    L.dvbt_spectrum_read.argtypes = [C.c_void_p, C.POINTER(SpectrumResult), C.POINTER(C.c_double), C.POINTER(C.c_ulonglong)]
+    L.dvbt_spectrum_reset.argtypes = [C.c_void_p]
+    L.dvbt_spectrum_destroy.argtypes = [C.c_void_p]
 
 
 def spectrum_window(fft_size, window):
@@ -1030,11 +968,12 @@ class SpectrumReading:
         return float((np.interp(f[sel], off, db) - rel).min())
 
 
-class Spectrum:
+class Spectrum(_Handle):
     """dvbt_spectrum_*: a spectrum analyser on the GPU.  It consumes complex64 baseband as one stream over any number of push() / push_device() calls of any
     size and accumulates Welch's averaged periodogram (fft_size a power of two in 64..8192, hop in [fft_size / 8, fft_size], None: fft_size / 2; window
     "rect", "hann" or "blackman-harris") and the statistics of |x|^2 over the first hop samples of every complete segment.  read() synchronises and returns
     a SpectrumReading; it does not disturb the accumulation.  A stream cut into calls gives the bits of one call."""
+    _prefix = "dvbt_spectrum"
 
     def __init__(self, fft_size=2048, hop=None, window="hann", device=0, sample_rate=64e6 / 7):
         self.L = _spectrum_lib()
@@ -1062,20 +1001,6 @@ class Spectrum:
         _chk(self.L.dvbt_spectrum_read(self.h, C.byref(r), psd.ctypes.data_as(C.POINTER(C.c_double)), hist.ctypes.data_as(C.POINTER(C.c_ulonglong))))
         return SpectrumReading(psd, hist, r.segments, r.samples_pushed, r.samples_counted, r.nonfinite, r.sum_power, r.peak_power, self.p.fft_size,
                                self.p.hop or self.p.fft_size // 2, self.p.window, self.sample_rate)
-
-    def reset(self):
-        _chk(self.L.dvbt_spectrum_reset(self.h))
-
-    def close(self):
-        if self.h:
-            self.L.dvbt_spectrum_destroy(self.h)
-            self.h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 # ------------------------------------------------------------------ per-block C ABI (one triple per reference block)

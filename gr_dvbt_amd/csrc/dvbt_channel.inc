@@ -1,22 +1,17 @@
-// dvbt_channel.inc -- dvbt_channel_*: static echoes, a carrier offset and seeded AWGN between a modulator and a receiver, as one streaming entry over
-// k_channel.hpp.  Included from dvbt_hip.hip.
+// dvbt_channel.inc -- dvbt_channel_*: static echoes, a carrier offset and seeded AWGN between a modulator and a receiver, as one streaming handle
+// (DESIGN.md 4i) over k_channel.hpp.  Included from dvbt_hip.hip.
 //
-// A handle carries one stream over any number of calls.  What it keeps from call to call: the number of samples it has seen (the absolute index of the next
-// one = first_sample + pos: the noise and the phase are functions of it) and -- on the device -- the last CH_MAX_DELAY input samples, in two buffers written
-// alternately (a call reads one and writes the other).  Every check is made before anything is queued, and the members change only behind the last launch, so
-// a failed call leaves the stream where it was.  dvbt_channel_run_device only enqueues.
+// What a handle keeps from call to call: the number of samples it has seen (the absolute index of the next one = first_sample + pos: the noise and the phase
+// are functions of it) and -- on the device -- the last CH_MAX_DELAY input samples, in two buffers written alternately (a call reads one and writes the other).
 
 struct dvbt_channel {
-  // Released in reverse order of declaration: the buffers first, then the event, the stream last (as dvbt_tx).
   dvbt_channel_params p;
   ChannelArgs a;
-  Stream s;                           // the host entry's stream
-  Event ev; hipStream_t last_stream = nullptr; bool have_ev = false;
   DevMem<float2> hist[2]; int cur = 0;
   long long pos = 0;                  // samples since first_sample
   DevMem<double> partial, result;     // dvbt_channel_power
   DevBuf din, dout;                   // staging of the host entry
-  ~dvbt_channel() { if (have_ev) (void)hipEventSynchronize(ev); }
+  CallOrder ord;                      // last: see CallOrder
 };
 
 namespace {
@@ -47,29 +42,17 @@ inline int channel_check_params(const dvbt_channel_params *p)
 // back to first_sample: zero history in the buffer the next call reads
 inline int channel_rewind(dvbt_channel *h)
 {
-  if (h->have_ev) HIPCHK(hipEventSynchronize(h->ev));
-  HIPCHK(hipMemsetAsync(h->hist[h->cur], 0, sizeof(float2) * CH_MAX_DELAY, h->s));
-  HIPCHK(hipEventRecord(h->ev, h->s));
-  h->last_stream = h->s; h->have_ev = true; h->pos = 0;
-  return DVBT_OK;
-}
-
-// in_place_ok: a memoryless block (dvbt_rf) takes one buffer as input and output; ranges that overlap in any other way are refused everywhere
-inline int channel_check_call(const void *in, size_t n, const void *out, bool in_place_ok = false)
-{
-  if (n == 0) return DVBT_OK;
-  if (!in || !out) return fail(DVBT_ERR_INVALID, "null buffer");
-  if (n > (size_t)1 << 31) return fail(DVBT_ERR_INVALID, "n must be <= 2^31 per call (a longer stream continues over calls)");
-  if (((uintptr_t)in & 7) || ((uintptr_t)out & 7)) return fail(DVBT_ERR_INVALID, "the sample buffers must be 8-byte aligned");
-  const uintptr_t a = (uintptr_t)in, b = (uintptr_t)out, bytes = n * sizeof(float2);
-  if (a < b + bytes && b < a + bytes && !(in_place_ok && a == b)) return fail(DVBT_ERR_INVALID, "the input and output ranges overlap");
+  HIPCHK(h->ord.drain());
+  HIPCHK(hipMemsetAsync(h->hist[h->cur], 0, sizeof(float2) * CH_MAX_DELAY, h->ord.s));
+  HIPCHK(h->ord.mark(h->ord.s));
+  h->pos = 0;
   return DVBT_OK;
 }
 
 // the call's launch on stream st; the caller has checked the buffers.  0 < n <= 2^31.
 inline int channel_enqueue(dvbt_channel *h, const float2 *in, long long n, float2 *out, hipStream_t st)
 {
-  if (h->have_ev && st != h->last_stream) HIPCHK(hipStreamWaitEvent(st, h->ev, 0));   // the previous call ran on another stream
+  HIPCHK(h->ord.join(st));
   const int nxt = h->cur ^ 1;
   const long long n0 = (long long)h->p.first_sample + h->pos;
   const long long p_first = n0 >> 1, npairs = ((n0 + n - 1) >> 1) + 1 - p_first;     // <= 2^30 + 1: one launch
@@ -77,8 +60,7 @@ inline int channel_enqueue(dvbt_channel *h, const float2 *in, long long n, float
   hipLaunchKernelGGL(channel_kernel, dim3(cblocks + CH_HIST_BLOCKS), dim3(CH_THREADS), 0, st, in, out, (const float2 *)h->hist[h->cur], h->hist[nxt].get(), n0, n,
                      p_first, npairs, cblocks, h->a);
   HIPCHK(hipGetLastError());
-  HIPCHK(hipEventRecord(h->ev, st));
-  h->have_ev = true; h->last_stream = st;
+  HIPCHK(h->ord.mark(st));
   h->cur = nxt; h->pos += n;
   return DVBT_OK;
 }
@@ -90,9 +72,7 @@ extern "C" int dvbt_channel_create(const dvbt_channel_params *p, dvbt_channel **
   if (!p || !out) return fail(DVBT_ERR_INVALID, "null argument");
   *out = nullptr;
   int r = channel_check_params(p); if (r) return r;
-  if ((r = need_device())) return r;
-  if (p->device < 0 || p->device >= dvbt_device_count()) return fail(DVBT_ERR_INVALID, "no such device");
-  HIPCHK(hipSetDevice(p->device));
+  if ((r = need_device()) || (r = use_device(p->device))) return r;
 
   std::unique_ptr<dvbt_channel> hold(new dvbt_channel()); dvbt_channel *const h = hold.get();   // released on every early return below
   h->p = *p;
@@ -102,12 +82,11 @@ extern "C" int dvbt_channel_create(const dvbt_channel_params *p, dvbt_channel **
   for (int i = 0; i < p->n_paths; i++) { a.delay[i] = p->delay[i]; a.are[i] = p->amp_re[i]; a.aim[i] = p->amp_im[i]; }
   a.inc = channel_phase_inc(p->cfo, p->fft_length); a.has_cfo = p->cfo != 0.0;
   a.sigma = p->noise_sigma; a.key0 = (uint32_t)p->seed; a.key1 = (uint32_t)(p->seed >> 32);
-  HIPCHK(h->s.create(hipStreamNonBlocking));
-  HIPCHK(h->ev.create(hipEventDisableTiming));
-  for (int i = 0; i < 2; i++) { HIPCHK(h->hist[i].alloc(CH_MAX_DELAY)); HIPCHK(hipMemsetAsync(h->hist[i], 0, sizeof(float2) * CH_MAX_DELAY, h->s)); }
+  HIPCHK(h->ord.create());
+  for (int i = 0; i < 2; i++) { HIPCHK(h->hist[i].alloc(CH_MAX_DELAY)); HIPCHK(hipMemsetAsync(h->hist[i], 0, sizeof(float2) * CH_MAX_DELAY, h->ord.s)); }
   HIPCHK(h->partial.alloc(CH_POW_BLOCKS)); HIPCHK(h->result.alloc(1));
   if ((r = channel_rewind(h))) return r;
-  HIPCHK(hipStreamSynchronize(h->s));
+  HIPCHK(hipStreamSynchronize(h->ord.s));
   *out = hold.release();
   return DVBT_OK;
 }
@@ -115,7 +94,7 @@ extern "C" int dvbt_channel_create(const dvbt_channel_params *p, dvbt_channel **
 extern "C" int dvbt_channel_run_device(dvbt_channel *h, const void *iq_device, size_t n, void *out_device, void *stream)
 {
   if (!h) return fail(DVBT_ERR_INVALID, "null handle");
-  int r = channel_check_call(iq_device, n, out_device); if (r) return r;
+  int r = check_samples(iq_device, n, out_device); if (r) return r;
   if (n == 0) return DVBT_OK;
   HIPCHK(hipSetDevice(h->p.device));
   return channel_enqueue(h, (const float2 *)iq_device, (long long)n, (float2 *)out_device, (hipStream_t)stream);
@@ -124,18 +103,11 @@ extern "C" int dvbt_channel_run_device(dvbt_channel *h, const void *iq_device, s
 extern "C" int dvbt_channel_run(dvbt_channel *h, const void *iq_host, size_t n, void *out_host)
 {
   if (!h) return fail(DVBT_ERR_INVALID, "null handle");
-  int r = channel_check_call(iq_host, n, out_host); if (r) return r;
+  int r = check_samples(iq_host, n, out_host); if (r) return r;
   if (n == 0) return DVBT_OK;
   HIPCHK(hipSetDevice(h->p.device));
-  const size_t bytes = n * sizeof(float2);
-  if (h->have_ev && h->last_stream != h->s) HIPCHK(hipStreamWaitEvent(h->s, h->ev, 0));
-  if ((r = h->din.reserve(bytes))) return r;
-  if ((r = h->dout.reserve(bytes))) return r;
-  HIPCHK(hipMemcpyAsync(h->din.p, iq_host, bytes, hipMemcpyHostToDevice, h->s));
-  if ((r = channel_enqueue(h, (const float2 *)h->din.p, (long long)n, (float2 *)h->dout.p, h->s))) return r;
-  HIPCHK(hipMemcpyAsync(out_host, h->dout.p, bytes, hipMemcpyDeviceToHost, h->s));
-  HIPCHK(hipStreamSynchronize(h->s));
-  return DVBT_OK;
+  return staged_call(h->ord, h->din, h->dout, iq_host, n * sizeof(float2), out_host, n * sizeof(float2), [&](const void *in, void *out) {
+    return channel_enqueue(h, (const float2 *)in, (long long)n, (float2 *)out, h->ord.s); });
 }
 
 extern "C" int dvbt_channel_power(dvbt_channel *h, const void *iq_device, size_t n, void *stream, double *mean_power)
@@ -146,15 +118,14 @@ extern "C" int dvbt_channel_power(dvbt_channel *h, const void *iq_device, size_t
   if ((uintptr_t)iq_device & 7) return fail(DVBT_ERR_INVALID, "the sample buffer must be 8-byte aligned");
   HIPCHK(hipSetDevice(h->p.device));
   const hipStream_t st = (hipStream_t)stream;
-  if (h->have_ev && st != h->last_stream) HIPCHK(hipStreamWaitEvent(st, h->ev, 0));   // the partial sums are the handle's: behind its last call
+  HIPCHK(h->ord.join(st));                        // the partial sums are the handle's: behind its last call
   hipLaunchKernelGGL(channel_power_kernel, dim3(CH_POW_BLOCKS), dim3(CH_THREADS), 0, st, (const float2 *)iq_device, (long long)n, h->partial.get());
   HIPCHK(hipGetLastError());
   hipLaunchKernelGGL(channel_power_final_kernel, dim3(1), dim3(CH_THREADS), 0, st, (const double *)h->partial, (long long)n, h->result.get());
   HIPCHK(hipGetLastError());
   double v = 0.0;
   HIPCHK(hipMemcpyAsync(&v, h->result, sizeof v, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipEventRecord(h->ev, st));
-  h->have_ev = true; h->last_stream = st;
+  HIPCHK(h->ord.mark(st));
   HIPCHK(hipStreamSynchronize(st));
   *mean_power = v;
   return DVBT_OK;

@@ -1,22 +1,18 @@
-// dvbt_clock.inc -- dvbt_clock_*: a sample-clock offset of some ppm between a modulator and a receiver (windowed-sinc resampling), as one streaming entry
-// over k_clock.hpp.  Included from dvbt_hip.hip.
+// dvbt_clock.inc -- dvbt_clock_*: a sample-clock offset of some ppm between a modulator and a receiver (windowed-sinc resampling), as one streaming handle
+// (DESIGN.md 4i) over k_clock.hpp.  Included from dvbt_hip.hip.
 //
-// A handle carries one stream over any number of calls.  What it keeps from call to call: the number of input samples it has seen, the number of the next
-// output (both exact integers: the count a call emits is host arithmetic on them, clock_E of k_clock_math.hpp, so nothing waits for the device) and -- on the
-// device -- the last CLK_HIST input samples, in two buffers written alternately (a call reads one and writes the other).  Every check is made before anything
-// is queued, and the members change only behind the launch, so a failed call leaves the stream where it was.  dvbt_clock_run_device only enqueues.
+// What a handle keeps from call to call: the number of input samples it has seen, the number of the next output (both exact integers: the count a call emits
+// is host arithmetic on them, clock_E of k_clock_math.hpp, so nothing waits for the device) and -- on the device -- the last CLK_HIST input samples, in two
+// buffers written alternately (a call reads one and writes the other).
 
 struct dvbt_clock {
-  // Released in reverse order of declaration: the buffers first, then the event, the stream last (as dvbt_channel).
   dvbt_clock_params p;                // taps already resolved (0 -> 16)
   ClockArgs a;
-  Stream s;                           // the host entry's stream
-  Event ev; hipStream_t last_stream = nullptr; bool have_ev = false;
   DevMem<float2> hist[2]; int cur = 0;
   long long pos = 0;                  // input samples since first_in
   unsigned long long m_next = 0;      // the next output: max(E(first_in + pos), first_out)
   DevBuf din, dout;                   // staging of the host entry
-  ~dvbt_clock() { if (have_ev) (void)hipEventSynchronize(ev); }
+  CallOrder ord;                      // last: see CallOrder
 };
 
 namespace {
@@ -42,10 +38,10 @@ inline unsigned long long clock_next(const ClockStep &c, int taps, long long fir
 // back to first_in / first_out: zero history in the buffer the next call reads
 inline int clock_rewind(dvbt_clock *h)
 {
-  if (h->have_ev) HIPCHK(hipEventSynchronize(h->ev));
-  HIPCHK(hipMemsetAsync(h->hist[h->cur], 0, sizeof(float2) * CLK_HIST, h->s));
-  HIPCHK(hipEventRecord(h->ev, h->s));
-  h->last_stream = h->s; h->have_ev = true; h->pos = 0;
+  HIPCHK(h->ord.drain());
+  HIPCHK(hipMemsetAsync(h->hist[h->cur], 0, sizeof(float2) * CLK_HIST, h->ord.s));
+  HIPCHK(h->ord.mark(h->ord.s));
+  h->pos = 0;
   h->m_next = clock_next(h->a.c, h->p.taps, h->p.first_out, h->p.first_in, 0);
   return DVBT_OK;
 }
@@ -59,9 +55,8 @@ inline int clock_check_call(const dvbt_clock *h, const void *in, size_t n_in, co
   *count = (size_t)(*m_after - h->m_next);
   if (n_in == 0) return DVBT_OK;
   if (!in || (*count && !out)) return fail(DVBT_ERR_INVALID, "null buffer");
-  if (((uintptr_t)in & 7) || ((uintptr_t)out & 7)) return fail(DVBT_ERR_INVALID, "the sample buffers must be 8-byte aligned");
-  const uintptr_t a = (uintptr_t)in, b = (uintptr_t)out, abytes = n_in * sizeof(float2), bbytes = *count * sizeof(float2);
-  if (*count && a < b + bbytes && b < a + abytes) return fail(DVBT_ERR_INVALID, "the input and output ranges overlap");
+  if (misaligned8(in, out)) return fail(DVBT_ERR_INVALID, "the sample buffers must be 8-byte aligned");
+  if (*count && samples_overlap(in, n_in, out, *count)) return fail(DVBT_ERR_INVALID, "the input and output ranges overlap");
   if (out_cap < *count) return fail(DVBT_ERR_CAPACITY, "out_cap is below what the call emits (dvbt_clock_outputs_for)");
   return DVBT_OK;
 }
@@ -69,7 +64,7 @@ inline int clock_check_call(const dvbt_clock *h, const void *in, size_t n_in, co
 // the call's launch on stream st; the caller has checked the buffers.  0 < n_in <= 2^31, count = m_after - m_next outputs.
 inline int clock_enqueue(dvbt_clock *h, const float2 *in, long long n_in, float2 *out, unsigned long long m_after, hipStream_t st)
 {
-  if (h->have_ev && st != h->last_stream) HIPCHK(hipStreamWaitEvent(st, h->ev, 0));   // the previous call ran on another stream
+  HIPCHK(h->ord.join(st));
   const int nxt = h->cur ^ 1;
   const long long n0 = (long long)h->p.first_in + h->pos, nout = (long long)(m_after - h->m_next);    // nout < 2^31 (1 + 2e-3): one launch
   const unsigned cblocks = (unsigned)((nout + CLK_THREADS - 1) / CLK_THREADS);
@@ -81,8 +76,7 @@ inline int clock_enqueue(dvbt_clock *h, const float2 *in, long long n_in, float2
     default: hipLaunchKernelGGL(clock_kernel<64>, grid, block, 0, st, in, out, hist, hist_next, n0, n_in, h->m_next, nout, cblocks, h->a); break;
   }
   HIPCHK(hipGetLastError());
-  HIPCHK(hipEventRecord(h->ev, st));
-  h->have_ev = true; h->last_stream = st;
+  HIPCHK(h->ord.mark(st));
   h->cur = nxt; h->pos += n_in; h->m_next = m_after;
   return DVBT_OK;
 }
@@ -105,9 +99,7 @@ extern "C" int dvbt_clock_create(const dvbt_clock_params *p, dvbt_clock **out)
   if (!p || !out) return fail(DVBT_ERR_INVALID, "null argument");
   *out = nullptr;
   int r = clock_check_params(p); if (r) return r;
-  if ((r = need_device())) return r;
-  if (p->device < 0 || p->device >= dvbt_device_count()) return fail(DVBT_ERR_INVALID, "no such device");
-  HIPCHK(hipSetDevice(p->device));
+  if ((r = need_device()) || (r = use_device(p->device))) return r;
 
   std::unique_ptr<dvbt_clock> hold(new dvbt_clock()); dvbt_clock *const h = hold.get();   // released on every early return below
   h->p = *p; h->p.taps = clock_taps(p);
@@ -120,11 +112,10 @@ extern "C" int dvbt_clock_create(const dvbt_clock_params *p, dvbt_clock **out)
     const double th = M_PI * (double)k / (double)(H + 1), sgn = (k & 1) ? 0.46 : -0.46;      // sin(pi (k - phi)) = -(-1)^k sin(pi phi)
     a.wc[i] = (float)(sgn * cos(th)); a.ws[i] = (float)(sgn * sin(th));
   }
-  HIPCHK(h->s.create(hipStreamNonBlocking));
-  HIPCHK(h->ev.create(hipEventDisableTiming));
-  for (int i = 0; i < 2; i++) { HIPCHK(h->hist[i].alloc(CLK_HIST)); HIPCHK(hipMemsetAsync(h->hist[i], 0, sizeof(float2) * CLK_HIST, h->s)); }
+  HIPCHK(h->ord.create());
+  for (int i = 0; i < 2; i++) { HIPCHK(h->hist[i].alloc(CLK_HIST)); HIPCHK(hipMemsetAsync(h->hist[i], 0, sizeof(float2) * CLK_HIST, h->ord.s)); }
   if ((r = clock_rewind(h))) return r;
-  HIPCHK(hipStreamSynchronize(h->s));
+  HIPCHK(hipStreamSynchronize(h->ord.s));
   *out = hold.release();
   return DVBT_OK;
 }
@@ -156,14 +147,8 @@ extern "C" int dvbt_clock_run(dvbt_clock *h, const void *iq_host, size_t n_in, v
   *n_out = count;
   if (n_in == 0) return DVBT_OK;
   HIPCHK(hipSetDevice(h->p.device));
-  if (h->have_ev && h->last_stream != h->s) HIPCHK(hipStreamWaitEvent(h->s, h->ev, 0));
-  if ((r = h->din.reserve(n_in * sizeof(float2)))) return r;
-  if ((r = h->dout.reserve(count * sizeof(float2)))) return r;
-  HIPCHK(hipMemcpyAsync(h->din.p, iq_host, n_in * sizeof(float2), hipMemcpyHostToDevice, h->s));
-  if ((r = clock_enqueue(h, (const float2 *)h->din.p, (long long)n_in, (float2 *)h->dout.p, m_after, h->s))) return r;
-  if (count) HIPCHK(hipMemcpyAsync(out_host, h->dout.p, count * sizeof(float2), hipMemcpyDeviceToHost, h->s));
-  HIPCHK(hipStreamSynchronize(h->s));
-  return DVBT_OK;
+  return staged_call(h->ord, h->din, h->dout, iq_host, n_in * sizeof(float2), out_host, count * sizeof(float2), [&](const void *in, void *out) {
+    return clock_enqueue(h, (const float2 *)in, (long long)n_in, (float2 *)out, m_after, h->ord.s); });
 }
 
 extern "C" int dvbt_clock_reset(dvbt_clock *h)

@@ -1,39 +1,23 @@
-// dvbt_fading.inc -- dvbt_fading_*: time-varying multipath with a Doppler spectrum between a modulator and a receiver, as one streaming entry over
-// k_fading.hpp.  Included from dvbt_hip.hip, behind dvbt_channel.inc (channel_check_call is shared).
+// dvbt_fading.inc -- dvbt_fading_*: time-varying multipath with a Doppler spectrum between a modulator and a receiver, as one streaming handle
+// (DESIGN.md 4i) over k_fading.hpp.  Included from dvbt_hip.hip.
 //
-// A handle carries one stream over any number of calls, as dvbt_channel does: the number of samples it has seen (the gains are functions of first_sample + pos)
-// and -- on the device -- the last CH_MAX_DELAY input samples in two buffers written alternately.  The sinusoid table is computed on the host in double, by
-// operations whose bits do not depend on the machine (tests/fadingref.py::table is the same arithmetic), and written to the device once at create.  Every
-// check is made before anything is queued, and the members change only behind the launch.  dvbt_fading_run_device only enqueues.
+// What a handle keeps from call to call, as dvbt_channel does: the number of samples it has seen (the gains are functions of first_sample + pos) and -- on
+// the device -- the last CH_MAX_DELAY input samples in two buffers written alternately.  The sinusoid table is computed on the host in double, by operations
+// whose bits do not depend on the machine (tests/fadingref.py::table is the same arithmetic), and written to the device once at create.
 
 struct dvbt_fading {
-  // Released in reverse order of declaration: the buffers first, then the event, the stream last (as dvbt_channel).
   dvbt_fading_params p;
   int M = 0;
-  Stream s;                           // the host entry's stream
-  Event ev; hipStream_t last_stream = nullptr; bool have_ev = false;
   DevMem<float2> hist[2]; int cur = 0;
   long long pos = 0;                  // samples since first_sample
   DevMem<FadePath> paths; DevMem<FadeSin> tab;
   DevBuf din, dout;                   // staging of the host entry
-  ~dvbt_fading() { if (have_ev) (void)hipEventSynchronize(ev); }
+  CallOrder ord;                      // last: see CallOrder
 };
 
 namespace {
 
 constexpr uint32_t FADING_TAG = 0x46414445u;      // "FADE": counter word 3 of the table's Philox blocks; the noise generator's is 0
-
-// Philox4x32-10 on the host (ch_philox is the device's)
-inline void fading_philox(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1, uint32_t w[4])
-{
-  for (int r = 0; r < 10; r++) {
-    const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
-    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
-    c0 = n0; c1 = (uint32_t)p1; c2 = n2; c3 = (uint32_t)p0;
-    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-  }
-  w[0] = c0; w[1] = c1; w[2] = c2; w[3] = c3;
-}
 
 // cos(2 pi alpha) for alpha in [0, 1] from IEEE double + - * / alone, in the order of tests/fadingref.py::cos_turns line by line (the file is built with
 // -ffp-contract=off): the nearest quarter turn comes off, the rest (|x| <= pi / 4) goes through the Taylor series of cos and sin, 12 terms behind the first
@@ -75,7 +59,7 @@ inline void fading_fill_table(const dvbt_fading_params *p, uint64_t *inc, uint64
   for (int i = 0; i < p->n_paths; i++)
     for (int m = 0; m < M; m++) {
       uint32_t w[4];
-      fading_philox((uint32_t)m, (uint32_t)i, 0u, FADING_TAG, (uint32_t)p->seed, (uint32_t)(p->seed >> 32), w);
+      philox4x32_10((uint32_t)m, (uint32_t)i, 0u, FADING_TAG, (uint32_t)p->seed, (uint32_t)(p->seed >> 32), w);
       const double u = ((double)w[0] + 0.5) * 2.3283064365386963e-10;               // 2^-32
       const double alpha = ((double)m + u) / (double)M;
       const double f = p->doppler * fading_cos_turns(alpha);
@@ -88,17 +72,17 @@ inline void fading_fill_table(const dvbt_fading_params *p, uint64_t *inc, uint64
 // back to first_sample: zero history in the buffer the next call reads
 inline int fading_rewind(dvbt_fading *h)
 {
-  if (h->have_ev) HIPCHK(hipEventSynchronize(h->ev));
-  HIPCHK(hipMemsetAsync(h->hist[h->cur], 0, sizeof(float2) * CH_MAX_DELAY, h->s));
-  HIPCHK(hipEventRecord(h->ev, h->s));
-  h->last_stream = h->s; h->have_ev = true; h->pos = 0;
+  HIPCHK(h->ord.drain());
+  HIPCHK(hipMemsetAsync(h->hist[h->cur], 0, sizeof(float2) * CH_MAX_DELAY, h->ord.s));
+  HIPCHK(h->ord.mark(h->ord.s));
+  h->pos = 0;
   return DVBT_OK;
 }
 
 // the call's launch on stream st; the caller has checked the buffers.  0 < n <= 2^31.
 inline int fading_enqueue(dvbt_fading *h, const float2 *in, long long n, float2 *out, hipStream_t st)
 {
-  if (h->have_ev && st != h->last_stream) HIPCHK(hipStreamWaitEvent(st, h->ev, 0));   // the previous call ran on another stream
+  HIPCHK(h->ord.join(st));
   const int nxt = h->cur ^ 1;
   const long long n0 = (long long)h->p.first_sample + h->pos;
   const long long tile0 = n0 & ~(long long)(FD_TILE - 1);
@@ -106,8 +90,7 @@ inline int fading_enqueue(dvbt_fading *h, const float2 *in, long long n, float2 
   hipLaunchKernelGGL(fading_kernel, dim3(cblocks + FD_HIST_BLOCKS), dim3(FD_THREADS), 0, st, in, out, (const float2 *)h->hist[h->cur], h->hist[nxt].get(), n0, n,
                      tile0, cblocks, (const FadePath *)h->paths, (const FadeSin *)h->tab, h->p.n_paths, h->M);
   HIPCHK(hipGetLastError());
-  HIPCHK(hipEventRecord(h->ev, st));
-  h->have_ev = true; h->last_stream = st;
+  HIPCHK(h->ord.mark(st));
   h->cur = nxt; h->pos += n;
   return DVBT_OK;
 }
@@ -127,9 +110,7 @@ extern "C" int dvbt_fading_create(const dvbt_fading_params *p, dvbt_fading **out
   if (!p || !out) return fail(DVBT_ERR_INVALID, "null argument");
   *out = nullptr;
   int r = fading_check_params(p); if (r) return r;
-  if ((r = need_device())) return r;
-  if (p->device < 0 || p->device >= dvbt_device_count()) return fail(DVBT_ERR_INVALID, "no such device");
-  HIPCHK(hipSetDevice(p->device));
+  if ((r = need_device()) || (r = use_device(p->device))) return r;
 
   std::unique_ptr<dvbt_fading> hold(new dvbt_fading()); dvbt_fading *const h = hold.get();   // released on every early return below
   h->p = *p; h->M = fading_sinusoids(p);
@@ -140,14 +121,13 @@ extern "C" int dvbt_fading_create(const dvbt_fading_params *p, dvbt_fading **out
   for (size_t k = 0; k < tab.size(); k++) { tab[k].inc = inc[k]; tab[k].ph = ph[k]; }
   std::vector<FadePath> paths(np);
   for (int i = 0; i < np; i++) paths[i] = FadePath{p->los_re[i], p->los_im[i], (float)((double)p->sigma[i] / sqrt((double)M)), p->delay[i]};
-  HIPCHK(h->s.create(hipStreamNonBlocking));
-  HIPCHK(h->ev.create(hipEventDisableTiming));
-  for (int i = 0; i < 2; i++) { HIPCHK(h->hist[i].alloc(CH_MAX_DELAY)); HIPCHK(hipMemsetAsync(h->hist[i], 0, sizeof(float2) * CH_MAX_DELAY, h->s)); }
+  HIPCHK(h->ord.create());
+  for (int i = 0; i < 2; i++) { HIPCHK(h->hist[i].alloc(CH_MAX_DELAY)); HIPCHK(hipMemsetAsync(h->hist[i], 0, sizeof(float2) * CH_MAX_DELAY, h->ord.s)); }
   HIPCHK(h->paths.alloc(paths.size())); HIPCHK(h->tab.alloc(tab.size()));
-  HIPCHK(hipMemcpyAsync(h->paths, paths.data(), sizeof(FadePath) * paths.size(), hipMemcpyHostToDevice, h->s));
-  HIPCHK(hipMemcpyAsync(h->tab, tab.data(), sizeof(FadeSin) * tab.size(), hipMemcpyHostToDevice, h->s));
+  HIPCHK(hipMemcpyAsync(h->paths, paths.data(), sizeof(FadePath) * paths.size(), hipMemcpyHostToDevice, h->ord.s));
+  HIPCHK(hipMemcpyAsync(h->tab, tab.data(), sizeof(FadeSin) * tab.size(), hipMemcpyHostToDevice, h->ord.s));
   if ((r = fading_rewind(h))) return r;
-  HIPCHK(hipStreamSynchronize(h->s));              // the vectors above are read until here
+  HIPCHK(hipStreamSynchronize(h->ord.s));              // the vectors above are read until here
   *out = hold.release();
   return DVBT_OK;
 }
@@ -155,7 +135,7 @@ extern "C" int dvbt_fading_create(const dvbt_fading_params *p, dvbt_fading **out
 extern "C" int dvbt_fading_run_device(dvbt_fading *h, const void *iq_device, size_t n, void *out_device, void *stream)
 {
   if (!h) return fail(DVBT_ERR_INVALID, "null handle");
-  int r = channel_check_call(iq_device, n, out_device); if (r) return r;
+  int r = check_samples(iq_device, n, out_device); if (r) return r;
   if (n == 0) return DVBT_OK;
   HIPCHK(hipSetDevice(h->p.device));
   return fading_enqueue(h, (const float2 *)iq_device, (long long)n, (float2 *)out_device, (hipStream_t)stream);
@@ -164,18 +144,11 @@ extern "C" int dvbt_fading_run_device(dvbt_fading *h, const void *iq_device, siz
 extern "C" int dvbt_fading_run(dvbt_fading *h, const void *iq_host, size_t n, void *out_host)
 {
   if (!h) return fail(DVBT_ERR_INVALID, "null handle");
-  int r = channel_check_call(iq_host, n, out_host); if (r) return r;
+  int r = check_samples(iq_host, n, out_host); if (r) return r;
   if (n == 0) return DVBT_OK;
   HIPCHK(hipSetDevice(h->p.device));
-  const size_t bytes = n * sizeof(float2);
-  if (h->have_ev && h->last_stream != h->s) HIPCHK(hipStreamWaitEvent(h->s, h->ev, 0));
-  if ((r = h->din.reserve(bytes))) return r;
-  if ((r = h->dout.reserve(bytes))) return r;
-  HIPCHK(hipMemcpyAsync(h->din.p, iq_host, bytes, hipMemcpyHostToDevice, h->s));
-  if ((r = fading_enqueue(h, (const float2 *)h->din.p, (long long)n, (float2 *)h->dout.p, h->s))) return r;
-  HIPCHK(hipMemcpyAsync(out_host, h->dout.p, bytes, hipMemcpyDeviceToHost, h->s));
-  HIPCHK(hipStreamSynchronize(h->s));
-  return DVBT_OK;
+  return staged_call(h->ord, h->din, h->dout, iq_host, n * sizeof(float2), out_host, n * sizeof(float2), [&](const void *in, void *out) {
+    return fading_enqueue(h, (const float2 *)in, (long long)n, (float2 *)out, h->ord.s); });
 }
 
 extern "C" int dvbt_fading_reset(dvbt_fading *h)

@@ -33,7 +33,7 @@
 #include "k_spectrum.hpp"
 
 using namespace dvbt;
-using hip_own::DevMem; using hip_own::PinMem; using hip_own::Stream; using hip_own::Event;
+using hip_own::DevMem; using hip_own::PinMem; using hip_own::Stream; using hip_own::Event; using hip_own::CallOrder;
 
 static thread_local std::string g_err;
 static int fail(int code, const std::string &msg) { g_err = msg; return code; }
@@ -95,6 +95,62 @@ struct DevBuf {          // growable device scratch: `mem` owns it, `p` is what 
     mem = std::move(q); p = mem; cap = n; return DVBT_OK;
   }
 };
+
+// ------------------------------------------------------------------------------------------ streaming handles
+// A host entry: in_bytes from in_host through din, enqueue(din.p, dout.p) on the handle's own stream, out_bytes back to out_host through dout, synchronised.
+// In place: din and dout are one buffer.  Nothing to return: out_bytes = 0.
+template <class Enqueue>
+static int staged_call(CallOrder &ord, DevBuf &din, DevBuf &dout, const void *in_host, size_t in_bytes, void *out_host, size_t out_bytes, Enqueue enqueue)
+{
+  HIPCHK(ord.join(ord.s));
+  int r;
+  if ((r = din.reserve(in_bytes)) || (r = dout.reserve(out_bytes))) return r;
+  HIPCHK(hipMemcpyAsync(din.p, in_host, in_bytes, hipMemcpyHostToDevice, ord.s));
+  if ((r = enqueue(din.p, dout.p))) return r;
+  if (out_bytes) HIPCHK(hipMemcpyAsync(out_host, dout.p, out_bytes, hipMemcpyDeviceToHost, ord.s));
+  HIPCHK(hipStreamSynchronize(ord.s));
+  return DVBT_OK;
+}
+
+// a create's device: in range, and the current one from here on (the caller has asked need_device() where its order of refusals wants it)
+static int use_device(int device)
+{
+  if (device < 0 || device >= dvbt_device_count()) return fail(DVBT_ERR_INVALID, "no such device");
+  HIPCHK(hipSetDevice(device));
+  return DVBT_OK;
+}
+
+// the pieces of a sample-buffer check, for the blocks whose order of refusals differs from check_samples' (dvbt_clock, dvbt_spectrum)
+static bool misaligned8(const void *a, const void *b = nullptr) { return (((uintptr_t)a | (uintptr_t)b) & 7) != 0; }
+static bool samples_overlap(const void *in, size_t n_in, const void *out, size_t n_out)
+{
+  const uintptr_t a = (uintptr_t)in, b = (uintptr_t)out;
+  return a < b + n_out * sizeof(float2) && b < a + n_in * sizeof(float2);
+}
+
+// the buffers of a call of n complex64 in, n out.  in_place_ok: a memoryless block (dvbt_rf) takes one buffer as input and output; ranges that overlap in
+// any other way are refused everywhere
+static int check_samples(const void *in, size_t n, const void *out, bool in_place_ok = false)
+{
+  if (n == 0) return DVBT_OK;
+  if (!in || !out) return fail(DVBT_ERR_INVALID, "null buffer");
+  if (n > (size_t)1 << 31) return fail(DVBT_ERR_INVALID, "n must be <= 2^31 per call (a longer stream continues over calls)");
+  if (misaligned8(in, out)) return fail(DVBT_ERR_INVALID, "the sample buffers must be 8-byte aligned");
+  if (samples_overlap(in, n, out, n) && !(in_place_ok && in == out)) return fail(DVBT_ERR_INVALID, "the input and output ranges overlap");
+  return DVBT_OK;
+}
+
+// Philox4x32-10 on the host (ch_philox is the device's)
+static void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1, uint32_t w[4])
+{
+  for (int r = 0; r < 10; r++) {
+    const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
+    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
+    c0 = n0; c1 = (uint32_t)p1; c2 = n2; c3 = (uint32_t)p0;
+    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+  }
+  w[0] = c0; w[1] = c1; w[2] = c2; w[3] = c3;
+}
 
 struct Tables {          // device lookup tables for one configuration
   Dims d;

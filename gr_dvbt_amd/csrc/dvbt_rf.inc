@@ -1,20 +1,15 @@
 // dvbt_rf.inc -- dvbt_rf_*: the radio hardware on either side of a channel -- the transmitter's amplifier, the oscillator's phase noise, the tuner's IQ
-// imbalance and DC offset -- as one streaming entry over k_rf.hpp.  Included from dvbt_hip.hip, behind dvbt_channel.inc and dvbt_fading.inc (channel_check_call and
-// fading_philox are shared).
+// imbalance and DC offset -- as one streaming handle (DESIGN.md 4i) over k_rf.hpp.  Included from dvbt_hip.hip.
 //
 // The block is memoryless, so all a handle carries from call to call is the number of samples it has seen (the phases are functions of first_sample + pos).
-// Every check is made before anything is queued, and the position changes only behind the launch, so a failed call leaves the stream where it was.
-// dvbt_rf_run_device only enqueues.  dvbt_rf_phase_noise_tones is host arithmetic in double (tests/rfref.py::tones is the same formulas).
+// dvbt_rf_phase_noise_tones is host arithmetic in double (tests/rfref.py::tones is the same formulas).
 
 struct dvbt_rf {
-  // Released in reverse order of declaration: the buffer first, then the event, the stream last (as dvbt_channel).
   dvbt_rf_params p;
   RfArgs a;
-  Stream s;                           // the host entry's stream
-  Event ev; hipStream_t last_stream = nullptr; bool have_ev = false;
   long long pos = 0;                  // samples since first_sample
   DevBuf dio;                         // staging of the host entry: the kernel runs in place on it
-  ~dvbt_rf() { if (have_ev) (void)hipEventSynchronize(ev); }
+  CallOrder ord;                      // last: see CallOrder
 };
 
 namespace {
@@ -59,14 +54,13 @@ inline void rf_fill_args(const dvbt_rf_params *p, RfArgs &a)
 // the call's launch on stream st; the caller has checked the buffers.  0 < n <= 2^31.
 inline int rf_enqueue(dvbt_rf *h, const float2 *in, long long n, float2 *out, hipStream_t st)
 {
-  if (h->have_ev && st != h->last_stream) HIPCHK(hipStreamWaitEvent(st, h->ev, 0));   // the previous call ran on another stream
+  HIPCHK(h->ord.join(st));
   const long long n0 = (long long)h->p.first_sample + h->pos;
   const int lead = (int)(((uintptr_t)out >> 3) & 1);
   const unsigned blocks = (unsigned)((n + lead + RF_TILE - 1) / RF_TILE);             // <= 2^21 + 1: one launch
   hipLaunchKernelGGL(rf_kernel, dim3(blocks), dim3(RF_THREADS), 0, st, in, out, n0, n, lead, h->a);
   HIPCHK(hipGetLastError());
-  HIPCHK(hipEventRecord(h->ev, st));
-  h->have_ev = true; h->last_stream = st;
+  HIPCHK(h->ord.mark(st));
   h->pos += n;
   return DVBT_OK;
 }
@@ -106,7 +100,7 @@ extern "C" int dvbt_rf_phase_noise_tones(const dvbt_rf_mask *mk, int n_tones, ui
   for (int m = 0; m < M; m++) {
     const double lo = m ? f0 * exp(lr * (double)m / (double)M) : f0, hi = m + 1 < M ? f0 * exp(lr * (double)(m + 1) / (double)M) : fl;
     uint32_t w[4];
-    fading_philox((uint32_t)m, 0u, 0u, RF_TAG, (uint32_t)seed, (uint32_t)(seed >> 32), w);
+    philox4x32_10((uint32_t)m, 0u, 0u, RF_TAG, (uint32_t)seed, (uint32_t)(seed >> 32), w);
     const double u = ((double)w[0] + 0.5) * 2.3283064365386963e-10;                 // 2^-32
     const double f = f0 * exp(lr * ((double)m + u) / (double)M);
     inc[m] = (uint64_t)nearbyint(ldexp(f / mk->sample_rate, 64));                    // f / sample_rate <= 1/2: at most 2^63
@@ -121,15 +115,12 @@ extern "C" int dvbt_rf_create(const dvbt_rf_params *p, dvbt_rf **out)
   if (!p || !out) return fail(DVBT_ERR_INVALID, "null argument");
   *out = nullptr;
   int r = rf_check_params(p); if (r) return r;
-  if ((r = need_device())) return r;
-  if (p->device < 0 || p->device >= dvbt_device_count()) return fail(DVBT_ERR_INVALID, "no such device");
-  HIPCHK(hipSetDevice(p->device));
+  if ((r = need_device()) || (r = use_device(p->device))) return r;
 
   std::unique_ptr<dvbt_rf> hold(new dvbt_rf()); dvbt_rf *const h = hold.get();   // released on every early return below
   h->p = *p;
   rf_fill_args(p, h->a);
-  HIPCHK(h->s.create(hipStreamNonBlocking));
-  HIPCHK(h->ev.create(hipEventDisableTiming));
+  HIPCHK(h->ord.create());
   *out = hold.release();
   return DVBT_OK;
 }
@@ -137,7 +128,7 @@ extern "C" int dvbt_rf_create(const dvbt_rf_params *p, dvbt_rf **out)
 extern "C" int dvbt_rf_run_device(dvbt_rf *h, const void *iq_device, size_t n, void *out_device, void *stream)
 {
   if (!h) return fail(DVBT_ERR_INVALID, "null handle");
-  int r = channel_check_call(iq_device, n, out_device, true); if (r) return r;   // in place is fine: the block has no delay line
+  int r = check_samples(iq_device, n, out_device, true); if (r) return r;   // in place is fine: the block has no delay line
   if (n == 0) return DVBT_OK;
   HIPCHK(hipSetDevice(h->p.device));
   return rf_enqueue(h, (const float2 *)iq_device, (long long)n, (float2 *)out_device, (hipStream_t)stream);
@@ -146,17 +137,11 @@ extern "C" int dvbt_rf_run_device(dvbt_rf *h, const void *iq_device, size_t n, v
 extern "C" int dvbt_rf_run(dvbt_rf *h, const void *iq_host, size_t n, void *out_host)
 {
   if (!h) return fail(DVBT_ERR_INVALID, "null handle");
-  int r = channel_check_call(iq_host, n, out_host, true); if (r) return r;
+  int r = check_samples(iq_host, n, out_host, true); if (r) return r;
   if (n == 0) return DVBT_OK;
   HIPCHK(hipSetDevice(h->p.device));
-  const size_t bytes = n * sizeof(float2);
-  if (h->have_ev && h->last_stream != h->s) HIPCHK(hipStreamWaitEvent(h->s, h->ev, 0));
-  if ((r = h->dio.reserve(bytes))) return r;
-  HIPCHK(hipMemcpyAsync(h->dio.p, iq_host, bytes, hipMemcpyHostToDevice, h->s));
-  if ((r = rf_enqueue(h, (const float2 *)h->dio.p, (long long)n, (float2 *)h->dio.p, h->s))) return r;
-  HIPCHK(hipMemcpyAsync(out_host, h->dio.p, bytes, hipMemcpyDeviceToHost, h->s));
-  HIPCHK(hipStreamSynchronize(h->s));
-  return DVBT_OK;
+  return staged_call(h->ord, h->dio, h->dio, iq_host, n * sizeof(float2), out_host, n * sizeof(float2), [&](const void *in, void *out) {
+    return rf_enqueue(h, (const float2 *)in, (long long)n, (float2 *)out, h->ord.s); });
 }
 
 extern "C" int dvbt_rf_reset(dvbt_rf *h)

@@ -1,18 +1,12 @@
 // dvbt_spectrum.inc -- dvbt_spectrum_*: a spectrum analyser for complex64 baseband -- Welch's averaged periodogram, the power sum, the peak and a histogram
-// of |x|^2 -- as one streaming entry over k_spectrum.hpp.  It consumes a stream and changes nothing.  Included from dvbt_hip.hip, behind dvbt_channel.inc
-// (the handle's ordering by an event is dvbt_channel's).
+// of |x|^2 -- as one streaming handle (DESIGN.md 4i) over k_spectrum.hpp.  It consumes a stream and changes nothing.  Included from dvbt_hip.hip.
 //
-// A handle carries one stream over any number of calls.  What it keeps from call to call: the number of samples it has seen (the number of complete segments
-// is host arithmetic on it, so nothing waits for the device) and, on the device, the up to N - 1 samples behind the last complete segment's start, in two
-// buffers written alternately (as dvbt_clock), the open group's state, likewise in two buffers, and the accumulators.  Every check is made before anything is
-// queued and the members change only behind the launches, so a failed call leaves the stream where it was.  dvbt_spectrum_push_device only enqueues;
-// dvbt_spectrum_read synchronises and copies, and changes nothing.
+// What a handle keeps from call to call: the number of samples it has seen (the number of complete segments is host arithmetic on it, so nothing waits for
+// the device) and, on the device, the up to N - 1 samples behind the last complete segment's start, in two buffers written alternately (as dvbt_clock), the
+// open group's state, likewise in two buffers, and the accumulators.  dvbt_spectrum_read synchronises and copies on the handle's own stream, and changes nothing.
 
 struct dvbt_spectrum {
-  // Released in reverse order of declaration: the buffers first, then the event, the stream last (as dvbt_channel).
   dvbt_spectrum_params p;             // hop already resolved (0 -> N/2)
-  Stream s;                           // the host entry's stream, and read's
-  Event ev; hipStream_t last_stream = nullptr; bool have_ev = false;
   DevMem<float> win; DevMem<float2> tw;
   DevMem<float2> hist[2]; int cur = 0;
   DevMem<double> open[2]; int ocur = 0;            // the open group: its power sum, then N floats (the open slab)
@@ -21,7 +15,7 @@ struct dvbt_spectrum {
   double sum_w2 = 0.0;
   DevBuf slabs;                       // the closed groups of one launch: floats [groups][N], then a double per group
   DevBuf din;                         // staging of the host entry
-  ~dvbt_spectrum() { if (have_ev) (void)hipEventSynchronize(ev); }
+  CallOrder ord;                      // last: see CallOrder
 };
 
 namespace {
@@ -65,7 +59,7 @@ inline int spectrum_check_call(const dvbt_spectrum *h, const void *in, size_t n)
   if (!in) return fail(DVBT_ERR_INVALID, "null buffer");
   if (n > (size_t)1 << 31) return fail(DVBT_ERR_INVALID, "n must be <= 2^31 per call (a longer stream continues over calls)");
   if ((long long)n > SPEC_MAX_TOTAL - h->pos) return fail(DVBT_ERR_INVALID, "a stream takes at most 2^56 samples");
-  if ((uintptr_t)in & 7) return fail(DVBT_ERR_INVALID, "the sample buffer must be 8-byte aligned");
+  if (misaligned8(in)) return fail(DVBT_ERR_INVALID, "the sample buffer must be 8-byte aligned");
   return DVBT_OK;
 }
 
@@ -92,7 +86,7 @@ inline int spectrum_enqueue(dvbt_spectrum *h, const float2 *in, long long n, hip
   a.hbase = a.s0 * hop;
   const long long first = a.s1 * hop, cnt = h->pos + n - first;            // what the next call needs: 0 <= cnt < N
   if (a.s1 > a.s0) { int r = h->slabs.reserve((size_t)SPEC_MAX_GROUPS * (N * sizeof(float) + sizeof(double))); if (r) return r; }
-  if (h->have_ev && st != h->last_stream) HIPCHK(hipStreamWaitEvent(st, h->ev, 0));   // the previous call ran on another stream
+  HIPCHK(h->ord.join(st));
   const int nxt = h->cur ^ 1, onxt = h->ocur ^ 1;
   const bool to_open = a.s1 > a.s0 && (a.s1 % SPEC_GROUP) != 0;
   if (a.s1 > a.s0) {
@@ -122,8 +116,7 @@ inline int spectrum_enqueue(dvbt_spectrum *h, const float2 *in, long long n, hip
                        first, (int)cnt, (float2 *)h->hist[nxt]);
     HIPCHK(hipGetLastError());
   }
-  HIPCHK(hipEventRecord(h->ev, st));
-  h->have_ev = true; h->last_stream = st;
+  HIPCHK(h->ord.mark(st));
   if (cnt > 0) h->cur = nxt;
   if (to_open) h->ocur = onxt;
   h->pos += n;
@@ -133,10 +126,10 @@ inline int spectrum_enqueue(dvbt_spectrum *h, const float2 *in, long long n, hip
 // back to the state after create: the accumulators zeroed (the history and the open group are not read before they are written again)
 inline int spectrum_rewind(dvbt_spectrum *h)
 {
-  if (h->have_ev) HIPCHK(hipEventSynchronize(h->ev));
-  HIPCHK(hipMemsetAsync(h->res, 0, sizeof(double) * spec_res_doubles(h->p.fft_size), h->s));
-  HIPCHK(hipEventRecord(h->ev, h->s));
-  h->last_stream = h->s; h->have_ev = true; h->pos = 0;
+  HIPCHK(h->ord.drain());
+  HIPCHK(hipMemsetAsync(h->res, 0, sizeof(double) * spec_res_doubles(h->p.fft_size), h->ord.s));
+  HIPCHK(h->ord.mark(h->ord.s));
+  h->pos = 0;
   return DVBT_OK;
 }
 
@@ -147,9 +140,7 @@ extern "C" int dvbt_spectrum_create(const dvbt_spectrum_params *p, dvbt_spectrum
   if (!p || !out) return fail(DVBT_ERR_INVALID, "null argument");
   *out = nullptr;
   int r = spectrum_check_params(p); if (r) return r;
-  if ((r = need_device())) return r;
-  if (p->device >= dvbt_device_count()) return fail(DVBT_ERR_INVALID, "no such device");
-  HIPCHK(hipSetDevice(p->device));
+  if ((r = need_device()) || (r = use_device(p->device))) return r;
 
   std::unique_ptr<dvbt_spectrum> hold(new dvbt_spectrum()); dvbt_spectrum *const h = hold.get();   // released on every early return below
   h->p = *p; h->p.hop = spectrum_hop(p);
@@ -164,15 +155,14 @@ extern "C" int dvbt_spectrum_create(const dvbt_spectrum_params *p, dvbt_spectrum
                  : N == 4 * FFT_THREADS ? (const void *)spectrum_kernel<4> : N == 8 * FFT_THREADS ? (const void *)spectrum_kernel<8>
                  : (const void *)spectrum_kernel<16>;
   if ((r = set_lds(fn, spec_lds(N)))) return r;
-  HIPCHK(h->s.create(hipStreamNonBlocking));
-  HIPCHK(h->ev.create(hipEventDisableTiming));
+  HIPCHK(h->ord.create());
   for (int i = 0; i < 2; i++) {
-    HIPCHK(h->hist[i].alloc(N)); HIPCHK(hipMemsetAsync(h->hist[i], 0, sizeof(float2) * N, h->s));
-    HIPCHK(h->open[i].alloc(spec_open_doubles(N))); HIPCHK(hipMemsetAsync(h->open[i], 0, sizeof(double) * spec_open_doubles(N), h->s));
+    HIPCHK(h->hist[i].alloc(N)); HIPCHK(hipMemsetAsync(h->hist[i], 0, sizeof(float2) * N, h->ord.s));
+    HIPCHK(h->open[i].alloc(spec_open_doubles(N))); HIPCHK(hipMemsetAsync(h->open[i], 0, sizeof(double) * spec_open_doubles(N), h->ord.s));
   }
   HIPCHK(h->res.alloc(spec_res_doubles(N)));
   if ((r = spectrum_rewind(h))) return r;
-  HIPCHK(hipStreamSynchronize(h->s));
+  HIPCHK(hipStreamSynchronize(h->ord.s));
   *out = hold.release();
   return DVBT_OK;
 }
@@ -192,12 +182,8 @@ extern "C" int dvbt_spectrum_push(dvbt_spectrum *h, const void *iq_host, size_t 
   int r = spectrum_check_call(h, iq_host, n); if (r) return r;
   if (n == 0) return DVBT_OK;
   HIPCHK(hipSetDevice(h->p.device));
-  if (h->have_ev && h->last_stream != h->s) HIPCHK(hipStreamWaitEvent(h->s, h->ev, 0));
-  if ((r = h->din.reserve(n * sizeof(float2)))) return r;
-  HIPCHK(hipMemcpyAsync(h->din.p, iq_host, n * sizeof(float2), hipMemcpyHostToDevice, h->s));
-  if ((r = spectrum_enqueue(h, (const float2 *)h->din.p, (long long)n, h->s))) return r;
-  HIPCHK(hipStreamSynchronize(h->s));             // the staging buffer is free for the next call
-  return DVBT_OK;
+  return staged_call(h->ord, h->din, h->din, iq_host, n * sizeof(float2), nullptr, 0, [&](const void *in, void *) {
+    return spectrum_enqueue(h, (const float2 *)in, (long long)n, h->ord.s); });
 }
 
 extern "C" int dvbt_spectrum_read(dvbt_spectrum *h, dvbt_spectrum_result *res, double *psd, unsigned long long *hist)
@@ -208,10 +194,10 @@ extern "C" int dvbt_spectrum_read(dvbt_spectrum *h, dvbt_spectrum_result *res, d
   const long long S = spectrum_segments(h->pos, N, hop);
   const bool open = (S % SPEC_GROUP) != 0;
   std::vector<double> r(spec_res_doubles(N)), o(spec_open_doubles(N));
-  if (h->have_ev && h->last_stream != h->s) HIPCHK(hipStreamWaitEvent(h->s, h->ev, 0));
-  HIPCHK(hipMemcpyAsync(r.data(), h->res, sizeof(double) * r.size(), hipMemcpyDeviceToHost, h->s));
-  if (open) HIPCHK(hipMemcpyAsync(o.data(), h->open[h->ocur], sizeof(double) * o.size(), hipMemcpyDeviceToHost, h->s));
-  HIPCHK(hipStreamSynchronize(h->s));
+  HIPCHK(h->ord.join(h->ord.s));
+  HIPCHK(hipMemcpyAsync(r.data(), h->res, sizeof(double) * r.size(), hipMemcpyDeviceToHost, h->ord.s));
+  if (open) HIPCHK(hipMemcpyAsync(o.data(), h->open[h->ocur], sizeof(double) * o.size(), hipMemcpyDeviceToHost, h->ord.s));
+  HIPCHK(hipStreamSynchronize(h->ord.s));
   const float *const oa = (const float *)(o.data() + 1);
   const unsigned long long *const h64 = (const unsigned long long *)(r.data() + N + 1);
   unsigned pk; memcpy(&pk, r.data() + N + 1 + SPEC_HIST_BINS, sizeof pk);

@@ -1,7 +1,7 @@
 // dvbt_tx.inc -- dvbt_tx_*: the modulator of apps/dvbt_tx_demo*.grc (energy_dispersal .. reference_signals, fft_vxx(reverse, shift),
-// cyclic prefixer, multiply_const) as one streaming entry over k_tx.hpp.  Included from dvbt_hip.hip.
+// cyclic prefixer, multiply_const) as one streaming handle (DESIGN.md 4i) over k_tx.hpp.  Included from dvbt_hip.hip.
 //
-// A handle modulates one transport stream delivered over any number of calls.  What it carries from call to call: the stream's packet
+// A handle modulates one transport stream.  What it carries from call to call: the stream's packet
 // count (the dispersal group phase), the symbols emitted so far (symbol_index / frame_index, and where the next symbol's bits start),
 // and -- on the device -- the last `hist` RS-coded bytes: the byte interleaver's memory (11 x 204 bytes), the info bits
 // that did not fill a symbol yet and the encoder's 6-bit history all lie in that window.  The output length follows from the
@@ -91,15 +91,11 @@ inline std::vector<uint8_t> rs_encoder_rows()
 }  // namespace
 
 struct dvbt_tx {
-  // Members are released in reverse order of declaration: the stream and the event stand in front of the buffers that work queued on them uses, so the buffers go
-  // first, then the event, the stream last.  tt holds views into T and the tables below.
   dvbt_tx_params p;
   Dims d;
   Tables T;                           // twiddles, symbol interleaver H / H^-1, constellation points
   TxSymParams sp;
-  TxTables tt;
-  Stream s;                           // the host entry's stream
-  Event ev; hipStream_t last_stream = nullptr; bool have_ev = false;
+  TxTables tt;                        // views into T and the tables below
   DevMem<uint8_t> prbs, enc_tab;
   DevMem<uint16_t> pay, pil, tps;
   DevMem<float> pref, tps_base, tps_sign;
@@ -109,7 +105,7 @@ struct dvbt_tx {
   long long max_sym = 0;
   DevMem<float2> carriers;
   DevMem<uint8_t> dts; DevBuf diq;                       // staging of the host entry
-  ~dvbt_tx() { if (have_ev) (void)hipEventSynchronize(ev); }   // the last call's work has left the buffers before any of them goes
+  CallOrder ord;                      // last: see CallOrder
 };
 
 static long long tx_symbols_after(const dvbt_tx *h, long long npackets)
@@ -118,11 +114,10 @@ static long long tx_symbols_after(const dvbt_tx *h, long long npackets)
 // back to the start of a stream: zero history in the buffer the next call reads
 static int tx_rewind(dvbt_tx *h)
 {
-  if (h->have_ev) HIPCHK(hipEventSynchronize(h->ev));
+  HIPCHK(h->ord.drain());
   h->packets = h->symbols = h->last_np = h->last_nsym = 0;
-  HIPCHK(hipMemsetAsync(h->rs[h->cur], 0, (size_t)h->hist, h->s));
-  HIPCHK(hipEventRecord(h->ev, h->s));
-  h->last_stream = h->s; h->have_ev = true;
+  HIPCHK(hipMemsetAsync(h->rs[h->cur], 0, (size_t)h->hist, h->ord.s));
+  HIPCHK(h->ord.mark(h->ord.s));
   return DVBT_OK;
 }
 
@@ -138,14 +133,11 @@ extern "C" int dvbt_tx_create(const dvbt_tx_params *p, dvbt_tx **out)
   if (p->first_packet < 0) return fail(DVBT_ERR_INVALID, "first_packet must be >= 0");
   if (p->include_cell_id < 0 || p->include_cell_id > 1 || p->cell_id < 0 || p->cell_id > 0xffff) return fail(DVBT_ERR_INVALID, "bad cell id parameters");
   if (p->keep_carriers < 0 || p->keep_carriers > 1) return fail(DVBT_ERR_INVALID, "keep_carriers must be 0 or 1");
-  int ndev = dvbt_device_count();
-  if (p->device < 0 || p->device >= ndev) return fail(DVBT_ERR_INVALID, "no such device");
-  HIPCHK(hipSetDevice(p->device));
+  if ((r = use_device(p->device))) return r;
 
   std::unique_ptr<dvbt_tx> hold(new dvbt_tx()); dvbt_tx *const h = hold.get();   // released on every early return below
   h->p = *p; h->d = d; h->T.d = d;
-  HIPCHK(h->s.create(hipStreamNonBlocking));
-  HIPCHK(h->ev.create(hipEventDisableTiming));
+  HIPCHK(h->ord.create());
   if ((r = h->T.build_fft(d.N))) return r;
   if ((r = h->T.build_inner(1.0f))) return r;
 
@@ -188,12 +180,12 @@ extern "C" int dvbt_tx_create(const dvbt_tx_params *p, dvbt_tx **out)
   // buffers: RS history covers the interleaver's 2244 bytes plus the bits of a symbol not yet emitted (+ the 6 in front of them)
   h->hist = (2244 + d.info_bits_per_symbol / 8 + 3 + 15) & ~15;
   const size_t rs_bytes = (size_t)h->hist + p->max_packets * 204;
-  for (int i = 0; i < 2; i++) { HIPCHK(h->rs[i].alloc(rs_bytes + 64)); HIPCHK(hipMemsetAsync(h->rs[i], 0, rs_bytes + 64, h->s)); }
+  for (int i = 0; i < 2; i++) { HIPCHK(h->rs[i].alloc(rs_bytes + 64)); HIPCHK(hipMemsetAsync(h->rs[i], 0, rs_bytes + 64, h->ord.s)); }
   h->max_sym = ((long long)p->max_packets * 1632 + d.info_bits_per_symbol - 1) / d.info_bits_per_symbol;
   if (p->keep_carriers) HIPCHK(h->carriers.alloc((size_t)h->max_sym * d.N + 8));
   if ((r = set_lds(d.N == 8192 ? (const void *)tx_symbol_kernel<8192> : (const void *)tx_symbol_kernel<2048>, tx_symbol_lds_bytes(d.N, d.payload)))) return r;
   if ((r = tx_rewind(h))) return r;
-  HIPCHK(hipStreamSynchronize(h->s));
+  HIPCHK(hipStreamSynchronize(h->ord.s));
   *out = hold.release();
   return DVBT_OK;
 }
@@ -207,7 +199,7 @@ extern "C" int64_t dvbt_tx_samples_for(const dvbt_tx *h, size_t npackets)
 // the call's two launches on stream st; the caller has checked the capacities
 static int tx_enqueue(dvbt_tx *h, const void *ts, long long np, void *iq, long long nsym, hipStream_t st)
 {
-  if (h->have_ev && st != h->last_stream) HIPCHK(hipStreamWaitEvent(st, h->ev, 0));   // the previous call ran on another stream
+  HIPCHK(h->ord.join(st));
   const int nxt = h->cur ^ 1;
   const long long nblk = (np + TX_OUTER_PK - 1) / TX_OUTER_PK;
   hipLaunchKernelGGL(tx_outer_kernel, dim3((unsigned)(nblk + 1)), dim3(TX_OUTER_PK), 0, st, (const uint8_t *)ts, np, (long long)h->p.first_packet + h->packets,
@@ -222,8 +214,7 @@ static int tx_enqueue(dvbt_tx *h, const void *ts, long long np, void *iq, long l
     else hipLaunchKernelGGL(tx_symbol_kernel<2048>, dim3((unsigned)nsym), dim3(FFT_THREADS), lds, st, (const uint8_t *)h->rs[nxt], sp, h->tt, (float2 *)iq, car);
     HIPCHK(hipGetLastError());
   }
-  HIPCHK(hipEventRecord(h->ev, st));
-  h->have_ev = true; h->last_stream = st;
+  HIPCHK(h->ord.mark(st));
   h->cur = nxt; h->packets += np; h->symbols += nsym; h->last_np = np; h->last_nsym = nsym;
   return DVBT_OK;
 }
@@ -262,12 +253,12 @@ extern "C" int dvbt_tx_run(dvbt_tx *h, const void *ts_host, size_t npackets, voi
   HIPCHK(hipSetDevice(h->p.device));
   const size_t nout = (size_t)nsym * (size_t)(h->d.N + h->d.cp);
   if (!h->dts) HIPCHK(h->dts.alloc(h->p.max_packets * 188 + 64));
-  if (h->have_ev && h->last_stream != h->s) HIPCHK(hipStreamWaitEvent(h->s, h->ev, 0));
+  HIPCHK(h->ord.join(h->ord.s));
   r = h->diq.reserve(nout * sizeof(float2)); if (r) return r;
-  HIPCHK(hipMemcpyAsync(h->dts, ts_host, npackets * 188, hipMemcpyHostToDevice, h->s));
-  r = tx_enqueue(h, h->dts, (long long)npackets, h->diq.p, nsym, h->s); if (r) return r;
-  if (nout) HIPCHK(hipMemcpyAsync(iq_host, h->diq.p, nout * sizeof(float2), hipMemcpyDeviceToHost, h->s));
-  HIPCHK(hipStreamSynchronize(h->s));
+  HIPCHK(hipMemcpyAsync(h->dts, ts_host, npackets * 188, hipMemcpyHostToDevice, h->ord.s));
+  r = tx_enqueue(h, h->dts, (long long)npackets, h->diq.p, nsym, h->ord.s); if (r) return r;
+  if (nout) HIPCHK(hipMemcpyAsync(iq_host, h->diq.p, nout * sizeof(float2), hipMemcpyDeviceToHost, h->ord.s));
+  HIPCHK(hipStreamSynchronize(h->ord.s));
   if (nsamples) *nsamples = nout;
   return DVBT_OK;
 }
@@ -279,7 +270,7 @@ extern "C" int64_t dvbt_tx_read_carriers(dvbt_tx *h, void *dst_host, size_t cap_
   const size_t bytes = (size_t)h->last_nsym * h->d.N * sizeof(float2);
   if (!dst_host) return (int64_t)bytes;
   if (cap_bytes < bytes) return fail(DVBT_ERR_CAPACITY, "cap_bytes is smaller than the last call's carriers");
-  if (h->have_ev) HIPCHK(hipEventSynchronize(h->ev));
+  HIPCHK(h->ord.drain());
   if (bytes) HIPCHK(hipMemcpy(dst_host, h->carriers, bytes, hipMemcpyDeviceToHost));
   return (int64_t)bytes;
 }

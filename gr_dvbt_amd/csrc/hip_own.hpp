@@ -50,4 +50,19 @@ struct Event : Owner<hipEvent_t, DestroyEvent> {
   hipError_t create(unsigned flags) { reset(); hipEvent_t v = nullptr; const hipError_t e = hipEventCreateWithFlags(&v, flags); return adopt(e, v); }
 };
 
+// How a streaming handle orders its calls, which may arrive on different streams: one event, recorded behind each call's last launch.  It is the LAST member
+// of its handle: members go in reverse order of declaration, so it is destroyed first -- it waits for the last call's work, then releases the event and the
+// stream -- and the handle's device buffers go after it, when nothing reads them any more.
+class CallOrder {
+public:
+  Stream s;                           // the handle's own stream: the host entries', rewind's
+  hipError_t create() { const hipError_t e = s.create(hipStreamNonBlocking); return e != hipSuccess ? e : ev.create(hipEventDisableTiming); }
+  hipError_t join(hipStream_t st) { return have_ev && st != last_stream ? hipStreamWaitEvent(st, ev, 0) : hipSuccess; }   // st waits for a call on another stream
+  hipError_t mark(hipStream_t st) { const hipError_t e = hipEventRecord(ev, st); if (e == hipSuccess) { have_ev = true; last_stream = st; } return e; }
+  hipError_t drain() { return have_ev ? hipEventSynchronize(ev) : hipSuccess; }                                           // the host waits for the last call
+  ~CallOrder() { (void)drain(); }
+private:
+  Event ev; hipStream_t last_stream = nullptr; bool have_ev = false;
+};
+
 }   // namespace hip_own

@@ -14,6 +14,11 @@ import clockref
 
 pytestmark = pytest.mark.gpu
 
+try:
+    import torch
+except Exception:  # pragma: no cover
+    torch = None
+
 FAR = 2 ** 40 + 3
 
 
@@ -169,6 +174,35 @@ def test_split_calls_equal_one_call_bit_for_bit(g, random_x, taps, ppm):
     assert ck.run_device(din.ptr, N_SPLIT, dout.ptr, len(whole)) == len(whole)
     assert dout.get(0, len(whole)).tobytes() == whole.tobytes()
     din.free(); dout.free(); ck.close()
+
+
+def test_device_entry_on_two_streams(g, random_x):
+    N = 20000
+    pa, pb = dict(taps=16, ppm=55.0), dict(taps=64, ppm=-1000.0)
+    x1, x2 = random_x[900:900 + N], random_x[30000:30000 + N]
+    ra, rb = g.ClockOffset(**pa), g.ClockOffset(**pb)
+    ref1, ref2 = ra.run(x1), rb.run(x2)
+    ra.close(); rb.close()
+    assert len(ref1) > N - 100 and len(ref2) > N - 100
+    dev = torch.device("cuda:0")
+    d1, d2 = torch.from_numpy(x1.view(np.float32).copy()).to(dev), torch.from_numpy(x2.view(np.float32).copy()).to(dev)
+    o1, o2 = torch.zeros(2 * len(ref1), dtype=torch.float32, device=dev), torch.zeros(2 * len(ref2), dtype=torch.float32, device=dev)
+    s1, s2 = torch.cuda.Stream(), torch.cuda.Stream()
+    a, b = g.ClockOffset(**pa), g.ClockOffset(**pb)
+    torch.cuda.synchronize()
+    # two handles interleaved on two streams, each in three calls; handle a changes streams between its calls
+    cuts = [0, 9001, 9002, N]
+    qa = qb = 0
+    for i in range(3):
+        lo, hi = cuts[i], cuts[i + 1]
+        sa = s1 if i != 1 else s2
+        qa += a.run_device(d1.data_ptr() + 8 * lo, hi - lo, o1.data_ptr() + 8 * qa, len(ref1) - qa, stream=sa.cuda_stream)
+        qb += b.run_device(d2.data_ptr() + 8 * lo, hi - lo, o2.data_ptr() + 8 * qb, len(ref2) - qb, stream=s2.cuda_stream)
+    torch.cuda.synchronize()
+    assert qa == len(ref1) and qb == len(ref2)
+    assert o1.cpu().numpy().view(np.complex64).tobytes() == ref1.tobytes()
+    assert o2.cpu().numpy().view(np.complex64).tobytes() == ref2.tobytes()
+    a.close(); b.close()
 
 
 # ------------------------------------------------------------------ 5. far out, and pieces
