@@ -51,6 +51,10 @@
 // (SQ_INSTS_VALU; 2,472 in round 7, 2,727 before it).  Since rounds 9 and 10 (the shortcut below; the renormalisation every sixth window): the hop-free windows 0-11 86.3 per window, with
 // hops 94.7, windows 12-23 90.2 (88.0 / 96.3 / 91.8 with the renormalisation every second window; tests/test_viterbi_isa_renorm.py holds them), 2,361 per block measured (2,400 in round 9).  Since round 11 (one v_perm per step at every phase: 74.7 for a window's eight steps instead of 77.3; the ring's row masked once per
 // group of eight windows instead of once per window, v3_fwd_window): 83.7 / 92.0 / 85.8 (tests/test_viterbi_isa_perm.py), 2,275 per block measured.  Every stamp is one v_and_or_b32 (the lane constants are kept opaque, v3_init_lane).
+// Since round 13 the work OUTSIDE the windows (staging, the chains' set-up, the decision: ~240 of the 2,275): staging's index chain walks two steps per link through the pair table
+// (v3_init_lut: six ds_read_b64 for twelve ds_read_b32), the received bits are compacted with constant masks per constellation (v3_compact) and the block's 16-byte load needs no
+// 64-bit compare inside the wave-uniform bounds l_first .. l_last (stage_load) -- the stretch between the loop header and the first window 471 -> 412 VALU as compiled, all paths
+// counted (tests/test_viterbi_isa_outside.py), 2,216 per block measured (SQ_INSTS_VALU 1,726.6 M -> 1,681.5 M per launch), the windows as they were; LDS 80,896 B per workgroup.
 // What the count alone did not buy, the order of the LDS reads did: a hop's read and its use stand three and five steps apart (v3_fwd_window), and a window's
 // step words are loaded one window ahead (v3_fwd_six) -- the wavefront, one of two on its SIMD, no longer waits out the LDS latency 70 times per block.  The same holds around
 // the windows since round 8: staging computes a lane's twelve table indices first, issues the twelve look-ups back to back behind one wait and stores the words as three
@@ -91,7 +95,7 @@ inline VitParams make_vit_params(const Dims &d, int bsize, int chunk_bytes)
   memcpy(v.punct, d.punct, 16); memcpy(v.prefix, d.prefix, 16);
   v.punct_mask = 0; v.prefix_nib = 0;
   for (int i = 0; i < d.plen; i++) { v.punct_mask |= (unsigned)d.punct[i] << i; v.prefix_nib |= (unsigned long long)d.prefix[i] << (4 * i); }
-  v.magic_plen = ~0ull / (unsigned)d.plen + 1; v.magic_m = ~0ull / (unsigned)d.m + 1;
+  v.magic_plen = ~0ull / (unsigned)d.plen + 1; v.magic_m = ~0ull / (unsigned)d.m + 1; v.magic_n = ~0ull / (unsigned)d.n + 1;
   for (int i = 0; i < 64; i++) v.punct_rep |= (unsigned long long)d.punct[i % d.plen] << i;
   v.magic16_plen = (65536u + (unsigned)d.plen - 1) / (unsigned)d.plen;
   return v;
@@ -434,7 +438,7 @@ template <int W0, bool HOPS, int HOP0, int NTB, int NW, bool MORE> __device__ __
 //             the m valid bits of every byte into a bit stream in LDS; every lane then owns 12 consecutive steps:
 //             it places itself in the puncture period with small-integer arithmetic relative to the row's base (one
 //             64-bit locate per row), takes the period's keep-mask for its 24 symbol positions and a 32-bit window
-//             of the bit stream, and emits one word of four class deltas per step through a 16-entry table;
+//             of the bit stream, and emits one word of four class deltas per step, two steps per look-up in the 256-entry pair table;
 //   forward   24 windows of add-compare-select (v3_fwd_window), path bytes into the LDS ring;
 //   traceback of the PREVIOUS block's 24 calls x 4 decoders (d_viterbi.c:714-724), lane = (decoder, call): its
 //             dependent LDS reads are interleaved into the first 12 windows of the forward pass.
@@ -485,19 +489,51 @@ __device__ __forceinline__ int *v3_fix(const V3Aux &ax, long long c) { return ax
 inline size_t v3_snap_words(long long cap) { return (size_t)(cap + 2) * 3 * V3_SLOT; }
 inline size_t v3_ctl_words(long long cap) { return (size_t)V3_CTL_HDR + 2 * (size_t)(cap + 2); }
 
-struct V3Lds { unsigned char *tab; unsigned *wbuf; unsigned char *bests; const unsigned *lut; int wv; };   // tab: the workgroup's ring; wbuf, bests: the wavefront's; wv: the wavefront
-// the label-class deltas of a step as a function of (keep flags, next two received bits); every wavefront writes the same 16 words
-__device__ __forceinline__ void v3_init_lut(unsigned *lut, int lane)
+struct V3Lds { unsigned char *tab; unsigned *wbuf; unsigned char *bests; const uint2 *lut; int wv; };   // tab: the workgroup's ring; wbuf, bests: the wavefront's; wv: the wavefront
+// the label-class deltas of a step as a function of e = (keep flags of its two symbols) << 2 | next two received bits: the step word
+__device__ __forceinline__ unsigned v3_step_word(int e)
 {
-  if (lane < 16) {
-    // deltas of the four label classes, doubled (a step with one punctured symbol keeps the bias bit free):
-    // class 0: u0+u1 | class 1 (c0=1): -u0+u1 | class 2 (c1=1): u0-u1 | class 3: -u0-u1, u = +1/-1 for a received 0/1, 0 if erased
-    const int k0 = (lane >> 2) & 1, k1 = (lane >> 3) & 1, t1 = (lane >> 1) & 1, t0 = lane & 1;
-    const int u0 = k0 ? 1 - 2 * t1 : 0, u1 = k1 ? 1 - 2 * (k0 ? t0 : t1) : 0;
-    const unsigned d0 = (unsigned)(2 * (u0 + u1)) & 0xff, d1 = (unsigned)(2 * (-u0 + u1)) & 0xff;
-    const unsigned d2 = (unsigned)(2 * (u0 - u1)) & 0xff, d3 = (unsigned)(2 * (-u0 - u1)) & 0xff;
-    lut[lane] = d0 | (d1 << 8) | (d2 << 16) | (d3 << 24);
+  // deltas of the four label classes, doubled (a step with one punctured symbol keeps the bias bit free):
+  // class 0: u0+u1 | class 1 (c0=1): -u0+u1 | class 2 (c1=1): u0-u1 | class 3: -u0-u1, u = +1/-1 for a received 0/1, 0 if erased
+  const int k0 = (e >> 2) & 1, k1 = (e >> 3) & 1, t1 = (e >> 1) & 1, t0 = e & 1;
+  const int u0 = k0 ? 1 - 2 * t1 : 0, u1 = k1 ? 1 - 2 * (k0 ? t0 : t1) : 0;
+  const unsigned d0 = (unsigned)(2 * (u0 + u1)) & 0xff, d1 = (unsigned)(2 * (-u0 + u1)) & 0xff;
+  const unsigned d2 = (unsigned)(2 * (u0 - u1)) & 0xff, d3 = (unsigned)(2 * (-u0 - u1)) & 0xff;
+  return d0 | (d1 << 8) | (d2 << 16) | (d3 << 24);
+}
+// The pair table: TWO steps per look-up.  Key = (keep flags of the two steps' four symbols) << 4 | next four received bits (the oldest on top); the entry holds the first
+// step's word, and the second step's behind the bits the first one consumed (one per kept symbol).  256 entries of 8 bytes; every wavefront writes all of them, the same
+// values, before its first use (a wavefront's LDS operations execute in order): staging's index chain is six links long instead of twelve, and a link costs what it did
+// (tests/test_viterbi_pair_table_model.py restates the entry and the chain)
+constexpr int V3_PAIRS = 256;
+__device__ __forceinline__ void v3_init_lut(uint2 *lut, int lane)
+{
+#pragma unroll
+  for (int j = 0; j < V3_PAIRS / 64; j++) {
+    const int e = lane + 64 * j, k4 = e >> 4, t = e & 15;
+    const int used = __popc(k4 & 3);                               // received bits the first step consumes
+    lut[e] = make_uint2(v3_step_word(((k4 & 3) << 2) | (t >> 2)), v3_step_word((k4 & 12) | (((t << used) >> 2) & 3)));
   }
+}
+
+// The M valid bits (the low ones) of each of a dword's four input bytes as one field of 4 M bits, byte 0 -- the first in memory -- most significant: what
+//   ((d & mk) << 3 M) | (((d >> 8) & mk) << 2 M) | (((d >> 16) & mk) << M) | ((d >> 24) & mk),  mk = (1 << M) - 1
+// gives, folded pairwise with constant masks: bytes 0 and 1 (2 and 3) into the low 2 M bits of each half, then the two halves.  Whatever a byte holds above its M bits is dropped
+// (tests/test_viterbi_compact_host.py compiles this for the host and compares it with the formula)
+template <int M> __device__ __forceinline__ unsigned v3_compact(unsigned d)
+{
+  constexpr unsigned c2 = ((1u << M) - 1) * 0x00010001u;           // the M bits of byte 0 and of byte 2
+  const unsigned t = ((d & c2) << M) | ((d >> 8) & c2);            // [byte 2 : byte 3] at bit 16, [byte 0 : byte 1] at bit 0
+  return ((t & ((1u << (2 * M)) - 1)) << (2 * M)) | (t >> 16);
+}
+// (end of v3_compact)
+// 16 bytes of the input at a 4-byte aligned address kept as an integer (stage_load): a global load (through a generic pointer it would be a flat one, which also counts as an LDS
+// operation in the wavefront's waits)
+typedef unsigned v3u4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ uint4 v3_load16(unsigned long long addr)
+{
+  const v3u4 t = *(const __attribute__((address_space(1))) v3u4 *)addr;
+  return make_uint4(t.x, t.y, t.z, t.w);
 }
 
 // One decoder per DPP row over [b0, min(b0 + B, total_out)), the wavefront's four rows in step.
@@ -509,10 +545,10 @@ __device__ __forceinline__ void v3_decode(const uint8_t *__restrict__ in, uint8_
                                           long long in_base, long long out_lo, long long b0, bool dec_active, const V3Lds &S, const V3Lane &L, int (&v)[2], int (&endv)[2],
                                           int *own, int *predn, const int *inject, int *carry, int carry_rel, int debug, unsigned long long *shortcut)
 {
-  unsigned char *const tab = S.tab; unsigned *const wbuf = S.wbuf; unsigned char *const bests = S.bests; const unsigned *const lut = S.lut;
+  unsigned char *const tab = S.tab; unsigned *const wbuf = S.wbuf; unsigned char *const bests = S.bests; const uint2 *const lut = S.lut;
   // compacted received bits per decoder (MSB first): V3_CBW words at the head of the decoder's wbuf row.  stage_words reads them (every
   // lane its two words) before the wavefront writes the block's step words over them, and the previous block's step words are dead by
-  // then; a wavefront's LDS operations execute in order.  The overlay keeps the workgroup at 19,776 B of LDS per wavefront: eight workgroups per CU
+  // then; a wavefront's LDS operations execute in order.  The overlay keeps the workgroup at 20,224 B of LDS per wavefront (19,712 + its share of the pair table): eight wavefronts per CU
   // (two wavefronts per SIMD) with room to spare
   unsigned *const cbits = wbuf;
   constexpr int V3_CBS = V3_BLK * 8;                                               // stride between the decoders' bit streams
@@ -547,12 +583,48 @@ __device__ __forceinline__ void v3_decode(const uint8_t *__restrict__ in, uint8_
     u_first = max(max(__builtin_amdgcn_readlane(first, 0), __builtin_amdgcn_readlane(first, 16)), max(__builtin_amdgcn_readlane(first, 32), __builtin_amdgcn_readlane(first, 48)));
     u_last = min(min(__builtin_amdgcn_readlane(last, 0), __builtin_amdgcn_readlane(last, 16)), min(__builtin_amdgcn_readlane(last, 32), __builtin_amdgcn_readlane(last, 48)));
   }
+  // A second pair of block bounds, for staging's loads: in the blocks jb = l_first .. l_last every one of the nload 16-byte loads of all four rows lies inside the input that exists,
+  // [in_base, n_in_bytes) -- the load is then one address and one global_load_dwordx4 under dec_active && pl < nload.  A row's block starts in byte y(t) = rb(2 t) / m of the
+  // stream, t = max(tb0 + 8 jb, 0) its first step and rb(p) = (p / plen) n + pfx(p % plen) the received bits in front of depunctured bit p; its lanes read
+  // [A, A + 16 nload) with A = the address in + (y - in_base) rounded down to four bytes.  With a = in & 3 and N = n_in_bytes - in_base:
+  //   A >= in                   <=>  y - in_base >= (4 - a) & 3                                   =: dmin
+  //   A + 16 nload <= in + N    <=>  y - in_base <= ((N + a - 16 nload) & ~3) + 3 - a             =: dmax   (N + a - 16 nload >= 0; otherwise no block)
+  // y is monotone in jb, so each side is one threshold on jb.  rb is inverted in whole puncture periods: rb(p) >= R for p >= ((R - 1) / n + 1) plen and rb(p) <= R for
+  // p <= (R / n) plen -- up to plen depunctured bits (seven steps, less than a window) on the safe side of the exact threshold, so a bound is the exact one or one block
+  // inside it (tests/test_viterbi_load_bounds_model.py).  Outside the bounds the lanes test their bytes themselves, as they always did.
+  const unsigned long long in_addr = (unsigned long long)(uintptr_t)in;
+  const int ld_lanes = dec_active ? nload : 0;                     // the lanes of the row that load: one compare, one exec region
+  int l_first, l_last;
+  {
+    const int a = (int)(in_addr & 3ull);
+    const long long H = n_in_bytes - in_base + a - 16 * nload;
+    const long long Rlo = (in_base + ((4 - a) & 3)) * m;                             // y >= in_base + dmin  <=>  rb >= Rlo
+    const long long Rhi = (in_base + (H & ~3ll) + 3 - a + 1) * m - 1;                // y <= in_base + dmax  <=>  rb <= Rhi
+    int first = 0, last = J;                                                       // (a decoder that does not exist loads nothing)
+    if (dec_active) {
+      if (Rlo > 0) {
+        const unsigned long long p = (__umul64hi((unsigned long long)(Rlo - 1), vp.magic_n) + 1) * (unsigned)vp.plen;
+        const long long w = ((long long)((p + 1) >> 1) - tb0 + 7) >> 3;            // the first window at or behind step p / 2
+        first = w <= 0 ? 0 : w >= J ? J : (((int)w + V3_BLK - 1) / V3_BLK) * V3_BLK;
+      }
+      if (H < 0 || Rhi < 0) last = -1;
+      else {
+        const unsigned long long p = __umul64hi((unsigned long long)Rhi, vp.magic_n) * (unsigned)vp.plen;
+        const long long w = ((long long)(p >> 1) - tb0) >> 3;                      // the last window whose first step is at or in front of step p / 2
+        last = w < 0 ? -1 : w >= J ? J : ((int)w / V3_BLK) * V3_BLK;
+      }
+    }
+    l_first = max(max(__builtin_amdgcn_readlane(first, 0), __builtin_amdgcn_readlane(first, 16)), max(__builtin_amdgcn_readlane(first, 32), __builtin_amdgcn_readlane(first, 48)));
+    l_last = min(min(__builtin_amdgcn_readlane(last, 0), __builtin_amdgcn_readlane(last, 16)), min(__builtin_amdgcn_readlane(last, 32), __builtin_amdgcn_readlane(last, 48)));
+  }
   // ---- staging, first half: where block jb starts in the input (row-uniform) and the load of its bytes.  The blocks are staged in order: behind a block whose step 0 is a real
   // step the position advances by BLKBITS depunctured bits -- ph0, the byte and bo0 are carried with small integers; the 64-bit locate runs for a decoder's first block, and for
   // the blocks of a decoder that starts before the stream does (the clamp below), in which case the whole wavefront takes it.
   // pfx(ph) = received bits of a period before its phase ph (VitParams.prefix): the kept symbols below ph -- one v_bfe + v_bcnt where the nibble table takes a 64-bit shift
   auto pfx = [&](int ph) { return (int)__popc(vp.punct_mask & ((1u << ph) - 1u)); };
-  int ph0 = 0, pf0 = 0, bo0 = 0, off = 0; long long byte0 = 0; uint4 q = make_uint4(0, 0, 0, 0);   // pf0 = pfx(ph0), carried with it
+  // The byte the row's block starts in is carried as its address pb = in + (byte - in_base), a 64-bit integer that advances with the block (it may lie in front of `in` or
+  // behind the last byte: nothing is read through it outside [in, in + n_in_bytes - in_base)).  The lanes read 16 bytes each from pb rounded down to four bytes
+  int ph0 = 0, pf0 = 0, bo0 = 0, off = 0; unsigned long long pb = 0; uint4 q = make_uint4(0, 0, 0, 0);   // pf0 = pfx(ph0), carried with it
   auto stage_load = [&](int jb) {
     const long long tb = tb0 + (long long)jb * 8;                  // real step index of block step 0 (may be < 0)
     if (jb > 0 && jb - V3_BLK >= u_first) {                         // (the block before starts at a real step in all four decoders)
@@ -563,25 +635,32 @@ __device__ __forceinline__ void v3_decode(const uint8_t *__restrict__ in, uint8_
       pf0 = pfx(ph0);
       const int r = bo0 + (inc_q + wrap) * vp.n + pf0 - pf_old;       // received bits from the old byte's first bit (0 <= r < 1024)
       const int dby = (int)(((unsigned)r * magic16_m) >> 16);
-      bo0 = r - dby * m; byte0 += dby;
+      bo0 = r - dby * m; pb += (unsigned)dby;
     } else {
       const unsigned long long pbit = 2ull * (unsigned long long)(tb > 0 ? tb : 0);
       const unsigned long long pq = __umul64hi(pbit, vp.magic_plen);
       ph0 = (int)(pbit - pq * (unsigned)vp.plen); pf0 = pfx(ph0);
       const unsigned long long rb = pq * (unsigned)vp.n + (unsigned)pf0;
       const unsigned long long by = __umul64hi(rb, vp.magic_m);
-      byte0 = (long long)by; bo0 = (int)(rb - by * (unsigned)m);
+      pb = in_addr + (by - (unsigned long long)in_base); bo0 = (int)(rb - by * (unsigned)m);
     }
-    off = (int)(((unsigned long long)(uintptr_t)in + (unsigned long long)(byte0 - in_base)) & 3ull);
-    const long long src = byte0 - off + pl * 16;                   // 4-byte aligned address
+    off = (int)((unsigned)pb & 3u);
+    const unsigned long long la = (pb & ~3ull) + (unsigned)(pl * 16);   // 4-byte aligned address of this lane's 16 bytes
     q = make_uint4(0, 0, 0, 0);
-    if (dec_active && pl < nload) {
-      if (src >= in_base && src + 16 <= n_in_bytes) q = *reinterpret_cast<const uint4 *>(in + (src - in_base));
+    if (__builtin_expect(jb >= l_first && jb <= l_last, 1)) {       // every lane's 16 bytes exist (wave-uniform): no lane compares a 64-bit position
+      if (pl < ld_lanes) q = v3_load16(la);
+    } else if (pl < ld_lanes) {
+      const long long src = (long long)(la - in_addr) + in_base;   // the bytes' index in the stream
+      if (src >= in_base && src + 16 <= n_in_bytes) q = v3_load16(la);
       else {
+        // byte by byte.  Which of the sixteen exist is settled once, in 64 bits: the bytes [e0, e1) -- a byte then costs two 32-bit compares with a constant, not two 64-bit
+        // ones behind a 64-bit add (sixteen copies of this stand in the middle of every iteration's code)
+        const long long d0 = in_base - src, d1 = n_in_bytes - src;
+        const int e0 = d0 < 0 ? 0 : d0 > 16 ? 16 : (int)d0, e1 = d1 < 0 ? 0 : d1 > 16 ? 16 : (int)d1;
+        const uint8_t *const pbyte = in + (src - in_base);
         unsigned w[4] = {0, 0, 0, 0};
         for (int i = 0; i < 16; i++) {
-          const long long bb = src + i;
-          const unsigned bv = (bb >= in_base && bb < n_in_bytes) ? in[bb - in_base] : 0;
+          const unsigned bv = (i >= e0 && i < e1) ? pbyte[i] : 0;
           w[i >> 2] |= bv << (8 * (i & 3));
         }
         q = make_uint4(w[0], w[1], w[2], w[3]);
@@ -591,14 +670,15 @@ __device__ __forceinline__ void v3_decode(const uint8_t *__restrict__ in, uint8_
   // ---- staging, second half: bit compaction and the step words of block jb
   auto stage_words = [&](int jb, auto &&mid) {
     {
-      const unsigned mk = (1u << m) - 1;
-      auto grp = [&](unsigned d) { return ((d & mk) << (3 * m)) | (((d >> 8) & mk) << (2 * m)) | (((d >> 16) & mk) << m) | ((d >> 24) & mk); };
-      const unsigned g0 = grp(q.x), g1 = grp(q.y), g2 = grp(q.z), g3 = grp(q.w);
+      // m is wave-uniform: each of the three exclusive branches compacts with constant masks and shifts (v3_compact)
       unsigned *cb = cbits + dd * V3_CBS;
       if (pl < nload) {
-        if (m == 2) cb[pl] = (g0 << 24) | (g1 << 16) | (g2 << 8) | g3;
-        else if (m == 4) { cb[2 * pl] = (g0 << 16) | g1; cb[2 * pl + 1] = (g2 << 16) | g3; }
-        else { cb[3 * pl] = (g0 << 8) | (g1 >> 16); cb[3 * pl + 1] = (g1 << 16) | (g2 >> 8); cb[3 * pl + 2] = (g2 << 24) | g3; }
+        if (m == 2) cb[pl] = (v3_compact<2>(q.x) << 24) | (v3_compact<2>(q.y) << 16) | (v3_compact<2>(q.z) << 8) | v3_compact<2>(q.w);
+        else if (m == 4) { cb[2 * pl] = (v3_compact<4>(q.x) << 16) | v3_compact<4>(q.y); cb[2 * pl + 1] = (v3_compact<4>(q.z) << 16) | v3_compact<4>(q.w); }
+        else {
+          const unsigned g0 = v3_compact<6>(q.x), g1 = v3_compact<6>(q.y), g2 = v3_compact<6>(q.z), g3 = v3_compact<6>(q.w);
+          cb[3 * pl] = (g0 << 8) | (g1 >> 16); cb[3 * pl + 1] = (g1 << 16) | (g2 >> 8); cb[3 * pl + 2] = (g2 << 24) | g3;
+        }
       }
     }
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
@@ -628,15 +708,16 @@ __device__ __forceinline__ void v3_decode(const uint8_t *__restrict__ in, uint8_
     unsigned win = (unsigned)(((((unsigned long long)cw0) << 32) | cw1) >> (32 - (pos & 31)));
     // the twelve table indices first (one VALU chain on win), then the twelve look-ups back to back behind ONE wait, then the lane's 48 bytes as three 16-byte stores.  Written as
     // look-up + store per step, the compiler keeps that order (the table and the step words are members of one LDS object) and the wavefront waits out twelve LDS round trips in a row
-    unsigned idx[SPL], sw[SPL];
+    // (two steps per link and per look-up: the pair table, v3_init_lut)
+    unsigned idx[SPL / 2], sw[SPL];
 #pragma unroll
-    for (int i = 0; i < SPL; i++) {
-      const unsigned k2 = (kmask >> (2 * i)) & 3u;                  // keep flags of the step's two symbols
-      idx[i] = (k2 << 2) | (win >> 30);
-      win <<= __popc(k2);                                          // consume one received bit per kept symbol
+    for (int i = 0; i < SPL / 2; i++) {
+      const unsigned k4 = (kmask >> (4 * i)) & 15u;                 // keep flags of the two steps' four symbols
+      idx[i] = (k4 << 4) | (win >> 28);
+      win <<= __popc(k4);                                          // consume one received bit per kept symbol
     }
 #pragma unroll
-    for (int i = 0; i < SPL; i++) sw[i] = lut[idx[i]];
+    for (int i = 0; i < SPL / 2; i++) { const uint2 w2 = lut[idx[i]]; sw[2 * i] = w2.x; sw[2 * i + 1] = w2.y; }
     static_assert(SPL % 4 == 0, "a lane's step words are whole 16-byte groups (its offset dd * 768 + pl * 48 bytes is 16-byte aligned)");
     uint4 *const wdst = reinterpret_cast<uint4 *>(wbuf + dd * (V3_BLK * 8) + ub0);
 #pragma unroll
@@ -768,8 +849,9 @@ template <int NW> struct V3Shared {
   alignas(16) unsigned char tab[V3_RINGW * V3_ROW<NW>];     // path bytes: [window][wavefront][decoder][cell z]  (the ppresult ring)
   alignas(16) unsigned wbuf[NW][4 * V3_BLK * 8];            // step words: [wavefront][decoder][step in block]
   unsigned char bests[NW][4 * V3_RINGW];                    // best state per window
-  unsigned lut[16];                                         // (keep flags, next two received bits) -> the step word
+  uint2 lut[V3_PAIRS];                                      // (keep flags of two steps, next four received bits) -> the two step words (v3_init_lut)
 };
+static_assert(sizeof(V3Shared<4>) == 80896, "79 KiB: two workgroups are 158 of a CU's 160 KiB");
 static_assert(sizeof(V3Shared<4>) <= 81920 && V3_RMASK<4> == 0xffc0 && V3_RMASK<1> == 0x3fc0, "two four-wave workgroups per CU beside the symbol kernel's 76 KB");
 #define V3_LDS_DECL(NW) __shared__ V3Shared<NW> sh_;
 #define V3_LDS(NW, wv) V3Lds{sh_.tab, sh_.wbuf[wv], sh_.bests[wv], sh_.lut, wv}
