@@ -1097,6 +1097,28 @@ class Block:
         self.L.dvbt_viterbi_decoder_set_walk.argtypes = [C.c_void_p, C.c_int]
         _chk(self.L.dvbt_viterbi_decoder_set_walk(self.h, int(bool(always))))
 
+    def set_viterbi_chunk_bytes(self, nbytes):
+        """viterbi_decoder only, a test hook: chunks of nbytes (0 = the default 264, else a multiple of 24 in [24, 264]) from the next stream reset on"""
+        self.L.dvbt_viterbi_decoder_set_chunk_bytes.argtypes = [C.c_void_p, C.c_int]
+        _chk(self.L.dvbt_viterbi_decoder_set_chunk_bytes(self.h, int(nbytes)))
+
+    def set_viterbi_warm_windows(self, windows):
+        """viterbi_decoder only: the chunk decoders' warm-up (0 = the default 72, else a multiple of 24 in [48, 576])"""
+        self.L.dvbt_viterbi_decoder_set_warm_windows.argtypes = [C.c_void_p, C.c_int]
+        _chk(self.L.dvbt_viterbi_decoder_set_warm_windows(self.h, int(windows)))
+
+    def set_viterbi_verify(self, mode):
+        """viterbi_decoder only, a test hook: RxParams.viterbi_verify (-1 .. 4) from the next stream reset on"""
+        self.L.dvbt_viterbi_decoder_set_verify.argtypes = [C.c_void_p, C.c_int]
+        _chk(self.L.dvbt_viterbi_decoder_set_verify(self.h, int(mode)))
+
+    def viterbi_last_ctl(self):
+        """viterbi_decoder only, a test hook: the 16 header words of the last launch's control block (k_viterbi3.hpp, V3_CTL_*)"""
+        out = (C.c_int * 16)()
+        self.L.dvbt_viterbi_decoder_last_ctl.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
+        _chk(self.L.dvbt_viterbi_decoder_last_ctl(self.h, out))
+        return [int(x) for x in out]
+
     def viterbi_shortcut(self):
         """viterbi_decoder only: (shortcut, walked) blocks of 24 windows, per wavefront, since the block was created"""
         out = (C.c_longlong * 2)()

@@ -329,6 +329,7 @@ struct dvbt_viterbi_decoder {
   size_t hist = 0; long long in_total = 0, steps = 0; int d_init = 0;      // hist: bytes of consumed input kept at the front of din
   static constexpr size_t kTail = 8192;
   bool walk = false;                                                       // dvbt_viterbi_decoder_set_walk
+  int chunk_next = 11 * V3_BLK, verify = VIT_REPAIR, verify_next = VIT_REPAIR;   // test hooks: dvbt_viterbi_decoder_set_chunk_bytes, _set_verify (both adopted at the next reset)
   VitProof proof; DevMem<int> carry; int cur = 0; bool have_carry = false; long long grid0 = 0;   // carry: 2 x 32 words (ping-pong), [cur] = the state at byte grid0
 };
 extern "C" int dvbt_viterbi_decoder_create(const dvbt_viterbi_decoder_params *p, dvbt_viterbi_decoder **out)
@@ -357,6 +358,7 @@ static int viterbi_call(dvbt_viterbi_decoder *h, int nout, int nin, const void *
   const dvbt_tag *t = find_tag(sb, DVBT_TAG_SUPERFRAME_START, 0, (int64_t)nblocks * d_nsym);
   if (t) {                                                       // :213-229
     h->d_init = 0; h->steps = 0; h->in_total = 0; h->hist = 0; h->have_carry = false; h->grid0 = 0;
+    h->vp.chunk_bytes = h->chunk_next; h->verify = h->verify_next;   // (the test hooks: the chunk grid and the passes change where no state is carried)
     if (t->rel_offset > 0) { if (sb) sb->n_consumed = (int)t->rel_offset; return 0; }
     HIPCHK(hipMemsetAsync(h->proof.ctl + V3_CTL_ACC, 0, 3 * sizeof(int), s));
   }
@@ -380,7 +382,7 @@ static int viterbi_call(dvbt_viterbi_decoder *h, int nout, int nin, const void *
     ax.grid0 = g0; ax.carry_in = h->have_carry ? h->carry + h->cur * V3_SLOT : nullptr;
     const long long b0_last = g0 + (chunks - 1) * B;
     ax.carry_rel = (int)((out_hi - b0_last) / V3_BLK) * V3_BLK; ax.carry_out = h->carry + (h->cur ^ 1) * V3_SLOT;
-    launch_viterbi(s, (const uint8_t *)h->c.din.p, o, (const RxState *)nullptr, h->steps, h->vp, in_base, out_lo, produced, &ax, VIT_REPAIR, h->walk);
+    launch_viterbi(s, (const uint8_t *)h->c.din.p, o, (const RxState *)nullptr, h->steps, h->vp, in_base, out_lo, produced, &ax, h->verify, h->walk);
     h->cur ^= 1; h->have_carry = true; h->grid0 = b0_last + ax.carry_rel;
     if (!dev) WCHK(h->c.get(out, h->c.dout.p, (size_t)produced));
   }
@@ -427,6 +429,37 @@ extern "C" int dvbt_viterbi_decoder_proof(dvbt_viterbi_decoder *h, dvbt_viterbi_
   int acc[3] = {0, 0, 0};
   HIPCHK(hipMemcpy(acc, h->proof.ctl + V3_CTL_ACC, sizeof acc, hipMemcpyDeviceToHost));      // (blocking: behind everything the block's stream holds)
   out->chunks = acc[0]; out->decoded_again = acc[1]; out->sequential = acc[2]; out->not_proven = -1;
+  if (h->verify >= VIT_REPAIR_COUNT) {                           // the final check ran behind the last launch (dvbt_viterbi_decoder_set_verify)
+    int un = -1;
+    HIPCHK(hipMemcpy(&un, h->proof.ctl + V3_CTL_UNPROVEN, sizeof un, hipMemcpyDeviceToHost));
+    out->not_proven = un;
+  }
+  return DVBT_OK;
+}
+// Test hooks.  The chunk size of the block's launches: 0 = the default of 264 bytes, else a multiple of 24 (a block of windows) in [24, 264].  Adopted by the next call that carries a
+// superframe-start tag (a stream reset): the chunk grid never changes under a carried state.  proof.reserve grows with the chunk count and kTail covers the warm-up at any chunk size.
+extern "C" int dvbt_viterbi_decoder_set_chunk_bytes(dvbt_viterbi_decoder *h, int bytes)
+{
+  if (bytes == 0) bytes = 11 * V3_BLK;
+  if (bytes < V3_BLK || bytes > 11 * V3_BLK || bytes % V3_BLK != 0) return fail(DVBT_ERR_INVALID, "chunk size must be 0 (default) or a multiple of 24 in [24, 264]");
+  if (!h) return fail(DVBT_ERR_INVALID, "null handle");
+  h->chunk_next = bytes;
+  return DVBT_OK;
+}
+// dvbt_rx_params.viterbi_verify for the block's launches (-1 .. 4; the default is 0, proof + repair without the final check).  Adopted by the next call that
+// carries a superframe-start tag, like the chunk size: the plain decoders (-1) carry no state and the proof alone (2) carries an unrepaired one, so a stream keeps its mode
+extern "C" int dvbt_viterbi_decoder_set_verify(dvbt_viterbi_decoder *h, int mode)
+{
+  if (mode < VIT_PLAIN || mode > VIT_FORCE_CONFLICT) return fail(DVBT_ERR_INVALID, "verify mode must be in [-1, 4]");
+  if (!h) return fail(DVBT_ERR_INVALID, "null handle");
+  h->verify_next = mode;
+  return DVBT_OK;
+}
+// the 16 header words of the last launch's control block (k_viterbi3.hpp, V3_CTL_*); blocking, like _proof
+extern "C" int dvbt_viterbi_decoder_last_ctl(dvbt_viterbi_decoder *h, int out[16])
+{
+  if (!h || !out) return fail(DVBT_ERR_INVALID, "null argument");
+  HIPCHK(hipMemcpy(out, h->proof.ctl, V3_CTL_HDR * sizeof(int), hipMemcpyDeviceToHost));
   return DVBT_OK;
 }
 // the traceback's shortcut (k_viterbi3.hpp): always != 0 = every chain of the following calls walks all its hops; the counters of shortcut / walked iterations since the block was created

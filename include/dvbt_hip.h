@@ -214,6 +214,15 @@ int  dvbt_viterbi_decoder_set_warm_windows(dvbt_viterbi_decoder *h, int windows)
 int  dvbt_viterbi_decoder_proof(dvbt_viterbi_decoder *h, dvbt_viterbi_proof *out);
 /* always != 0: the traceback chains of the following calls walk every hop instead of taking the shortcut over chained best states (the same bytes; tests, measurements) */
 int  dvbt_viterbi_decoder_set_walk(dvbt_viterbi_decoder *h, int always);
+/* test hooks.  The chunk size of the block's launches: 0 = the default 264 bytes, else a multiple of 24 in [24, 264]; adopted by the next call that carries a
+ * superframe-start tag (a stream reset).  The same bytes at any size (tests/test_gpu_viterbi_handover.py) */
+int  dvbt_viterbi_decoder_set_chunk_bytes(dvbt_viterbi_decoder *h, int bytes);
+/* test hook: dvbt_rx_params.viterbi_verify (-1 .. 4) for the block's launches from the next stream reset on, 0 = the default.  With a mode >= 1 dvbt_viterbi_decoder_proof reports the
+ * last launch's final check in not_proven */
+int  dvbt_viterbi_decoder_set_verify(dvbt_viterbi_decoder *h, int mode);
+/* test hook, read-only and blocking: the 16 header words of the last launch's control block (chunks, decoded again, left to the sequential pass, not proven,
+ * decoded by the sequential pass, ..., the sums at [8..10], the shortcut's counters at [12..15]) */
+int  dvbt_viterbi_decoder_last_ctl(dvbt_viterbi_decoder *h, int out[16]);
 /* out[0], out[1]: blocks of 24 windows, per wavefront, whose bytes left by the shortcut / whose chains walked, since the block was created */
 int  dvbt_viterbi_decoder_shortcut(dvbt_viterbi_decoder *h, long long out[2]);
 void dvbt_viterbi_decoder_destroy(dvbt_viterbi_decoder *h);

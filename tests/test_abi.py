@@ -119,6 +119,28 @@ def test_no_cpu_fallback(g):
     assert L.dvbt_debug_acquire(*ok) == -2
 
 
+def test_viterbi_block_test_hooks_refuse_without_a_device(g):
+    """dvbt_viterbi_decoder_set_chunk_bytes / _set_verify / _last_ctl: a value out of range is refused before the handle is looked at, a null handle after it"""
+    L = g.lib()
+    L.dvbt_last_error.restype = C.c_char_p
+    for fn in (L.dvbt_viterbi_decoder_set_chunk_bytes, L.dvbt_viterbi_decoder_set_verify):
+        fn.argtypes = [C.c_void_p, C.c_int]
+    L.dvbt_viterbi_decoder_last_ctl.argtypes = [C.c_void_p, C.c_void_p]
+    fake = C.c_void_p(1)                                                    # never dereferenced: the value is refused first
+    for bad in (23, 25, 288, -24):
+        for h in (None, fake):
+            assert L.dvbt_viterbi_decoder_set_chunk_bytes(h, bad) == -1 and b"multiple of 24 in [24, 264]" in L.dvbt_last_error(), bad
+    for bad in (-2, 5):
+        for h in (None, fake):
+            assert L.dvbt_viterbi_decoder_set_verify(h, bad) == -1 and b"[-1, 4]" in L.dvbt_last_error(), bad
+    for ok in (0, 24, 48, 264):
+        assert L.dvbt_viterbi_decoder_set_chunk_bytes(None, ok) == -1 and b"null handle" in L.dvbt_last_error(), ok
+    for ok in (-1, 0, 1, 2, 3, 4):
+        assert L.dvbt_viterbi_decoder_set_verify(None, ok) == -1 and b"null handle" in L.dvbt_last_error(), ok
+    out = (C.c_int * 16)()
+    assert L.dvbt_viterbi_decoder_last_ctl(None, out) == -1 and L.dvbt_viterbi_decoder_last_ctl(None, None) == -1
+
+
 def test_product_does_not_import_oracle():
     """The product path must not route through the oracle (or any CPU fallback)."""
     for dirpath, _, files in os.walk(os.path.join(ROOT, "gr_dvbt_amd")):

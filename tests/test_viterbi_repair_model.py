@@ -10,22 +10,16 @@ state representation -- the 64 path metrics right behind a get_output call (lib/
 
 With chunks of 42 windows and a warm-up of 10 on garbage the decoders rarely merge in time: most chunks are listed, repaired decoders do not arrive where the unproven ones did,
 the walk has work -- the hand-overs that real chunk sizes (thousands of windows) never reach.  Whatever the sizes: the assembled bytes are the streaming decoder's, every one."""
-import ctypes as C
+import os
+import sys
 
 import numpy as np
 import pytest
 
-UNIT_IN, UNIT_OUT = 32, 21          # QAM64 7/8: 24 trellis bits' worth x 14 = the smallest stretch that is whole in bytes in, bytes out, puncture periods and 16-bit output cadences
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import vitrepairref  # noqa: E402
 
-
-def _lib(po):
-    L = po.lib()
-    L.o_viterbi_decode_n.restype = C.c_size_t
-    L.o_viterbi_decode_snap.restype = C.c_size_t
-    L.o_viterbi_decode_snap.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
-    L.o_viterbi_decode_from.restype = C.c_size_t
-    L.o_viterbi_decode_from.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
-    return L
+UNIT_IN, UNIT_OUT = vitrepairref.UNITS[(6, 7)]          # QAM64 7/8: 24 trellis bits' worth x 14 = the smallest stretch that is whole in bytes in, bytes out, puncture periods and 16-bit output cadences
 
 
 @pytest.mark.parametrize("Q,W,kind,seed", [(2, 10, "garbage", 11), (2, 10, "garbage", 12), (2, 10, "garbage", 13), (1, 5, "garbage", 14), (1, 5, "6 %", 15), (2, 24, "6 %", 11),
@@ -34,8 +28,6 @@ def _lib(po):
                               "168 / 24, garbage", "756 / 72 (the product's warm-up), 6 %"])
 def test_check_repair_and_walk_give_the_streaming_decoder(po, Q, W, kind, seed):
     c = po.cfg(po.QAM64, po.C7_8, po.T2k)
-    L = _lib(po)
-    nt = 24
     B = UNIT_OUT * Q                                                        # chunk size in bytes = windows
     nunits = 40 * Q if Q <= 8 else 12 * Q
     rng = np.random.RandomState(seed)
@@ -49,66 +41,18 @@ def test_check_repair_and_walk_give_the_streaming_decoder(po, Q, W, kind, seed):
             vin ^= (rng.rand(len(vin)) < 0.06).astype(np.uint8) << b
     vin = np.ascontiguousarray(vin)
     nch = nunits // Q - 2                                                   # chunks c = 0 .. nch - 1; chunk c = bytes [c B + W - 1, (c + 1) B + W - 1)
-    # ---- the streaming decoder, and (for the last assertion only) its state at every chunk's first window
-    at = np.array([cc * B + W for cc in range(1, nch + 1)], np.int64)
-    full = np.zeros(nunits * UNIT_OUT + 64, np.uint8)
-    truth = np.zeros((len(at), 64), np.uint8)
-    nfull = L.o_viterbi_decode_snap(C.byref(c), vin.ctypes.data, len(vin), full.ctypes.data, at.ctypes.data, len(at), truth.ctypes.data)
-    assert nfull >= nch * B + W - 1
-    out = np.zeros_like(full)
-    own = np.zeros((nch + 1, 64), np.uint8); pred = np.zeros((nch + 1, 64), np.uint8); fix = np.zeros((nch + 1, 64), np.uint8)
-    span = (2 * B + W + nt + UNIT_OUT) // UNIT_OUT + 1                      # units a chunk decoder / a repair reads
-
-    def sub(cc):
-        return np.ascontiguousarray(vin[cc * Q * UNIT_IN:(cc * Q + span) * UNIT_IN])
-
-    # ---- the chunk decoders: chunk 0 IS the streaming decoder (it starts the stream); chunk c >= 1 starts W windows early from zero metrics
-    out[:B + W - 1] = full[:B + W - 1]; pred[1] = truth[0]
-    for cc in range(1, nch):
-        o = np.zeros(span * UNIT_OUT + 64, np.uint8); s2 = np.zeros((2, 64), np.uint8)
-        L.o_viterbi_decode_snap(C.byref(c), sub(cc).ctypes.data, span * UNIT_IN, o.ctypes.data, np.array([W, B + W], np.int64).ctypes.data, 2, s2.ctypes.data)
-        out[cc * B + W - 1:(cc + 1) * B + W - 1] = o[W - 1:B + W - 1]
-        own[cc] = s2[0]; pred[cc + 1] = s2[1]
-
-    def job(cc, state):
-        """decode chunk cc from `state` at its first window: its bytes, the state at the next chunk's first window"""
-        o = np.zeros(span * UNIT_OUT + 64, np.uint8); e = np.zeros((1, 64), np.uint8)
-        L.o_viterbi_decode_from(C.byref(c), sub(cc).ctypes.data, span * UNIT_IN, o.ctypes.data, W, np.ascontiguousarray(state).ctypes.data, np.array([B + W], np.int64).ctypes.data, 1, e.ctypes.data)
-        out[cc * B + W - 1:(cc + 1) * B + W - 1] = o[W - 1:B + W - 1]
-        return e[0].copy()
-    # ---- check
-    listed = [cc for cc in range(1, nch) if (own[cc] != pred[cc]).any()]
-    plain_wrong = int((out[:nch * B + W - 1] != full[:nch * B + W - 1]).sum())
-    # ---- repair (every listed chunk on its own: the order does not matter)
-    flagged = np.zeros(nch + 1, bool)
-    for cc in listed:
-        own[cc] = pred[cc]
-        end = job(cc, pred[cc])
-        if cc + 1 < nch and (end != pred[cc + 1]).any():
-            fix[cc + 1] = end; flagged[cc + 1] = True
-    # ---- the walk
-    pos, walked = 0, 0
-    while True:
-        nxt = [cc for cc in range(pos + 1, nch) if flagged[cc]]
-        if not nxt:
-            break
-        cc = nxt[0]; state = fix[cc].copy()
-        while True:
-            own[cc] = state; pred[cc] = state
-            end = job(cc, state); walked += 1
-            if cc + 1 >= nch:
-                pos = nch; break
-            eq = (end == own[cc + 1]).all()
-            pred[cc + 1] = end
-            if eq:
-                pos = cc + 1; break
-            cc += 1; state = end
+    # ---- the streaming decoder, the chunk decoders (chunk 0 IS the streaming decoder: it starts the stream; chunk c >= 1 starts W windows early from zero metrics), check, repair, walk
+    R = vitrepairref.Replay(po, c, B, W, vin, start="fresh", nch=nch)
+    assert R.nfull >= nch * B + W - 1
+    r = R.launch()
+    out, full, own, pred, truth, listed, walked, plain_wrong = r["out"], R.full, r["own"], r["pred"], R.truth, r["listed"], r["walked"], R.plain_wrong
+    flagged = np.zeros(nch + 1, bool); flagged[r["flagged"]] = True
     # ---- every byte is the streaming decoder's; the chain of states is consistent and IS the streaming decoder's
     n = nch * B + W - 1
     print(f"{nch} chunks of {B} windows, warm-up {W}, {kind}: {len(listed)} listed ({plain_wrong} bytes of the plain chunk decoders differ), {int(flagged.sum())} handed to the walk, {walked} decoded by it")
     assert (out[:n] == full[:n]).all(), int((out[:n] != full[:n]).sum())
     for cc in range(1, nch):
-        assert (own[cc] == pred[cc]).all() and (pred[cc] == truth[cc - 1]).all(), cc
+        assert (own[cc] == pred[cc]).all() and (pred[cc] == truth[cc]).all(), cc
     if Q <= 2 and kind == "garbage":
         assert len(listed) > nch // 10                                        # the small sizes list many chunks (and, on some seeds, reach the hand-over and the walk: printed)
     if (Q, W, seed) in ((2, 10, 11), (1, 5, 14)):
