@@ -10,12 +10,12 @@
  * /root/reference).  Pinning status (see DESIGN.md "Oracle pinning"):
  *   - Viterbi ACS/traceback: pinned bit-for-bit against the reference's own
  *     lib/d_viterbi.c + lib/d_tab.c compiled unmodified into oracle/_ref/.
- *   - All other stages: the reference holds no tests, fixtures or golden vectors
- *     (every qa_*.cc / qa_*.py is an empty stub) and their sources need GNU Radio
- *     headers that are absent here, so they cannot be compiled: PARITY UNPINNED
- *     by reference execution; pinned only by the known-answer values captured
- *     from the compiled reference in SURVEY.md Appendix F (tests/test_oracle_kat.py)
- *     and by TX->RX loopback closure.
+ *   - demod_reference_signals, demapper / mapper, symbol and bit (de)interleavers, the viterbi_decoder block, the byte
+ *     (de)interleaver, Reed-Solomon, energy dispersal / descramble, inner coder, reference_signals: pinned bit-for-bit
+ *     against the reference's own block sources compiled unmodified into oracle/_ref/libdvbt_blocks_ref.so (stand-in
+ *     GNU Radio headers: ref_standin/, driver: ref_driver.cc, tests/test_oracle_ref_blocks.py).
+ *   - Acquisition, resampler, FFT: third-party arithmetic that is absent here; pinned by the known-answer values of
+ *     SURVEY.md Appendix F (tests/test_oracle_kat.py), loopback closure and the channel cases.
  */
 #ifndef DVBT_ORACLE_H
 #define DVBT_ORACLE_H
@@ -109,6 +109,8 @@ size_t o_viterbi_decode_from(const o_cfg *c, const unsigned char *in, size_t nsy
 /* closed form of the 12 FIFOs starting from all-zero state; n bytes -> n bytes */
 void o_conv_deinterleave(const unsigned char *in, unsigned char *out, size_t n);
 void o_conv_interleave(const unsigned char *in, unsigned char *out, size_t n);
+/* the block's reaction to a superframe_start tag, in calls of one pair of items: how many of the nbytes in front of the tag it takes (the rest is dropped) */
+size_t o_conv_deint_taken_before_tag(size_t nbytes);
 
 /* ---- energy dispersal / descramble (next-row component) ---- */
 void o_energy_prbs(unsigned char *seq1504); /* xor pattern for one 8-packet group, byte0 of each pkt=0 */
@@ -156,6 +158,8 @@ int o_demod_work(o_demod *d, const ocf *in, ocf *out, int sync_start_tag,
 /* ts: npackets*188 bytes (byte0=0x47). Produces whole OFDM symbols only.
  * returns number of complex samples written to iq (<= cap). scale multiplies the IFFT output. */
 size_t o_tx_symbols_for_packets(const o_cfg *c, size_t npackets);
+/* the generator's inner coder (the one loop o_tx_generate_from runs too), from a zero register: nbytes -> nbytes*8*n/(k*m) bytes of m coded bits each */
+size_t o_inner_code(const o_cfg *c, const unsigned char *in, size_t nbytes, unsigned char *out);
 size_t o_tx_generate(const o_cfg *c, const unsigned char *ts, size_t npackets, float scale,
                      ocf *iq, size_t cap_samples, ocf *freq_taps /* optional nsym*N or NULL */);
 size_t o_tx_generate_from(const o_cfg *c, const unsigned char *ts, size_t npackets, size_t packet0, float scale,

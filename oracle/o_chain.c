@@ -158,7 +158,7 @@ int o_rx_run_cut(const o_cfg *c, const ocf *iq, size_t nsamples, float snr_db, i
     size_t nv = o_viterbi_decode_n(c, b2 + per_start[pi] * (size_t)P, (size_t)nin_l, vit + nvit);
     nb_g = nblocks_g * (long long)c->k * bsize / 8 - o_vit_ntraceback(c->code_rate);
     if (nb_g < 0) nb_g = 0;
-    if (pi + 1 < nper) nv = (nv / 3264) * 3264;                        /* convolutional_deinterleaver_impl.cc:109-120 */
+    if (pi + 1 < nper) nv = o_conv_deint_taken_before_tag(nv);          /* convolutional_deinterleaver_impl.cc:109-120 */
     nvit += nv;
   }
   if (nper > 1) nb_g = (long long)nvit;                              /* several periods: the item count below follows the concatenated stream */

@@ -4,7 +4,7 @@
  * process_cpilot_data :715-744, compute_oneshot_csft :747-790, frequency_correction :793-819,
  * process_spilot_data :536-689, process_tps_data :919-1032, process_payload_data :1065-1124,
  * parse_input :1189-1248; and lib/demod_reference_signals_impl.cc:73-77,97-150.
- * PARITY UNPINNED by reference execution (needs GNU Radio headers); float-tolerance tap. */
+ * Pinned against the reference's block, executed: tags, counts and the equalised carriers' float bits (tests/test_oracle_ref_blocks.py). */
 #include "dvbt_oracle.h"
 #include <math.h>
 #include <stdlib.h>

@@ -13,6 +13,12 @@ void o_conv_deinterleave(const unsigned char *in, unsigned char *out, size_t n)
   }
 }
 
+/* lib/convolutional_deinterleaver_impl.cc:61,109-120 in the smallest calls (a pair of items, set_output_multiple(2)): of nbytes that lie in front of a
+ * superframe_start tag the block takes the whole pairs of items; a call that finds the tag further in consumes up to it and returns nothing, so the
+ * remainder is dropped (and the FIFOs go on: nothing is reset). */
+size_t o_conv_deint_taken_before_tag(size_t nbytes)
+{ return (nbytes / 3264) * 3264; }
+
 /* lib/convolutional_interleaver_impl.cc:49-50,73-82: branch j delay 17*j */
 void o_conv_interleave(const unsigned char *in, unsigned char *out, size_t n)
 {

@@ -30,6 +30,34 @@ static void codeword(unsigned *reg, int bit, int *x, int *y)
   *y = ((r >> 6) ^ (r >> 4) ^ (r >> 3) ^ (r >> 1) ^ r) & 1;   /* G2 = 133 oct */
 }
 
+/* inner_coder (lib/inner_coder_impl.cc:33-121,225-254), the ONE loop of this file: nbits input bits from bit bit0 of in[] on, MSB first, through the mother
+ * code and the puncturing of the code rate, packed m coded bits to an output byte.  The state goes on from call to call (the generator calls it once per
+ * OFDM symbol, o_inner_code once for everything).  returns the bytes written */
+typedef struct { unsigned reg; size_t pphase; int acc, nacc; } coder_state;
+
+static size_t coder_run(coder_state *st, const o_cfg *c, const unsigned char *in, size_t bit0, size_t nbits, unsigned char *out)
+{
+  int plen; const unsigned char *punct = o_vit_puncture(c->code_rate, &plen);
+  size_t nout = 0;
+  for (size_t bitpos = bit0; bitpos < bit0 + nbits; bitpos++) {
+    int xy[2]; codeword(&st->reg, (in[bitpos >> 3] >> (7 - (bitpos & 7))) & 1, &xy[0], &xy[1]);
+    for (int h = 0; h < 2; h++)
+      if (punct[st->pphase + h]) {
+        st->acc = (st->acc << 1) | xy[h];
+        if (++st->nacc == c->m) { out[nout++] = (unsigned char)st->acc; st->acc = 0; st->nacc = 0; }
+      }
+    st->pphase = (st->pphase + 2) % (size_t)plen;
+  }
+  return nout;
+}
+
+/* the narrow entry into it: nbytes input bytes from a zero register; nbytes * 8 * n / k must be a multiple of m */
+size_t o_inner_code(const o_cfg *c, const unsigned char *in, size_t nbytes, unsigned char *out)
+{
+  coder_state st = { 0, 0, 0, 0 };
+  return coder_run(&st, c, in, 0, nbytes * 8, out);
+}
+
 size_t o_tx_generate(const o_cfg *c, const unsigned char *ts, size_t npackets, float scale,
                      ocf *iq, size_t cap, ocf *freq_taps)
 { return o_tx_generate_from(c, ts, npackets, 0, scale, iq, cap, freq_taps); }
@@ -60,10 +88,7 @@ size_t o_tx_generate_from(const o_cfg *c, const unsigned char *ts, size_t npacke
   }
   o_conv_interleave(rsout, il, nbytes);
 
-  /* inner coder: puncture pattern == the depuncture vector of the RX side */
-  int plen; const unsigned char *punct = o_vit_puncture(c->code_rate, &plen);
-  size_t coded_per_sym = (size_t)c->payload * c->m;
-  unsigned char *cbits = malloc(coded_per_sym + 16);
+  /* inner coder (coder_run): puncture pattern == the depuncture vector of the RX side */
   unsigned char *sym_a = malloc(c->payload), *sym_b = malloc(c->payload);
   int *H = malloc(sizeof(int) * c->payload); o_sym_H(c, H);
   ocf *points = malloc(sizeof(ocf) * c->csize); o_constellation(c, 1.0f, points);
@@ -71,23 +96,13 @@ size_t o_tx_generate_from(const o_cfg *c, const unsigned char *ts, size_t npacke
   ocf *freq = malloc(sizeof(ocf) * N), *timeb = malloc(sizeof(ocf) * N);
   ocf *tps_val = calloc(c->n_tps, sizeof(ocf));
   unsigned char tps_data[68];
-  unsigned enc_reg = 0; size_t pphase = 0;
+  coder_state enc = { 0, 0, 0, 0 };
   int symbol_index = 0, frame_index = 0;
 
   for (size_t s = 0; s < nsym; s++) {
-    /* encode ib bytes, MSB first (inner_coder_impl.cc:225-254) */
-    size_t nb = 0;
-    for (size_t i = 0; i < ibits; i++, bitpos++) {
-      int x, y; codeword(&enc_reg, (il[bitpos >> 3] >> (7 - (bitpos & 7))) & 1, &x, &y);
-      if (punct[pphase]) cbits[nb++] = (unsigned char)x;
-      if (punct[pphase + 1]) cbits[nb++] = (unsigned char)y;
-      pphase = (pphase + 2) % (size_t)plen;
-    }
-    for (int i = 0; i < c->payload; i++) {
-      int v = 0;
-      for (int j = 0; j < c->m; j++) v |= cbits[(size_t)c->m * i + j] << (c->m - 1 - j);
-      sym_a[i] = (unsigned char)v;
-    }
+    /* one symbol's information bits: a whole number of puncture periods and of m-bit words (inner_coder_impl.cc:225-254) */
+    coder_run(&enc, c, il, bitpos, ibits, sym_a);
+    bitpos += ibits;
     o_bit_interleave(c, sym_a, sym_b, c->payload);
     o_sym_interleave(c, H, sym_b, sym_a, symbol_index, 1);
 
@@ -119,7 +134,7 @@ size_t o_tx_generate_from(const o_cfg *c, const unsigned char *ts, size_t npacke
     for (int i = 0; i < cp; i++) o[i] = scale * timeb[N - cp + i];
     for (int i = 0; i < N; i++) o[cp + i] = scale * timeb[i];
   }
-  free(disp); free(rsout); free(il); free(cbits); free(sym_a); free(sym_b); free(H);
+  free(disp); free(rsout); free(il); free(sym_a); free(sym_b); free(H);
   free(points); free(wk); free(freq); free(timeb); free(tps_val);
   return nsym * (size_t)(N + cp);
 }
