@@ -7,6 +7,8 @@ import pytest
 import gr_dvbt_amd as g
 from gr_dvbt_amd import multi
 
+import streamcases
+
 
 def oracle_piece(po, c, iq, sym_off):
     r = po.rx(c, iq, want=("ts",), sym_off=sym_off)
@@ -15,19 +17,28 @@ def oracle_piece(po, c, iq, sym_off):
     return r, r["ts"]
 
 
-CASES = [
-    (g.QAM16, g.C1_2, g.T2k, 7, (2, 3, 4)),       # d_fi_start = 3, 504 packets per superframe
-    (g.QAM64, g.C7_8, g.T8k, 4, (2, 3)),          # d_fi_start = 2 (one frame early), 5292 packets per superframe (odd multiple of 4)
-    (g.QPSK, g.C2_3, g.T2k, 6, (3,)),             # decoded bits per symbol not a whole number of bytes... per superframe they are
+CASES = [                                                   # (the ids these three have had since before the guard was a parameter)
+    pytest.param(g.QAM16, g.C1_2, g.T2k, g.G1_32, 7, (2, 3, 4), id="1-0-0-7-parts_list0"),   # d_fi_start = 3, 504 packets per superframe
+    pytest.param(g.QAM64, g.C7_8, g.T8k, g.G1_32, 4, (2, 3), id="2-4-1-4-parts_list1"),      # d_fi_start = 2 (one frame early), 5292 packets per superframe (odd multiple of 4)
+    pytest.param(g.QPSK, g.C2_3, g.T2k, g.G1_32, 6, (3,), id="0-1-0-6-parts_list2"),         # decoded bits per symbol not a whole number of bytes... per superframe they are
 ]
+# every other guard interval, every code rate (tests/streamcases.py): L = N + cp and the post-roll move every sample offset of the plan
+CELL_CASES = [pytest.param(k.const, k.cr, k.mode, k.guard, streamcases.cut_size(k)[0], (streamcases.cut_size(k)[1],), id=streamcases.cell_id(k)) for k in streamcases.CELLS]
 
 
-@pytest.mark.parametrize("const,cr,mode,nsf,parts_list", CASES)
-def test_stitched_pieces_equal_the_single_chain(po, const, cr, mode, nsf, parts_list):
-    c = po.cfg(const, cr, mode)
-    d = g.get_dims(const, cr, mode)
+def test_the_case_table_states_the_dimensions():
+    for k in streamcases.CELLS:
+        d = g.get_dims(k.const, k.cr, k.mode, k.guard)
+        assert (d.fft_length + d.cp_length, multi.post_symbols(d)) == (k.L, k.post), streamcases.cell_id(k)
+
+
+@pytest.mark.parametrize("const,cr,mode,guard,nsf,parts_list", CASES + CELL_CASES)
+def test_stitched_pieces_equal_the_single_chain(po, const, cr, mode, guard, nsf, parts_list):
+    c = po.cfg(const, cr, mode, guard)
+    d = g.get_dims(const, cr, mode, guard)
     iq = po.stream_slice(c, nsf, 11)
     one = po.rx(c, iq, want=("ts",))
+    assert len(one["lock_periods"]) == 1
     assert one["first_out_symbol"] == (204 if (const == g.QAM64 and mode == g.T8k) else 272)
     for parts in parts_list:
         cuts = multi.plan_cuts(d, len(iq), 0, one["first_out_symbol"], parts)
