@@ -1003,6 +1003,169 @@ class Spectrum(_Handle):
                                self.p.hop or self.p.fft_size // 2, self.p.window, self.sample_rate)
 
 
+SOUNDER_WINDOWS = {"rect": 0, "rectangular": 0, "hann": 1}
+
+
+class SounderParams(C.Structure):
+    _fields_ = [("device", C.c_int), ("transmission_mode", C.c_int), ("window", C.c_int), ("first_index", C.c_int)]
+
+
+class SounderResult(C.Structure):
+    _fields_ = [("symbols_pushed", C.c_longlong), ("groups_used", C.c_longlong), ("groups_skipped", C.c_longlong), ("M", C.c_int), ("Kp", C.c_int)]
+
+
+_PI = C.POINTER(C.c_int)
+
+
+@_typed_once
+def _sounder_lib(L):
+    L.dvbt_sounder_create.argtypes = [C.POINTER(SounderParams), C.POINTER(C.c_void_p)]
+    L.dvbt_sounder_push.argtypes = [C.c_void_p, C.c_void_p, _PI, _PI, _PI, C.c_size_t]
+    L.dvbt_sounder_push_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+    L.dvbt_sounder_read.argtypes = [C.c_void_p, C.POINTER(SounderResult), C.POINTER(C.c_double), C.c_size_t, C.POINTER(C.c_double), C.c_size_t]
+    L.dvbt_sounder_reset.argtypes = [C.c_void_p]
+    L.dvbt_sounder_destroy.argtypes = [C.c_void_p]
+    L.dvbt_device_malloc.restype = C.c_void_p
+    L.dvbt_device_malloc.argtypes = [C.c_size_t]
+    L.dvbt_device_free.argtypes = [C.c_void_p]
+    L.dvbt_copy_to_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+
+
+class SounderReading:
+    """What Sounder.read() returns: `pdp` (M doubles: the sums of |h|^2 over the used groups, bin m a delay of 2 m / 3 samples), `resp` (Kp doubles: the sums
+    of |E|^2, carrier 3 j) and the fields of dvbt_sounder_result.  The helpers are numpy in double on the host and need no GPU."""
+
+    def __init__(self, pdp, resp, symbols_pushed, groups_used, groups_skipped, mode, sample_rate=64e6 / 7):
+        self.pdp, self.resp = np.asarray(pdp, np.float64), np.asarray(resp, np.float64)
+        self.symbols_pushed, self.groups_used, self.groups_skipped = int(symbols_pushed), int(groups_used), int(groups_skipped)
+        self.mode, self.sample_rate = int(mode), float(sample_rate)
+        self.M, self.Kp = len(self.pdp), len(self.resp)
+
+    def delays(self, sample_rate=None):
+        """the delay of every bin relative to the strongest, signed (bins from M / 2 on behind it read as pre-echoes), in samples, or in seconds for a
+        sample rate"""
+        m0 = int(np.argmax(self.pdp))
+        d = ((np.arange(self.M) - m0 + self.M // 2) % self.M - self.M // 2) * (2.0 / 3.0)
+        return d if sample_rate is None else d / float(sample_rate)
+
+    def _five(self, m):
+        return float(self.pdp[(m + np.arange(-2, 3)) % self.M].sum())
+
+    def paths(self, threshold_db=-30.0):
+        """[(delay in samples, level in dB relative to the strongest)] of the local maxima at or above the threshold, the strongest (0, 0) first, then by
+        delay.  A level is the sum of the five bins around the maximum over the same sum around the strongest.  A local maximum is a bin above every other
+        within five bins (3.3 samples) of it: the Hann window's main lobe is 7.2 bins wide and its first side lobe stands 4.5 bins from the centre, where the
+        five bins would reach back into the main lobe."""
+        p, d = self.pdp, self.delays()
+        m0 = int(np.argmax(p))
+        ref = self._five(m0)
+        if not ref > 0.0:
+            return []
+        out = []
+        around = np.max([np.roll(p, k) for k in range(-5, 6) if k], axis=0)
+        for m in np.nonzero(p > around)[0]:
+            lev = 10.0 * np.log10(self._five(int(m)) / ref) if self._five(int(m)) > 0.0 else -np.inf
+            if m != m0 and lev >= threshold_db:
+                out.append((float(d[m]), float(lev)))
+        return [(0.0, 0.0)] + sorted(out)
+
+    def outside_guard_db(self, cp):
+        """10 log10 of the share of the profile's power whose delay relative to the strongest path lies outside [0, cp] samples -- by more than four bins
+        (2.7 samples), the half width of the window's main lobe, which a path at 0 or at cp itself spreads over"""
+        d, total = self.delays(), float(self.pdp.sum())
+        outside = float(self.pdp[(d < -8.0 / 3.0 - 1e-9) | (d > cp + 8.0 / 3.0 + 1e-9)].sum())
+        return 10.0 * np.log10(outside / total) if outside > 0.0 and total > 0.0 else -np.inf
+
+    def ripple_db(self):
+        """max over min of the amplitude response's power over the Kp carriers, in dB"""
+        lo, hi = float(self.resp.min()), float(self.resp.max())
+        return 10.0 * np.log10(hi / lo) if lo > 0.0 else np.inf
+
+
+class Sounder(_Handle):
+    """dvbt_sounder_*: a channel sounder on the GPU.  It consumes demodulated symbols -- rows of N complex64 in fft-shifted order, with the symbol index, the
+    integer carrier offset and cp_start of each -- as one stream over any number of push() / push_device() calls and accumulates the echo profile and the
+    amplitude response from the scattered pilots of every four consecutive symbols (include/dvbt_hip.h has the definitions).  read() synchronises and returns
+    a SounderReading; it does not disturb the accumulation.  A stream cut into calls gives the bits of one call."""
+    _prefix = "dvbt_sounder"
+
+    def __init__(self, mode, window="hann", first_index=0, device=0, sample_rate=64e6 / 7):
+        self.L = _sounder_lib()
+        if isinstance(window, str):
+            if window.lower() not in SOUNDER_WINDOWS:
+                raise DvbtError(f"window must be one of {sorted(SOUNDER_WINDOWS)}")
+            window = SOUNDER_WINDOWS[window.lower()]
+        self.p = SounderParams(int(device), int(mode), int(window), int(first_index))
+        self.sample_rate = float(sample_rate)
+        self.h = C.c_void_p()
+        self._ints = None
+        _chk(self.L.dvbt_sounder_create(C.byref(self.p), C.byref(self.h)))
+        self.N = 8192 if int(mode) == T8k else 2048
+
+    def push(self, rows, index=None, offset=None, cp_start=None):
+        """rows [n][N] complex64 from the host and up to three int arrays of n (None: index first_index + position, offset 0, cp_start 0); continues the
+        stream"""
+        rows = np.ascontiguousarray(rows, dtype=np.complex64).reshape(-1, self.N)
+        ints = [None if a is None else np.ascontiguousarray(a, dtype=np.int32).reshape(-1) for a in (index, offset, cp_start)]
+        if any(a is not None and len(a) != len(rows) for a in ints):
+            raise DvbtError("index, offset and cp_start take one value per row")
+        _chk(self.L.dvbt_sounder_push(self.h, rows.ctypes.data_as(C.c_void_p), *[None if a is None else a.ctypes.data_as(_PI) for a in ints], len(rows)))
+
+    def push_device(self, rows_ptr, nsym, index_ptr=None, offset_ptr=None, cp_start_ptr=None, stream=None):
+        """device pointers (ints; the three int arrays may be None): enqueues on `stream` (a hipStream_t as int, None: the default stream)"""
+        _chk(self.L.dvbt_sounder_push_device(self.h, C.c_void_p(rows_ptr), *[C.c_void_p(p) if p else None for p in (index_ptr, offset_ptr, cp_start_ptr)],
+                                             nsym, C.c_void_p(stream) if stream else None))
+
+    def read(self):
+        r = SounderResult()
+        M, Kp = self.N // 2, (1705 if self.N == 2048 else 6817) // 3 + 1
+        pdp, resp = np.zeros(M, np.float64), np.zeros(Kp, np.float64)
+        _chk(self.L.dvbt_sounder_read(self.h, C.byref(r), pdp.ctypes.data_as(C.POINTER(C.c_double)), M, resp.ctypes.data_as(C.POINTER(C.c_double)), Kp))
+        assert (r.M, r.Kp) == (M, Kp)
+        return SounderReading(pdp, resp, r.symbols_pushed, r.groups_used, r.groups_skipped, self.p.transmission_mode, self.sample_rate)
+
+    def push_rx(self, rx, first_row=0):
+        """the last finished segment of an Rx(taps=True): rows first_row .. n_symbols - 2 of its FFT tap straight from the device, with the symbol-index,
+        carrier-offset and cp_start taps (4 bytes a symbol each, which the receiver keeps inside per-symbol records: read to the host and put back as three
+        arrays)"""
+        if rx.report is None:
+            raise DvbtError("the receiver has not run a segment")
+        n = rx.report.n_symbols - 1 - int(first_row)
+        rows = rx.tap_device_ptr(TAP_FFT)
+        if first_row < 0 or not rows:
+            raise DvbtError("no FFT tap to read")
+        if n <= 0:
+            return
+        ints = np.stack([np.asarray(rx.tap(t)[first_row:first_row + n], np.int32) for t in (TAP_SYMBOL_INDEX, TAP_FREQ_OFFSET, TAP_CP_START)])
+        if ints.shape != (3, n):
+            raise DvbtError("the receiver's taps are shorter than its report (taps=True is needed)")
+        self._free_ints()
+        self._ints = self.L.dvbt_device_malloc(ints.nbytes)
+        if not self._ints:
+            raise DvbtError("no device memory for the int arrays")
+        ints = np.ascontiguousarray(ints)
+        _chk(self.L.dvbt_copy_to_device(C.c_void_p(self._ints), ints.ctypes.data_as(C.c_void_p), ints.nbytes))
+        self.push_device(rows + 8 * self.N * int(first_row), n, self._ints, self._ints + 4 * n, self._ints + 8 * n)
+        _chk(self.L.dvbt_synchronize(None))        # the int arrays and the receiver's tap may change once this returns
+
+    @classmethod
+    def from_rx(cls, rx, window="hann", first_row=0):
+        """a sounder of the receiver's mode and device that has been pushed its last finished segment (push_rx)"""
+        s = cls(rx.p.transmission_mode, window, 0, rx.p.device)
+        s.push_rx(rx, first_row)
+        return s
+
+    def _free_ints(self):
+        if getattr(self, "_ints", None):
+            self.L.dvbt_device_free(C.c_void_p(self._ints))
+            self._ints = None
+
+    def close(self):
+        if self.h:
+            self._free_ints()
+        super().close()
+
+
 # ------------------------------------------------------------------ per-block C ABI (one triple per reference block)
 TAG_SYNC_START, TAG_SUPERFRAME_START, TAG_SYMBOL_INDEX = 1, 2, 3
 

@@ -31,6 +31,7 @@
 #include "k_fading.hpp"
 #include "k_rf.hpp"
 #include "k_spectrum.hpp"
+#include "k_sounder.hpp"
 
 using namespace dvbt;
 using hip_own::DevMem; using hip_own::PinMem; using hip_own::Stream; using hip_own::Event; using hip_own::CallOrder;
@@ -2076,3 +2077,4 @@ extern "C" int dvbt_debug_acquire(dvbt_rx *h, const void *iq_host, size_t nsampl
 #include "dvbt_fading.inc"
 #include "dvbt_rf.inc"
 #include "dvbt_spectrum.inc"
+#include "dvbt_sounder.inc"

@@ -1150,6 +1150,49 @@ int  dvbt_spectrum_read(dvbt_spectrum *h, dvbt_spectrum_result *result, double *
 int  dvbt_spectrum_reset(dvbt_spectrum *h);   /* back to the state after create */
 void dvbt_spectrum_destroy(dvbt_spectrum *h);
 
+/* ------------------------------------------------------------------ sounder: the echo profile and the amplitude response from the scattered pilots
+ * A measurement block (csrc/k_sounder.hpp): it consumes demodulated symbols as a stream of fft-shifted rows, changes nothing and accumulates on the device.
+ * Every fourth symbol has a scattered pilot on every twelfth carrier, so four consecutive symbols give the channel on every third carrier, and the inverse
+ * transform of that comb is the impulse response over Tu / 3.
+ *   Mode       2k or 8k, with N, K (1705 / 6817) and zl = zeros_on_left as dvbt_get_dims gives them.  Kp = (K - 1) / 3 + 1 (569 / 2273), M = N / 2
+ *              (1024 / 4096), w_k = +-4/3 the pilots' reference values.
+ *   Input      per symbol s (the stream position, counted over all calls since create or reset) one row Y_s of N complex64 in fft-shifted order -- the
+ *              layout of DVBT_TAP_FFT, of dvbt_fft with shift and of dvbt_tx_read_carriers -- and three int32: symbol_index (0..67), freq_offset (-8..7)
+ *              and cp_start.  Each of the three arrays may be NULL: 0, 0 and the index (first_index + s) mod 68, for rows straight from a modulator.
+ *   Group      group g is the symbols [4 g, 4 g + 4).  It is USED iff the four indices are consecutive mod 68 (and in 0..67), the four offsets are equal
+ *              (and in -8..7) and |d_i| <= 64, d_i = cp_start[4 g + i] - cp_start[4 g].  Any other group is SKIPPED and counted; it adds nothing.
+ *   Symbol     of a used group, with l = index mod 4, o = freq_offset, c0 = (K - 1) / 2:
+ *                tau_i(k) = cis(-2 pi ((k - c0) d_i mod N) / N)          (an exact N-th root of unity: the FFT's own twiddle table)
+ *                c_i      = sum_k Y[zl + k + o] w_k tau_i(k)             over the continual-pilot carriers
+ *                r_i      = c_0 conj(c_i) / |c_0 conj(c_i)|              (1 where that is 0 or not finite)
+ *                E[k / 3] = Y[zl + k + o] w_k (9/16) tau_i(k) r_i        for k = 3 l + 12 p < K
+ *              tau undoes the move of the receiver's FFT window inside the group, r the common phase between its symbols.  Each of the Kp entries is
+ *              written exactly once per group.
+ *   Profile    per used group x[j] = E[j] win[j] for j < Kp and 0 up to M; win is 0 rectangular or 1 periodic Hann, 0.5 - 0.5 cos(2 pi j / Kp), a float
+ *              table computed in double.  h[m] = (sum_j x[j] e^{+2 pi i j m / M}) / sum win, so that a single unit path reads |h|^2 = 1.
+ *              pdp[m] += |h[m]|^2 and resp[j] += |E[j]|^2: both are sums over the used groups.
+ *   Geometry   bin m is a delay of 2 m / 3 samples; the profile is periodic in N / 3 samples; bins from M / 2 on read as negative delays (pre-echoes).
+ * A stream cut into calls of any sizes (0 and 1 included) gives the pdp, resp and counts of one call, bit for bit, through either entry: sums are formed in an
+ * order fixed by the stream (runs of 8 groups in float, the runs in ascending order in double), never by atomics in floating point; the symbols of a group
+ * that a call leaves open are carried on the device.  dvbt_sounder_read synchronises and does not disturb the accumulation; pdp takes M doubles and resp Kp
+ * (cap_*: what the caller's arrays hold; either may be NULL).  dvbt_sounder_push_device takes four device pointers and only enqueues on `stream`; calls on
+ * different streams are ordered by the handle (an event).  nsym <= 2^24 per call, 2^56 per stream; rows 8-byte aligned.  One thread per handle.  Every
+ * parameter is checked before the device is asked for: a bad struct or pointer is DVBT_ERR_INVALID everywhere, a good one DVBT_ERR_NO_DEVICE without a GPU --
+ * there is no CPU path.  A refused call leaves the stream where it was. */
+typedef struct { int device, transmission_mode, window, first_index; } dvbt_sounder_params;
+typedef struct {
+  long long symbols_pushed, groups_used, groups_skipped;
+  int M, Kp;
+} dvbt_sounder_result;
+typedef struct dvbt_sounder dvbt_sounder;
+int  dvbt_sounder_create(const dvbt_sounder_params *p, dvbt_sounder **out);
+int  dvbt_sounder_push(dvbt_sounder *h, const void *rows_host, const int *idx_host, const int *off_host, const int *cps_host, size_t nsym);
+int  dvbt_sounder_push_device(dvbt_sounder *h, const void *rows_dev, const int *idx_dev, const int *off_dev, const int *cps_dev, size_t nsym, void *stream);
+int  dvbt_sounder_read(dvbt_sounder *h, dvbt_sounder_result *result, double *pdp /* M, may be NULL */, size_t cap_pdp,
+                       double *resp /* Kp, may be NULL */, size_t cap_resp);
+int  dvbt_sounder_reset(dvbt_sounder *h);   /* back to the state after create */
+void dvbt_sounder_destroy(dvbt_sounder *h);
+
 #ifdef __cplusplus
 }
 #endif
