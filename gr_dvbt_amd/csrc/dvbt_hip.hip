@@ -420,12 +420,12 @@ struct dvbt_rx {
   DevMem<AcqState> acq_carry; bool use_carry = false;     // peak-detector state carried into a restart after a lost lock   // front-of-chain resample + scale (next row 2): its output buffer
   DevMem<float2> g_init; DevMem<float> l_init; DevMem<float2> g_trk; DevMem<float> l_trk;
   SymMeta *meta = nullptr; RxState *st = nullptr, *st_host = nullptr; DevMem<TpsState> tps_state;
-  // two acquisition contexts (state block + per-symbol tracker results): `st` / `meta` point at the one in use.  The lock-period walk searches on in the
-  // other one, so that what the last decoded period left behind stays valid for the byte de-interleaver, the report and the taps (segment_periods)
-  // (NCTX = 3: segment_periods uses two; the streaming entry's walk keeps a found period, decodes the one before it and searches for the next one at once)
+  // acquisition contexts (state block + per-symbol tracker results): `st` / `meta` point at the one in use.  NCTX = 3: the lock-period walk (walk_window) keeps
+  // a found period in one, decodes the period before it in the second and searches for the next one in the third at once; what the last decoded period left
+  // behind stays valid for the byte de-interleaver, the report and the taps (segment_periods switches back to it)
   DevMem<RxState> st_ctx[NCTX]; DevMem<SymMeta> meta_ctx[NCTX]; int ctx = 0;
-  // ... and what else an acquisition of one period and the decode of the period before it would share if they ran at the same time -- which they do (segment_periods:
-  // the search for period p + 1 on the caller's stream, the decode of period p on aux_stream): the trackers' flag words, the symbol kernel's ticket, the drift
+  // ... and what else an acquisition of one period and the decode of an earlier one would share if they ran at the same time -- which they do (walk_window:
+  // the search for period p + 1 on the caller's stream, the decode of period p - 1 on aux_stream): the trackers' flag words, the symbol kernel's ticket, the drift
   // model's verdict, the page-locked copy of the state block.  trk_flags / sym_ticket / drift.flags / st_host point at the context in use (set_ctx)
   DevMem<int> trk_flags_ctx[NCTX], sym_ticket_ctx[NCTX], drift_flags_ctx[NCTX];
   DevMem<int> trk_cp_a, trk_cp_b; int *trk_flags = nullptr; DevMem<float> trk_eps; DevMem<TpsEdge> tps_edges;
@@ -447,10 +447,10 @@ struct dvbt_rx {
   double acc_ms[ST_COUNT] = {0}; long n_timed = 0; bool ev_recorded = false;
   dvbt_rx_report last; bool have_last = false;
   dvbt_rx_cut cut = {0, 0, 0};
-  DevMem<float2> tps_prev, tps_prev_snap[2]; DevMem<TpsState> tps_snap[2]; DevMem<DescrRun> descr_runs; DevMem<int> descr_nruns;
+  DevMem<float2> tps_prev, tps_prev_snap; DevMem<TpsState> tps_snap;   // (the snapshots: what the streaming walk rolls back to when a head is not established)
+  DevMem<DescrRun> descr_runs; DevMem<int> descr_nruns;
   int descr_runs_cap = 0;                   // runs descr_runs holds: one per descrambler call of a stream of vit_cap bytes (descr_runs_for), DESCR_MAX_RUNS at the least
-  int n_periods = 1; size_t seg_offset = 0;
-  std::vector<dvbt_lock_period> periods;    // phase A of the last synchronous run
+  std::vector<dvbt_lock_period> periods;    // the lock periods of the last walk (walk_window): dvbt_rx_lock_periods
   DriftBufs drift = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; DevMem<double> drift_mem; DevMem<float> drift_delta;   // k_drift.hpp: drift's pointers are views into these two (flags: into drift_flags_ctx)
   struct GraphEntry { const void *iq; size_t n; hipStream_t s; long long sym_off; int delay, phase; hipGraphExec_t exec; };
   std::vector<GraphEntry> graphs;           // launch_graph: the captured launch sequences (a handful: a receiver's ring of segments)
@@ -525,7 +525,7 @@ extern "C" int dvbt_rx_create(const dvbt_rx_params *p, dvbt_rx **out)
   h->trk_flags = h->trk_flags_ctx[0];
   HIPCHK(h->aux_stream.create()); HIPCHK(h->aux_ev.create(hipEventDisableTiming));
   HIPCHK(h->tps_prev.alloc(d.n_tps)); HIPCHK(hipMemset(h->tps_prev, 0, sizeof(float2) * d.n_tps));
-  for (int i = 0; i < 2; i++) { HIPCHK(h->tps_prev_snap[i].alloc(d.n_tps)); HIPCHK(h->tps_snap[i].alloc(1)); }
+  HIPCHK(h->tps_prev_snap.alloc(d.n_tps)); HIPCHK(h->tps_snap.alloc(1));
   HIPCHK(h->descr_nruns.alloc(1));
   HIPCHK(h->centre.alloc(C + 1)); HIPCHK(h->anchor_pos.alloc(C / ACQ_ANCHOR + 4));
   HIPCHK(h->tps_edges.alloc(C / TPS_SEG + 2));
@@ -644,12 +644,13 @@ static int ensure_taps(dvbt_rx *h)
   if (!h->deint_tap) HIPCHK(h->deint_tap.alloc(h->vit_cap));
   return DVBT_OK;
 }
+static size_t bd_log_bytes(const dvbt_rx *h) { return (size_t)h->max_calls * h->d.payload + 64; }   // the per-period decoder-input log: every symbol a segment can hold
 extern "C" int dvbt_rx_enable_taps(dvbt_rx *h, int enable)
 {
   if (!h) return DVBT_ERR_INVALID;
   if (h->pending) return fail(DVBT_ERR_STATE, "dvbt_rx_enable_taps: a segment is in flight (dvbt_rx_segment_finish first)");
   drop_graphs(h);
-  if (enable == 2 && !h->bd_log) HIPCHK(h->bd_log.alloc((size_t)h->max_calls * h->d.payload + 64));
+  if (enable == 2 && !h->bd_log) HIPCHK(h->bd_log.alloc(bd_log_bytes(h)));
   if (enable) return ensure_taps(h);
   h->bd_log.reset();
   // in soft-decision mode eq is not a debug tap but the soft demapper's input (allocated at create; it also selects the symbol kernel's instantiation that writes eq and csi)
@@ -952,7 +953,6 @@ extern "C" int dvbt_rx_segment_enqueue_device(dvbt_rx *h, const void *iq_device,
   hipStream_t s = stream ? (hipStream_t)stream : h->own_stream;
   const float2 *chain; size_t chain_n;
   int r = prepare_chain(h, (const float2 *)iq_device, nsamples, s, &chain, &chain_n); if (r) return r;
-  h->n_periods = 1; h->seg_offset = 0;
   if (h->prm.launch_graph && !h->timing && !h->rsd.ri && !(h->acq_tap || h->fft_out || h->symdeint_tap || h->deint_tap)) {   // (not with the debug taps: a replay would write buffers that dvbt_rx_enable_taps(h, 0) frees)
     // the launch sequence as ONE graph launch: captured the first time this (segment, length, stream, cut) is seen
     for (auto &ge : h->graphs)
@@ -1024,13 +1024,6 @@ extern "C" int dvbt_rx_segment_finish(dvbt_rx *h, dvbt_rx_report *rep)
   return DVBT_OK;
 }
 
-// The synchronous entries follow the reference through every loss of the CP lock inside the segment (ofdm_sym_acquisition_impl.cc:545-559;
-// oracle/o_chain.c restates the downstream consequences).  Phase A walks the segment with ofdm_sym_acquisition alone: where each lock period
-// starts, how many symbols it holds, where the search resumes (half a window behind a lost lock; one window after each call that found
-// nothing), d_avg carried along.  Phase B runs the chain over every period that acquired symbols, in order: TPS state carried, the period's last
-// item kept when a later period follows, every period's Viterbi stream appended to the segment's at a multiple of two de-interleaver items.
-// Then the byte de-interleaver, RS and the descrambler run once over the whole stream.
-struct LockPeriod { size_t off; int n_symbols; float avg_in; bool carry; int call0, cp_start0; bool lost; };
 static void set_ctx(dvbt_rx *h, int k)
 {
   if (k != h->ctx && !h->graphs.empty()) drop_graphs(h);
@@ -1038,263 +1031,23 @@ static void set_ctx(dvbt_rx *h, int k)
   h->st_host = h->st_host_ctx[k];
 }
 
-static int segment_periods(dvbt_rx *h, const float2 *chain, size_t chain_n, hipStream_t s, dvbt_rx_report *rep)
-{
-  const Dims &d = h->d;
-  const size_t L = (size_t)(d.N + d.cp), win = (size_t)(2 * d.N + d.cp + 16);
-  std::vector<LockPeriod> per;
-  h->plog.clear(); h->plog_bytes = 0;
-  bool capped = false;                                            // the walk was cut short: the rest of the segment is not decoded (status bit 8)
-  h->periods.clear();
-  // what the decode of the periods accumulates
-  struct Book {
-    size_t acc = 0; int delivering = 0, processed = 0; bool any = false; dvbt_rx_report first_rep; RxState last_st; int total_symbols = 0; size_t last_off = 0;
-  } bk, snap[2];
-  memset(&bk.first_rep, 0, sizeof bk.first_rep); bk.first_rep.first_out_symbol = -1;
-  memset(&bk.last_st, 0, sizeof bk.last_st); bk.last_st.first_out = -1; bk.last_st.status = 1;
-  bool snap_assumed[2] = {false, false};                          // ... and were decoded on the assumption that a later period has items
-  bool need_full = false;
-  int ctx_last = -1;                                              // acquisition context of the last decoded period (-1: none yet): acquisitions go to the other one
-  auto acq_ctx = [&]() -> int {                                   // switch to the context an acquisition may write (the other one may be in use by a decode in flight;
-    const int k = ctx_last < 0 ? h->ctx : (ctx_last == 0 ? 1 : 0);   // what has to live through the periods of a segment -- the stream's TPS word -- is kept on the host)
-                                                                  // (three contexts exist, the streaming entry's walk uses all of them: never ctx_last ^ 1, which is 3 for 2)
-    if (k != h->ctx) set_ctx(h, k);
-    return DVBT_OK;
-  };
-  // The decode of period p runs on the handle's second stream WHILE the caller's stream searches for period p + 1 (the search needs the samples and the average
-  // the lost call left, nothing of the decode): a period costs the longer of the two instead of their sum.  The decode's outcome (its Viterbi byte count: where
-  // the next period's bytes go; whether it delivered) is read before the NEXT decode is launched.
-  hipStream_t s2 = h->aux_stream;
-  HIPCHK(hipEventRecord(h->aux_ev, s)); HIPCHK(hipStreamWaitEvent(s2, h->aux_ev, 0));   // (whatever made the samples ready on the caller's stream)
-  struct Pend { bool on = false; size_t p = 0, vit_off = 0; int ctx = 0; hipStream_t st = nullptr; } pend;
-  unsigned long long tps_keep = 0;
-  int snap_period[2] = {-1, -1}, sn = 0;                          // the last two decoded periods: snap[] and the device-side copies of the pilot engine's state were taken in front of
-                                                                  // them (snap[sn]: the last one, snap[sn ^ 1]: the one before)
-  // one period through the chain up to the Viterbi decoder.  later: a later period delivers items (the last item of this one leaves the demodulator too);
-  // reuse: the acquisition results of the acq_only run just before are still in the handle (the period is decoded right behind its discovery)
-  auto decode_finish = [&]() -> int {
-    if (!pend.on) return DVBT_OK;
-    HIPCHK(hipStreamSynchronize(pend.st));
-    pend.on = false; h->pending = false;
-    const size_t p = pend.p;
-    const RxState &st = *h->st_host_ctx[pend.ctx];
-    if (st.tps_bits) tps_keep = st.tps_bits;
-    bk.processed++; bk.any = true; bk.last_st = st; bk.last_off = per[p].off;
-    h->periods[p].first_out_symbol = 0;
-    if (h->bd_log) {   // the period's decoder input, at a place that depends on the period alone (a period may be decoded twice: the entry is overwritten)
-      size_t base = 0; for (size_t q = 0; q < p; q++) base += (size_t)std::max(per[q].n_symbols, 0);
-      if (h->plog.size() <= p) h->plog.resize(p + 1, dvbt_period_tap{0, 0, 0, 0});
-      dvbt_period_tap e = {(int64_t)(base * d.payload), 0, (int64_t)pend.vit_off, 0};
-      if (st.first_out >= 0 && st.n_out_symbols > 0) {
-        e.bitdeint_bytes = (int64_t)st.n_out_symbols * d.payload; e.viterbi_bytes = st.n_vit_bytes;
-        HIPCHK(hipMemcpy(h->bd_log + e.bitdeint_offset, (h->prm.hier_stream && h->bitdeint_lp) ? h->bitdeint_lp : h->bitdeint, (size_t)e.bitdeint_bytes, hipMemcpyDeviceToDevice));
-        h->plog_bytes = std::max(h->plog_bytes, (size_t)(e.bitdeint_offset + e.bitdeint_bytes));
-      }
-      h->plog[p] = e;
-    }
-    if (st.first_out >= 0) {
-      h->periods[p].first_out_symbol = st.first_out + 1;
-      if (bk.delivering == 0) { fill_report(h, st, bk.first_rep); bk.first_rep.segment_offset = (int64_t)per[p].off; }
-      bk.acc = pend.vit_off + (size_t)st.n_vit_bytes; bk.delivering++;
-    }
-    return DVBT_OK;
-  };
-  auto decode_launch = [&](size_t p, bool later, bool reuse, hipStream_t ds) -> int {
-    const int usable = per[p].n_symbols - (later ? 0 : 1);       // items that leave the demodulator
-    bk.total_symbols += per[p].n_symbols;
-    if (usable < 1) return DVBT_OK;
-    if (!reuse) { int r = acq_ctx(); if (r) return r; }
-    EnqOpt o; o.use_carry = per[p].carry; o.carry_avg = per[p].avg_in; o.hist = (long long)per[p].off; o.avail = (long long)(chain_n - per[p].off); o.continuation = bk.processed > 0; o.keep_last = later; o.tail = false; o.skip_acq = reuse;
-    o.vit_off = bk.delivering > 0 ? (bk.acc / 3264) * 3264 : 0;   // convolutional_deinterleaver_impl.cc:109-120: the tag realigns the input
-    o.init_tries = std::min(ACQ_INIT_TRIES_MAX, std::max(ACQ_INIT_TRIES, per[p].call0 + 1));   // (a second acquisition must reach the window the wide search found the peak in)
-    // a period that ends in a lost lock is decoded over its own calls and the one that lost the lock, not over the whole rest of the segment
-    size_t span = chain_n - per[p].off;
-    if (per[p].lost) span = std::min(span, win + (size_t)(per[p].call0 + per[p].n_symbols) * L);
-    int r = enqueue(h, chain + per[p].off, span, ds, o); if (r) return r;
-    // the TPS carriers of the last demodulated symbol are the DBPSK reference of the next period's first one
-    HIPCHK(hipMemcpyAsync(h->tps_prev, h->tpsval + (size_t)(usable - 1) * d.n_tps, sizeof(float2) * d.n_tps, hipMemcpyDeviceToDevice, ds));
-    pend.on = true; pend.p = p; pend.vit_off = o.vit_off; pend.ctx = h->ctx; pend.st = ds;
-    ctx_last = h->ctx;
-    return DVBT_OK;
-  };
-  auto decode = [&](size_t p, bool later, bool reuse) -> int {     // the synchronous form (periods decoded again behind the walk)
-    int r = decode_finish(); if (r) return r;
-    r = decode_launch(p, later, reuse, s); if (r) return r;
-    return decode_finish();
-  };
-  {   // ---- the walk: find a period (acquisition alone over a growing window), decode it, go on behind the call that lost the lock
-    size_t off = 0; bool carry = false; float avg = 0.f; int fails = 0, guard = 0;
-    EnqOpt so; size_t slook = 0;                                   // the search in flight on the caller's stream
-    // the search for the next period is ENQUEUED before the host turns to the launches of the last period's decode: the device looks for period p + 1 while
-    // the host is busy with the ~15 launches of period p's decode and while that decode runs
-    auto launch_search = [&]() -> int {
-      { int r = acq_ctx(); if (r) return r; }
-      so = EnqOpt(); so.acq_only = true; so.use_carry = carry; so.carry_avg = avg; so.hist = (long long)off; so.avail = (long long)(chain_n - off);
-      // searches that found nothing are followed by wider ones (4, 8, ... 64 windows per launch): dead air costs a launch sequence per 64 windows, not per 4
-      so.init_tries = std::min(ACQ_INIT_TRIES_MAX, ACQ_INIT_TRIES << std::min(fails, 4));
-      // the search and the tracker look at a window of the rest of the segment that grows while the lock holds to its end: a segment with many lock
-      // periods costs its length a few times over, not its length times the number of periods (a call's outcome depends on the samples before it only)
-      // (first window: 768 calls, or four times the previous period's length when the lock is being lost every few dozen symbols -- the metric, anchor and
-      // tracker launches cost in proportion to the window)
-      size_t look_calls = 767;
-      if (!per.empty()) look_calls = std::min<size_t>(767, std::max<size_t>(47, 4 * (size_t)std::max(per.back().n_symbols, 0)));
-      slook = std::min(chain_n - off, win + look_calls * L);
-      // the first attempts take the whole rest of the segment: a lock that holds to its end (the usual case, possibly behind a start-up transient of a
-      // few symbols) is one pass; only a stream that keeps losing the lock goes over to the short windows
-      if (per.size() < 3 && guard < 8) slook = chain_n - off;
-      return enqueue(h, chain + off, slook, s, so);
-    };
-    auto complete_search = [&]() -> int {
-      for (;;) {
-        HIPCHK(hipStreamSynchronize(s));
-        if (!(h->st_host->status & 1) && h->st_host->small_viol && !so.no_small) { so.no_small = true; }   // outside acq_small_kernel's closed form: the general kernels
-        else if ((h->st_host->status & 3) || slook >= chain_n - off) return DVBT_OK;
-        else slook = std::min(chain_n - off, win + 4 * (slook - win) + 3 * L);
-        int r = enqueue(h, chain + off, slook, s, so); if (r) return r;
-      }
-    };
-    bool searching = off + win <= chain_n;
-    if (searching) { int r = launch_search(); if (r) return r; }
-    while (searching) {
-      if (guard++ >= 4096) { capped = true; HIPCHK(hipStreamSynchronize(s)); break; }
-      { int r = complete_search(); if (r) return r; }
-      const RxState st = *h->st_host;
-      const int tries = (int)std::min<size_t>((size_t)so.init_tries, (slook - win) / L + 1);      // what enqueue() examined
-      if (st.status & 1) {                                       // no peak in these windows: the reference consumes them one by one and searches on
-        off += (size_t)tries * L; avg = st.avg; carry = true; fails++;
-        searching = off + win <= chain_n;
-        if (searching) { int r = launch_search(); if (r) return r; }   // (the same context again: ctx_last has not moved)
-        continue;
-      }
-      fails = 0;
-      const int ctx_found = h->ctx;                               // the period's acquisition results live here until its decode has run
-      { int r = decode_finish(); if (r) return r; }               // the decode of the period before has had this search's time
-      // a period with items behind one that was decoded as the last one (the guess near the segment's end, below): everything is decoded again in order
-      if (st.n_symbols >= 1 && snap_period[sn] >= 0 && !snap_assumed[sn]) need_full = true;
-      const bool lost = (st.status & 2) != 0;
-      per.push_back(LockPeriod{off, st.n_symbols, avg, carry, st.call0, st.cp_start0, lost});
-      h->periods.push_back(dvbt_lock_period{(int64_t)off, st.call0, st.cp_start0, st.n_symbols, 0});
-      // Decoded at once, on the acquisition results that are still in the handle.  Whether the period's last item leaves the demodulator depends on a
-      // LATER period having items: a period that ends in a lost lock is decoded as if one did (corrected behind the walk if none does); a lock that
-      // holds to the segment's end -- or is lost only where the samples run out -- makes the last period.
-      // a lock that is lost where the samples run out (no room for another window behind it) ends the walk like one that holds to the end
-      const size_t behind = off + (size_t)(st.call0 + st.n_symbols) * L + L / 2;
-      const bool final_period = !lost || behind + win > chain_n;
-      // ... and with less than 16 symbols left behind the first or second loss of a segment a later period with items is the less likely outcome (a stream
-      // that simply ends; where the lock is being lost all the time, another short period is the likely one)
-      const bool later_guess = !final_period && !(per.size() <= 2 && behind + win + 16 * L > chain_n);
-      const size_t pidx = per.size() - 1;
-      // the next search starts now, in the other context (free: the decode that used it has just been read back)
-      searching = !final_period && per.size() < 1024;
-      if (!final_period && per.size() >= 1024) capped = true;
-      const bool will_decode = st.n_symbols - (later_guess ? 0 : 1) >= 1;
-      if (searching) {
-        off = behind; avg = st.avg_lost; carry = true;
-        // a period that is going to be decoded keeps its context: the search takes the other one (that of the period decoded before: its decode has been read
-        // back, the new period's takes its place as the last one).  A period that launches no decode leaves everything as it is
-        const int keep = ctx_last; if (will_decode) ctx_last = ctx_found;
-        int r = launch_search(); if (r) return r;
-        ctx_last = keep;
-      }
-      const int ctx_search = h->ctx;
-      set_ctx(h, ctx_found);
-      if (will_decode) {                                         // keep the state in front of it
-        sn ^= 1; snap[sn] = bk; snap_period[sn] = (int)pidx; snap_assumed[sn] = later_guess;
-        HIPCHK(hipMemcpyAsync(h->tps_snap[sn], h->tps_state, sizeof(TpsState), hipMemcpyDeviceToDevice, s2));
-        HIPCHK(hipMemcpyAsync(h->tps_prev_snap[sn], h->tps_prev, sizeof(float2) * d.n_tps, hipMemcpyDeviceToDevice, s2));
-      }
-      { int r = decode_launch(pidx, later_guess, true, s2); if (r) return r; }   // ... and runs while that search does
-      set_ctx(h, ctx_search);
-    }
-    { int r = decode_finish(); if (r) return r; }
-    int last_items = -1;                                          // the last period that has items at all
-    for (size_t q = 0; q < per.size(); q++) if (per[q].n_symbols >= 1) last_items = (int)q;
-    // The byte de-interleaver, the RS decoder and the report read the device-side state of the LAST decoded period, and that period's last item depends on
-    // whether a later one has items.  Both are in order when the last period's lock held to the segment's end (the common case: its decode was the last
-    // launch, or the lock was lost where the samples run out).  Behind a last decoded period that ended in a lost lock, searches have followed: they ran in
-    // the other acquisition context (acq_ctx), so its state block and tracker results are intact and the handle just switches back to them.  Only when
-    // the guess about a later period with items was wrong is the period decoded again from the state kept in front of it, acquisition included.  Should
-    // that leave nothing to decode (a single item, not delivered after all), the period decoded before it is decoded again instead (the state in front of
-    // the last TWO is kept; its context has been overwritten by the searches behind the last one).
-    auto again = [&](int k) -> int {                              // period snap_period[k] once more, from the state in front of it, acquisition included
-      const size_t z = (size_t)snap_period[k];
-      bk = snap[k];
-      HIPCHK(hipMemcpyAsync(h->tps_state, h->tps_snap[k], sizeof(TpsState), hipMemcpyDeviceToDevice, s));
-      HIPCHK(hipMemcpyAsync(h->tps_prev, h->tps_prev_snap[k], sizeof(float2) * d.n_tps, hipMemcpyDeviceToDevice, s));
-      h->periods[z].first_out_symbol = 0;
-      int r = decode(z, last_items > (int)z, false); if (r) return r;
-      for (size_t q = z + 1; q < per.size(); q++) bk.total_symbols += per[q].n_symbols;
-      return DVBT_OK;
-    };
-    auto full = [&]() -> int {                                    // every period again in order, each with its own acquisition and the true `later`
-      bk = Book(); memset(&bk.first_rep, 0, sizeof bk.first_rep); bk.first_rep.first_out_symbol = -1;
-      memset(&bk.last_st, 0, sizeof bk.last_st); bk.last_st.first_out = -1; bk.last_st.status = 1;
-      for (size_t q = 0; q < per.size(); q++) { h->periods[q].first_out_symbol = 0; int rr = decode(q, last_items > (int)q, false); if (rr) return rr; }
-      return DVBT_OK;
-    };
-    const bool guess_ok = snap_period[sn] < 0 || snap_assumed[sn] == (last_items > snap_period[sn]);
-    if (need_full) { ctx_last = -1; int r = full(); if (r) return r; }
-    else if (snap_period[sn] >= 0 && !guess_ok) {
-      ctx_last = -1;                                               // nothing to protect: the period is decoded again
-      const int before = snap[sn].processed;
-      { int r = again(sn); if (r) return r; }
-      if (bk.processed == before && before > 0) {
-        // the last period's single item is not delivered after all: the period decoded before it is the last one, and its device-side state is stale too
-        if (snap_period[sn ^ 1] >= 0) { int r = again(sn ^ 1); if (r) return r; }
-        else { int r = full(); if (r) return r; }                // (cannot happen: `before` > 0 means an earlier period was decoded)
-      }
-    }
-  }
-  if (ctx_last >= 0 && ctx_last != h->ctx) set_ctx(h, ctx_last);   // the searches behind the last decoded period ran in the other context
-  size_t acc = bk.acc; const int delivering = bk.delivering, processed = bk.processed; const bool any = bk.any;
-  const dvbt_rx_report first_rep = bk.first_rep; const RxState last_st = bk.last_st; const int total_symbols = bk.total_symbols; const size_t last_off = bk.last_off;
-  dvbt_rx_report r;
-  if (!any) {   // nothing was acquired (or single symbols only): report the last acquisition attempt
-    RxState st = *h->st_host; st.first_out = -1; st.n_out_symbols = 0; st.n_vit_bytes = 0; st.n_rs_items = 0; st.n_rs_words = 0; st.n_ts_bytes = 0;
-    st.rs_fail = st.rs_corr = 0; st.tps_bits = 0; st.ts_first_packet = 0; st.stream_rs_items = 0; st.status |= 4;
-    fill_report(h, st, r);
-    if (capped) r.status |= 256;
-    h->n_periods = 0; h->seg_offset = 0;
-    h->last = r; h->have_last = true; h->seg_serial++; if (rep) *rep = r;
-    return DVBT_OK;
-  }
-  if (delivering <= 1 && processed == 1 && per.size() >= 1 && acc == (size_t)last_st.n_vit_bytes) {
-    // one period: the device-side plan of that period is already the segment's (cut-stream roundings included)
-    int rr = enqueue_tail(h, s, (long long)(acc / 204 + 1), -1); if (rr) return rr;
-  } else {
-    int rr = enqueue_tail(h, s, (long long)(acc / 204 + 1), (long long)(acc / 204)); if (rr) return rr;
-  }
-  HIPCHK(hipMemcpyAsync(h->st_host, h->st, sizeof(RxState), hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
-  RxState fin = *h->st_host;
-  if (!fin.tps_bits) fin.tps_bits = tps_keep;                     // (the stream's TPS word: a period that saw no whole frame does not take it away)
-  if (delivering > 1 || processed > 1) fin.n_vit_bytes = (long long)acc;
-  fill_report(h, fin, r);
-  // the front-end fields describe the LAST processed period (the debug taps hold it); the stream fields the whole segment
-  r.segment_offset = (int64_t)last_off;
-  if (r.resume_sample) r.resume_sample += (int64_t)last_off;
-  r.n_lock_periods = delivering; r.total_symbols = total_symbols;
-  if (capped) r.status |= 256;
-  if (h->cut.stream_symbol_offset != 0 && (delivering > 1 || processed > 1)) r.status |= 128;   // a cut piece that lost the lock: laid out from its own start, not in the stream's coordinates
-  if (delivering == 0) { r.first_out_symbol = -1; r.status |= 4; }
-  h->n_periods = delivering; h->seg_offset = last_off;
-  h->last = r; h->have_last = true; h->seg_serial++;
-  if (rep) *rep = r;
-  return DVBT_OK;
-}
-
-// ---- one WINDOW of a walk (the streaming entry, dvbt_stream.inc): the lock-period walk of segment_periods over a stretch of a stream that goes on behind it,
-// with what the reference's blocks hold between two work() calls carried in and out.  Two phases: A finds the window's lock periods with the acquisition alone
-// (as segment_periods does), B decodes them in order up to the Viterbi decoder, every one with its own acquisition and with the TRUE answer to "does a later
-// period deliver an item" (the period's last item leaves the demodulator only then, demod_reference_signals_impl.cc:88-94) -- no guess, nothing decoded twice.
+// ---- the lock-period walk: the reference followed through every loss of the CP lock (ofdm_sym_acquisition_impl.cc:545-559; oracle/o_chain.c restates the
+// downstream consequences).  ONE implementation: the synchronous entries walk a whole segment with it (segment_periods, below), the streaming entry one WINDOW
+// of a stream that goes on behind it (dvbt_stream.inc), with what the reference's blocks hold between two work() calls carried in and out.
+// The lock periods are found with ofdm_sym_acquisition alone: where each one starts, how many symbols it holds, where the search resumes (half a window behind
+// a lost lock; one window after each call that found nothing), d_avg carried along.  Every period that has items is decoded up to the Viterbi decoder, in order,
+// from the acquisition results its search left: TPS state carried, its Viterbi stream appended to the walk's at a multiple of two de-interleaver items, and with
+// the TRUE answer to "does a later period deliver an item" (the period's last item leaves the demodulator only then, demod_reference_signals_impl.cc:88-94) --
+// the decode stays one period behind the search, so nothing is guessed and nothing decoded twice.
 // partial: the stream goes on.  The last period that has items is not final then (its end, and whether its last item is delivered, lie in samples to come): it is
 // left to the next window, which starts its search where that period's search started, with that search's carried average.  The exception is an OPEN period (the
 // lock holds to the window's end) whose superframe start lies at least `establish_calls` calls before the window's last call: it is decoded and kept -- the stream
 // goes over to pieces from it (the head of an epoch).
-// A8, A9 and the descrambler are the caller's (walk flush): the window only appends to the handle's Viterbi stream.
+// A8, A9 and the descrambler are the caller's (segment_periods; walk flush): the walk only appends to the handle's Viterbi stream.
 struct WalkPeriod {
   size_t off = 0; int n_symbols = 0, call0 = 0, cp_start0 = 0; float avg_in = 0.f; bool carry = false, lost = false;
   size_t behind = 0; float avg_lost = 0.f;                           // where the reference searches on after this period, and with which average
+  int ctx = 0;                                                       // the acquisition context its search ran in (and its decode, if any)
   bool decoded = false; int first_out = -1; int n_out_symbols = 0; size_t vit_off = 0; long long n_vit_bytes = 0;
 };
 struct WalkIO {
@@ -1307,12 +1060,15 @@ struct WalkIO {
   size_t acc = 0; int delivering = 0;                                // the walk's Viterbi stream so far (bytes in h->vit), periods that delivered so far
   bool cut = false; long long cut_sym_off = 0; int cut_delay = 0; size_t vit_pad = 0;   // the first decoded period continues a cut stream; its bytes go to h->vit + vit_pad
   long long establish_calls = 0;
+  bool cut_handle = false;                                           // a cut piece walked on its own: the handle's cut (dvbt_rx_set_cut) holds for every period
+  int max_periods = 4096, max_searches = 8192;                       // the walk gives up behind that many (status bit 8)
   // out
   std::vector<WalkPeriod> per;
   size_t next_off = 0; bool next_carry = false; float next_avg = 0.f;   // partial, not established: the next window's search starts here (offset in this window)
-  bool established = false; int head = -1; RxState head_st; long long head_ncalls = 0;   // calls of the head's grid that the window holds
+  bool established = false; int head = -1; RxState head_st; long long head_ncalls = 0;   // (head_st: the state block of the period decoded last) calls of the head's grid that the window holds
   bool any_decoded = false; int status_or = 0;
   int total_symbols = 0;
+  unsigned long long tps_keep = 0;                                   // the stream's TPS word: the last one a decoded period of this walk saw whole
 };
 
 static int walk_window(dvbt_rx *h, const float2 *chain, size_t chain_n, hipStream_t s, WalkIO &io)
@@ -1322,7 +1078,7 @@ static int walk_window(dvbt_rx *h, const float2 *chain, size_t chain_n, hipStrea
   const size_t maxn = h->chain_max;                                  // what one launch sequence of the handle can take: a longer window is looked at through this much
   std::vector<WalkPeriod> &per = io.per;
   per.clear(); h->periods.clear();
-  io.established = false; io.head = -1; io.any_decoded = false; io.status_or = 0; io.total_symbols = 0;
+  io.established = false; io.head = -1; io.any_decoded = false; io.status_or = 0; io.total_symbols = 0; io.tps_keep = 0;
   // One pass, three acquisition contexts: the period found last that has items is KEPT undecoded (whether its last item leaves the demodulator depends on a later
   // period having items, demod_reference_signals_impl.cc:88-94) -- when the next one with items is found, the kept one is decoded (later = true, on the acquisition
   // results that are still in its context, on the handle's second stream) while the caller's stream already searches for the one after: a period costs the longer
@@ -1331,8 +1087,7 @@ static int walk_window(dvbt_rx *h, const float2 *chain, size_t chain_n, hipStrea
   HIPCHK(hipEventRecord(h->aux_ev, s)); HIPCHK(hipStreamWaitEvent(s2, h->aux_ev, 0));
   size_t acc = io.acc; int delivering = io.delivering; bool processed = io.continuation; bool cut_pending = io.cut;
   struct Pend { bool on = false; size_t p = 0, vit_off = 0; int ctx = 0; hipStream_t st = nullptr; } pend;
-  std::vector<int> pctx;                                             // context of every period's acquisition
-  int kept = -1;                                                     // the period that waits for its successor
+  int kept = -1;                                                    // the period that waits for its successor
   auto decode_finish = [&]() -> int {
     if (!pend.on) return DVBT_OK;
     HIPCHK(hipStreamSynchronize(pend.st));
@@ -1346,6 +1101,22 @@ static int walk_window(dvbt_rx *h, const float2 *chain, size_t chain_n, hipStrea
     h->periods[pend.p].first_out_symbol = st.first_out >= 0 ? st.first_out + 1 : 0;
     if (st.first_out >= 0) { acc = pend.vit_off + (size_t)st.n_vit_bytes; delivering++; }
     io.head_st = st;
+    if (st.tps_bits) io.tps_keep = st.tps_bits;
+    // dvbt_rx_enable_taps(h, 2): the period's decoder input, at a place that depends on the periods before it alone.  The log is the SEGMENT entry's: segment_periods
+    // clears plog before the walk, the offsets count from the walk's first period and the copy blocks the host.  A stream handle has no such log (no window-to-window
+    // meaning is defined for it): whoever gives it one has to decide what the offsets are relative to, and who clears it.
+    if (h->bd_log) {
+      size_t base = 0; for (size_t q = 0; q < pend.p; q++) base += (size_t)std::max(per[q].n_symbols, 0);
+      if (h->plog.size() <= pend.p) h->plog.resize(pend.p + 1, dvbt_period_tap{0, 0, 0, 0});
+      dvbt_period_tap e = {(int64_t)(base * d.payload), 0, (int64_t)pend.vit_off, 0};
+      if (st.first_out >= 0 && st.n_out_symbols > 0) {
+        e.bitdeint_bytes = (int64_t)st.n_out_symbols * d.payload; e.viterbi_bytes = st.n_vit_bytes;
+        if ((size_t)(e.bitdeint_offset + e.bitdeint_bytes) > bd_log_bytes(h)) return fail(DVBT_ERR_CAPACITY, "decoder-input log too small for the segment's lock periods");
+        HIPCHK(hipMemcpy(h->bd_log + e.bitdeint_offset, (h->prm.hier_stream && h->bitdeint_lp) ? h->bitdeint_lp : h->bitdeint, (size_t)e.bitdeint_bytes, hipMemcpyDeviceToDevice));
+        h->plog_bytes = std::max(h->plog_bytes, (size_t)(e.bitdeint_offset + e.bitdeint_bytes));
+      }
+      h->plog[pend.p] = e;
+    }
     return DVBT_OK;
   };
   // period p from the acquisition results in its context (the handle points at another one meanwhile: switched for the launches, switched back)
@@ -1355,11 +1126,11 @@ static int walk_window(dvbt_rx *h, const float2 *chain, size_t chain_n, hipStrea
     const int usable = w.n_symbols - (later ? 0 : 1);                // items that leave the demodulator
     if (usable < 1) return DVBT_OK;
     const int back = h->ctx;
-    set_ctx(h, pctx[p]);
+    set_ctx(h, w.ctx);
     EnqOpt o; o.use_carry = w.carry; o.carry_avg = w.avg_in; o.hist = io.hist + (long long)w.off; o.avail = (long long)(chain_n - w.off);
     o.continuation = processed; o.keep_last = later; o.tail = false; o.skip_acq = true;
     o.tps_init = !processed && io.tps_preset;
-    o.cut_set = true; o.sym_off = cut_pending ? io.cut_sym_off : 0; o.delay = cut_pending ? io.cut_delay : 0;
+    o.cut_set = !io.cut_handle; o.sym_off = cut_pending ? io.cut_sym_off : 0; o.delay = cut_pending ? io.cut_delay : 0;
     // convolutional_deinterleaver_impl.cc:109-120: the tag realigns the block's input to a pair of items (3264 bytes of the walk's stream: h->vit[0] is a multiple of
     // 3264 bytes into it, the caller sees to that with vit_pad and by compacting in such multiples)
     o.vit_off = delivering > 0 ? (acc / 3264) * 3264 : (cut_pending ? io.vit_pad : acc);
@@ -1369,11 +1140,11 @@ static int walk_window(dvbt_rx *h, const float2 *chain, size_t chain_n, hipStrea
     if (!r) { hipError_t e = hipMemcpyAsync(h->tps_prev, h->tpsval + (size_t)(usable - 1) * d.n_tps, sizeof(float2) * d.n_tps, hipMemcpyDeviceToDevice, ds); if (e != hipSuccess) r = fail(DVBT_ERR_HIP, "tps_prev copy"); }
     set_ctx(h, back);
     if (r) return r;
-    pend.on = true; pend.p = p; pend.vit_off = o.vit_off; pend.ctx = pctx[p]; pend.st = ds;
+    pend.on = true; pend.p = p; pend.vit_off = o.vit_off; pend.ctx = w.ctx; pend.st = ds;
     return DVBT_OK;
   };
   auto free_ctx = [&]() -> int {                                      // a context that neither the kept period nor the decode in flight lives in
-    for (int k = 0; k < dvbt_rx::NCTX; k++) if (!(kept >= 0 && pctx[(size_t)kept] == k) && !(pend.on && pend.ctx == k)) return k;
+    for (int k = 0; k < dvbt_rx::NCTX; k++) if (!(kept >= 0 && per[(size_t)kept].ctx == k) && !(pend.on && pend.ctx == k)) return k;
     return 0;
   };
   // ---- the walk
@@ -1382,11 +1153,16 @@ static int walk_window(dvbt_rx *h, const float2 *chain, size_t chain_n, hipStrea
   auto launch_search = [&]() -> int {
     set_ctx(h, free_ctx());
     so = EnqOpt(); so.acq_only = true; so.use_carry = carry; so.carry_avg = avg; so.hist = io.hist + (long long)off; so.avail = (long long)(chain_n - off);
+    // searches that found nothing are followed by wider ones (4, 8, ... 64 windows per launch): dead air costs a launch sequence per 64 windows, not per 4
     so.init_tries = std::min(ACQ_INIT_TRIES_MAX, ACQ_INIT_TRIES << std::min(fails, 4));
+    // the search and the tracker look at a window of the rest of the samples that grows while the lock holds to its end (complete_search): many lock periods
+    // cost the samples' length a few times over, not that length times the number of periods (a call's outcome depends on the samples before it only).
+    // First window: 768 calls, or four times the previous period's length when the lock is being lost every few dozen symbols
     size_t look_calls = 767;
     if (!per.empty()) look_calls = std::min<size_t>(767, std::max<size_t>(47, 4 * (size_t)std::max(per.back().n_symbols, 0)));
     srest = std::min(chain_n - off, maxn);
     slook = std::min(srest, win + look_calls * L);
+    // the first attempts take the whole rest: a lock that holds to the end (the usual case, possibly behind a start-up transient of a few symbols) is one pass
     if (per.size() < 3 && guard < 8) slook = srest;
     return enqueue(h, chain + off, slook, s, so);
   };
@@ -1402,11 +1178,11 @@ static int walk_window(dvbt_rx *h, const float2 *chain, size_t chain_n, hipStrea
   bool searching = off + win <= chain_n;
   if (searching) { int r = launch_search(); if (r) return r; }
   while (searching) {
-    if (guard++ >= 8192 || per.size() >= 4096) { io.status_or |= 256; HIPCHK(hipStreamSynchronize(s)); break; }
+    if (guard++ >= io.max_searches) { io.status_or |= 256; HIPCHK(hipStreamSynchronize(s)); break; }   // cut short: the rest of the samples is not decoded
     { int r = complete_search(); if (r) return r; }
     const RxState st = *h->st_host;
-    const int tries = (int)std::min<size_t>((size_t)so.init_tries, (slook - win) / L + 1);
-    if (st.status & 1) {
+    const int tries = (int)std::min<size_t>((size_t)so.init_tries, (slook - win) / L + 1);      // what enqueue() examined
+    if (st.status & 1) {                                               // no peak in these windows: the reference consumes them one by one and searches on
       off += (size_t)tries * L; avg = st.avg; carry = true; fails++;
       searching = off + win <= chain_n;
       if (searching) { int r = launch_search(); if (r) return r; }
@@ -1414,8 +1190,8 @@ static int walk_window(dvbt_rx *h, const float2 *chain, size_t chain_n, hipStrea
     }
     fails = 0;
     WalkPeriod p; p.off = off; p.n_symbols = st.n_symbols; p.call0 = st.call0; p.cp_start0 = st.cp_start0; p.avg_in = avg; p.carry = carry; p.lost = (st.status & 2) != 0;
-    p.behind = off + (size_t)(st.call0 + st.n_symbols) * L + L / 2; p.avg_lost = st.avg_lost;
-    per.push_back(p); pctx.push_back(h->ctx);
+    p.behind = off + (size_t)(st.call0 + st.n_symbols) * L + L / 2; p.avg_lost = st.avg_lost; p.ctx = h->ctx;
+    per.push_back(p);
     h->periods.push_back(dvbt_lock_period{(int64_t)off, st.call0, st.cp_start0, st.n_symbols, 0});
     io.total_symbols += st.n_symbols;
     if (!p.lost && srest < chain_n - off && !io.partial) io.status_or |= 256;   // (a final window longer than the handle's capacity: cannot happen with the stream's sizing)
@@ -1430,10 +1206,11 @@ static int walk_window(dvbt_rx *h, const float2 *chain, size_t chain_n, hipStrea
     else {
       off = p.behind; avg = p.avg_lost; carry = true;
       searching = off + win <= chain_n;
+      if (per.size() >= (size_t)io.max_periods) { io.status_or |= 256; searching = false; }   // (given up before the next search is launched, not behind it)
     }
     // the kept period's decode is LAUNCHED behind the next search (the host's ~15 launches ride on the search's device time), in its own context
     if (to_decode >= 0 && searching) {
-      pend.on = true; pend.ctx = pctx[(size_t)to_decode];              // (reserve its context for free_ctx)
+      pend.on = true; pend.ctx = per[(size_t)to_decode].ctx;             // (reserve its context for free_ctx)
       int r = launch_search(); pend.on = false; if (r) return r;
     } else if (searching) { int r = launch_search(); if (r) return r; }
     if (to_decode >= 0) { int r = decode_launch((size_t)to_decode, true, s2); if (r) return r; }
@@ -1451,17 +1228,17 @@ static int walk_window(dvbt_rx *h, const float2 *chain, size_t chain_n, hipStrea
       io.head_ncalls = ncalls;
       if (ncalls - per[zl].call0 >= io.establish_calls) {
         // keep what the pilot engine holds in front of the period: it is handed to the next window when the superframe start comes too late for the stream to go over to pieces
-        HIPCHK(hipMemcpyAsync(h->tps_snap[0], h->tps_state, sizeof(TpsState), hipMemcpyDeviceToDevice, s));
-        HIPCHK(hipMemcpyAsync(h->tps_prev_snap[0], h->tps_prev, sizeof(float2) * d.n_tps, hipMemcpyDeviceToDevice, s));
+        HIPCHK(hipMemcpyAsync(h->tps_snap, h->tps_state, sizeof(TpsState), hipMemcpyDeviceToDevice, s));
+        HIPCHK(hipMemcpyAsync(h->tps_prev_snap, h->tps_prev, sizeof(float2) * d.n_tps, hipMemcpyDeviceToDevice, s));
         const size_t acc0 = acc; const int del0 = delivering; const bool proc0 = processed, cut0 = cut_pending; const bool any0 = io.any_decoded;
         { int r = decode_launch((size_t)zl, false, s); if (r) return r; r = decode_finish(); if (r) return r; }
         const WalkPeriod &w = per[zl];
-        if (w.decoded && w.first_out >= 0 && ncalls - (w.call0 + w.first_out) >= io.establish_calls) { io.established = true; io.head = zl; set_ctx(h, pctx[(size_t)zl]); }
+        if (w.decoded && w.first_out >= 0 && ncalls - (w.call0 + w.first_out) >= io.establish_calls) { io.established = true; io.head = zl; set_ctx(h, per[zl].ctx); }
         else {
           acc = acc0; delivering = del0; processed = proc0; cut_pending = cut0; io.any_decoded = any0;
           per[zl].decoded = false;
-          HIPCHK(hipMemcpyAsync(h->tps_state, h->tps_snap[0], sizeof(TpsState), hipMemcpyDeviceToDevice, s));
-          HIPCHK(hipMemcpyAsync(h->tps_prev, h->tps_prev_snap[0], sizeof(float2) * d.n_tps, hipMemcpyDeviceToDevice, s));
+          HIPCHK(hipMemcpyAsync(h->tps_state, h->tps_snap, sizeof(TpsState), hipMemcpyDeviceToDevice, s));
+          HIPCHK(hipMemcpyAsync(h->tps_prev, h->tps_prev_snap, sizeof(float2) * d.n_tps, hipMemcpyDeviceToDevice, s));
           HIPCHK(hipStreamSynchronize(s));
         }
       }
@@ -1477,7 +1254,52 @@ static int walk_window(dvbt_rx *h, const float2 *chain, size_t chain_n, hipStrea
   }
   io.acc = acc; io.delivering = delivering; io.continuation = processed; io.cut = cut_pending;
   if (processed) io.tps_preset = false;
-  h->n_periods = delivering; h->seg_offset = 0;
+  return DVBT_OK;
+}
+
+// The synchronous entries: the walk over the whole segment as one final window with nothing carried in, then the byte de-interleaver, RS and the descrambler
+// once over the Viterbi stream it laid out, the read-back and the report.
+static int segment_periods(dvbt_rx *h, const float2 *chain, size_t chain_n, hipStream_t s, dvbt_rx_report *rep)
+{
+  h->plog.clear(); h->plog_bytes = 0;
+  WalkIO io; io.cut_handle = true; io.max_periods = 1024; io.max_searches = 4096;
+  { int r = walk_window(h, chain, chain_n, s, io); if (r) return r; }
+  const bool capped = (io.status_or & 256) != 0;                   // the walk was cut short: the rest of the segment is not decoded (status bit 8)
+  int processed = 0, last = -1;                                    // periods decoded, the last of them
+  for (size_t q = 0; q < io.per.size(); q++) if (io.per[q].decoded) { processed++; last = (int)q; }
+  dvbt_rx_report r;
+  if (last < 0) {   // nothing was acquired (or single symbols only): report the last acquisition attempt
+    RxState st = *h->st_host; st.first_out = -1; st.n_out_symbols = 0; st.n_vit_bytes = 0; st.n_rs_items = 0; st.n_rs_words = 0; st.n_ts_bytes = 0;
+    st.rs_fail = st.rs_corr = 0; st.tps_bits = 0; st.ts_first_packet = 0; st.stream_rs_items = 0; st.status |= 4;
+    fill_report(h, st, r);
+    if (capped) r.status |= 256;
+    h->last = r; h->have_last = true; h->seg_serial++; if (rep) *rep = r;
+    return DVBT_OK;
+  }
+  // the byte de-interleaver, the RS decoder, the report and the taps read the state of the LAST decoded period: the searches behind it ran in other contexts
+  set_ctx(h, io.per[(size_t)last].ctx);
+  const size_t acc = io.acc, last_off = io.per[(size_t)last].off; const int delivering = io.delivering;
+  if (delivering <= 1 && processed == 1 && acc == (size_t)io.head_st.n_vit_bytes) {
+    // one period: the device-side plan of that period is already the segment's (cut-stream roundings included)
+    int rr = enqueue_tail(h, s, (long long)(acc / 204 + 1), -1); if (rr) return rr;
+  } else {
+    int rr = enqueue_tail(h, s, (long long)(acc / 204 + 1), (long long)(acc / 204)); if (rr) return rr;
+  }
+  HIPCHK(hipMemcpyAsync(h->st_host, h->st, sizeof(RxState), hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  RxState fin = *h->st_host;
+  if (!fin.tps_bits) fin.tps_bits = io.tps_keep;                  // (the stream's TPS word: a period that saw no whole frame does not take it away)
+  if (delivering > 1 || processed > 1) fin.n_vit_bytes = (long long)acc;
+  fill_report(h, fin, r);
+  // the front-end fields describe the LAST processed period (the debug taps hold it); the stream fields the whole segment
+  r.segment_offset = (int64_t)last_off;
+  if (r.resume_sample) r.resume_sample += (int64_t)last_off;
+  r.n_lock_periods = delivering; r.total_symbols = io.total_symbols;
+  if (capped) r.status |= 256;
+  if (h->cut.stream_symbol_offset != 0 && (delivering > 1 || processed > 1)) r.status |= 128;   // a cut piece that lost the lock: laid out from its own start, not in the stream's coordinates
+  if (delivering == 0) { r.first_out_symbol = -1; r.status |= 4; }
+  h->last = r; h->have_last = true; h->seg_serial++;
+  if (rep) *rep = r;
   return DVBT_OK;
 }
 

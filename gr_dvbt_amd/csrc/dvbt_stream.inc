@@ -21,7 +21,7 @@
 // ON COUNTERS THAT WENT ON COUNTING THROUGH THE GAP (demod_reference_signals_impl.cc:115-136; the pilot engine's members live on), the Viterbi decoder is reset
 // at the tag (viterbi_decoder_impl.cc:213-229), the byte de-interleaver realigned but not cleared (convolutional_deinterleaver_impl.cc:109-120), the
 // descrambler searches again (energy_descramble_impl.cc:121-141).  None of that can be cut into independent pieces: the stream is walked window by window
-// (walk_window: the lock-period walk of dvbt_rx_segment_run with the blocks' state carried from window to window), synchronously, on handle 0:
+// (walk_window: the one lock-period walk, which dvbt_rx_segment_run calls for a whole segment, here with the blocks' state carried from window to window), synchronously, on handle 0:
 //   * a window = the samples from the search position of the first lock period that is not final yet to the end of what has been pushed; the periods that are
 //     final are decoded and appended to the walk's Viterbi stream; the last period that has items is handed to the next window (its end lies in samples to come);
 //   * behind every window A8 + A9 run over the words of the Viterbi stream that are final and the host follows the descrambler over them (walk_flush); the
@@ -840,7 +840,6 @@ static int stream_harvest(dvbt_rx_stream *s, StreamPiece &pc)
     pc.skip = skip;                                                  // (beyond what the piece's own TPS frame search can give up: the walk takes it from there, counters preset)
     if (skip > 0 && skip <= STREAM_PIECE_SKIP_MAX * s->L) {
       dvbt_rx_cut cut = {272 * pc.first_sf, s->delay, pc.phase}; { int r = dvbt_rx_set_cut(h, &cut); if (r) return r; }
-      h->n_periods = 1; h->seg_offset = 0;
       { int r = enqueue(h, iq + skip, (size_t)(pc.n - skip), st); if (r) return r; }
       { int r = dvbt_rx_segment_finish(h, &pc.rep); if (r) return r; }
       lost_inside = (pc.rep.status & 2) && pc.rep.resume_sample && pc.rep.resume_sample < pc.n - pc.skip - 4 * s->L;
@@ -937,7 +936,6 @@ static int stream_launch(dvbt_rx_stream *s)
   const long long e0 = pc.first_sf * s->wsf;
   pc.phase = s->world == 1 && s->dc_valid ? (int)(((s->dc - e0) % 16 + 16) % 16) + 1 : 0;
   dvbt_rx_cut cut = {272 * pc.first_sf, s->delay, pc.phase}; { int r = dvbt_rx_set_cut(h, &cut); if (r) return r; }
-  h->n_periods = 1; h->seg_offset = 0;
   const float2 *iq; { int r = stream_piece_samples(s, pc, st, &iq); if (r) return r; }   // (borrowed samples: decoded in place when one region holds the piece)
   { int r = enqueue(h, iq, (size_t)pc.n, st); if (r) return r; }
   s->last_handle = hi;
