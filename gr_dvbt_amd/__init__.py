@@ -1,4 +1,4 @@
-"""gr_dvbt_amd -- host-side Python binding of libdvbt_hip.so (the MI355X DVB-T RX hot path, the modulator, the channel block, the sample-clock offset block, the fading block, the RF front-end block, the spectrum analyser and the channel sounder).
+"""gr_dvbt_amd -- host-side Python binding of libdvbt_hip.so (the MI355X DVB-T RX hot path, the modulator, the channel block, the sample-clock offset block, the fading block, the RF front-end block, the spectrum analyser, the channel sounder and the constellation analyser).
 
 Thin ctypes layer over the C ABI declared in include/dvbt_hip.h.  There is no CPU
 fallback: importing works anywhere, but every compute entry point raises unless the HIP
@@ -8,6 +8,7 @@ from .binding import (  # noqa: F401
     lib, build, DvbtError, RxParams, RxReport, RxQuality, Rx, RxStream, TxParams, Tx, TX_SCALE, ChannelParams, Channel, CHANNEL_MAX_PATHS, CHANNEL_MAX_DELAY, ClockParams, ClockOffset, clock_outputs, FadingParams, Fading, fading_table, tu6_paths,
     FADING_MAX_PATHS, FADING_MAX_DELAY, FADING_MAX_SINUSOIDS, FADING_KNOT, RfParams, RfMask, RfFrontend, phase_noise_tones, RF_MAX_TONES, RF_MAX_MASK_POINTS, SpectrumParams, SpectrumResult, SpectrumReading, Spectrum,
     SounderParams, SounderResult, SounderReading, Sounder,
+    ConstellationParams, ConstellationResult, ConstellationReading, Constellation, constellation_grid, CONSTELLATION_GRID, CONSTELLATION_STEP, POINT_DTYPE, CARRIER_DTYPE,
     spectrum_window, SPECTRUM_HIST_BINS, get_dims, device_count, Block, Tag, Sideband, BLOCK_PARAMS, TX_BLOCKS,
     TAG_SYNC_START, TAG_SUPERFRAME_START, TAG_SYMBOL_INDEX,
     QPSK, QAM16, QAM64, NH, C1_2, C2_3, C3_4, C5_6, C7_8, T2k, T8k, G1_32, G1_16, G1_8, G1_4,

@@ -1166,6 +1166,214 @@ class Sounder(_Handle):
         super().close()
 
 
+CONSTELLATION_GRID = 128
+CONSTELLATION_STEP = 4096.0      # quantisation steps per grid unit d
+POINT_DTYPE = np.dtype([(f, np.int64) for f in ("n", "sum_re", "sum_im", "sum_re_im", "sum_re2", "sum_im2")])
+CARRIER_DTYPE = np.dtype([(f, np.int64) for f in ("n", "signal", "error")])
+
+
+class ConstellationParams(C.Structure):
+    _fields_ = [("device", C.c_int), ("constellation", C.c_int), ("hierarchy", C.c_int), ("row_length", C.c_int)]
+
+
+class ConstellationResult(C.Structure):
+    _fields_ = [("rows_pushed", C.c_longlong), ("cells", C.c_longlong), ("nonfinite", C.c_longlong), ("clipped", C.c_longlong),
+                ("points", C.c_int), ("levels", C.c_int), ("alpha", C.c_int), ("span", C.c_int)]
+
+
+@_typed_once
+def _constellation_lib(L):
+    L.dvbt_constellation_create.argtypes = [C.POINTER(ConstellationParams), C.POINTER(C.c_void_p)]
+    L.dvbt_constellation_push.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+    L.dvbt_constellation_push_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+    L.dvbt_constellation_read.argtypes = [C.c_void_p, C.POINTER(ConstellationResult), C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]
+    L.dvbt_constellation_reset.argtypes = [C.c_void_p]
+    L.dvbt_constellation_destroy.argtypes = [C.c_void_p]
+
+
+def constellation_grid(constellation, hierarchy=NH):
+    """(levels L, alpha, span S) of a constellation and hierarchy, as dvbt_constellation_result echoes them"""
+    if constellation not in (QPSK, QAM16, QAM64) or hierarchy not in (NH, ALPHA1, ALPHA2, ALPHA4) or (constellation == QPSK and hierarchy != NH):
+        raise DvbtError("no such constellation / hierarchy")
+    L, alpha = (2, 4, 8)[constellation], (1, 1, 2, 4)[hierarchy]
+    S = 2
+    while S < alpha + L - 1:
+        S *= 2
+    return L, alpha, S
+
+
+def _db(num, den):
+    """10 log10(num / den) in float64: nan where either is empty, inf where only the denominator is"""
+    num, den = np.asarray(num, np.float64), np.asarray(den, np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        out = np.where(num > 0, np.where(den > 0, 10.0 * np.log10(num / np.where(den > 0, den, 1.0)), np.inf), np.nan)
+    return out
+
+
+class ConstellationReading:
+    """What Constellation.read() returns: `hist` ([G][G] uint64: the I/Q density, hist[b_im][b_re] over [-span, span) grid units per axis), `points` (L^2
+    records n, sum_re, sum_im, sum_re_im, sum_re2, sum_im2 of the quantised error, point p = row L + col), `carriers` (row_length records n, signal, error)
+    and the totals of dvbt_constellation_result.  The figures of TR 101 290's constellation analysis are float64 on the host from these integers, in grid
+    units d, and need no GPU; each is nan where its inputs are empty."""
+
+    def __init__(self, hist, points, carriers, rows_pushed, cells, nonfinite, clipped, levels, alpha, span):
+        self.hist = np.asarray(hist, dtype=np.uint64).reshape(CONSTELLATION_GRID, CONSTELLATION_GRID)
+        self.points = np.asarray(points, dtype=POINT_DTYPE).reshape(-1)
+        self.carriers = np.asarray(carriers, dtype=CARRIER_DTYPE).reshape(-1)
+        self.rows_pushed, self.cells, self.nonfinite, self.clipped = int(rows_pushed), int(cells), int(nonfinite), int(clipped)
+        self.levels, self.alpha, self.span = int(levels), int(alpha), int(span)
+        assert len(self.points) == self.levels ** 2
+
+    @property
+    def ideal(self):
+        """[L^2][2]: (re, im) of every point in grid units, point p = row L + col"""
+        H = self.levels // 2
+        i = np.arange(self.levels)
+        ax = np.where(i >= H, self.alpha + 2.0 * (i - H), -(self.alpha + 2.0 * (H - 1 - i)))
+        return np.stack([np.tile(ax, self.levels), np.repeat(ax, self.levels)], axis=1)
+
+    @property
+    def mer_db(self):
+        return float(_db(float(self.carriers["signal"].sum()) * CONSTELLATION_STEP ** 2, float(self.carriers["error"].sum())))
+
+    @property
+    def mer_per_carrier_db(self):
+        return _db(self.carriers["signal"].astype(np.float64) * CONSTELLATION_STEP ** 2, self.carriers["error"].astype(np.float64))
+
+    def means(self):
+        """(n, [L^2][2] mean error of every point in grid units; nan where the point was never hit)"""
+        n = self.points["n"].astype(np.float64)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            d = np.stack([self.points["sum_re"], self.points["sum_im"]], axis=1) / (CONSTELLATION_STEP * n[:, None])
+        return n, d
+
+    def fit(self):
+        """(A, b): the least-squares affine map from ideal point to measured mean, mean_p = A ideal_p + b, A real 2 x 2, weights n_p"""
+        n, d = self.means()
+        use = n > 0
+        if use.sum() < 3:
+            return np.full((2, 2), np.nan), np.full(2, np.nan)
+        x, w = self.ideal[use], n[use]
+        X = np.concatenate([x, np.ones((len(x), 1))], axis=1) * np.sqrt(w)[:, None]
+        Y = (x + d[use]) * np.sqrt(w)[:, None]
+        sol, _, rank, _ = np.linalg.lstsq(X, Y, rcond=None)
+        if rank < 3:
+            return np.full((2, 2), np.nan), np.full(2, np.nan)
+        return sol[:2].T.copy(), sol[2].copy()
+
+    @property
+    def carrier_suppression_db(self):
+        _, b = self.fit()
+        return float(_db(float((self.ideal ** 2).sum(axis=1).mean()), float(b @ b))) if np.isfinite(b).all() else float("nan")
+
+    @property
+    def amplitude_imbalance_pct(self):
+        A, _ = self.fit()
+        v = np.hypot(A[0], A[1])                   # the lengths of A's columns
+        return float((v.max() / v.min() - 1.0) * 100.0) if np.isfinite(v).all() and v.min() > 0 else float("nan")
+
+    @property
+    def quadrature_error_deg(self):
+        A, _ = self.fit()
+        if not np.isfinite(A).all():
+            return float("nan")
+        c = float(A[:, 0] @ A[:, 1]) / float(np.hypot(*A[:, 0]) * np.hypot(*A[:, 1]))
+        return 90.0 - float(np.degrees(np.arccos(np.clip(c, -1.0, 1.0))))
+
+    def ste(self):
+        """(STEM, STED): the mean and the standard deviation over the points hit of |d_p| / S_rms, d_p the mean error of point p and S_rms the rms magnitude
+        of the ideal points"""
+        n, d = self.means()
+        use = n > 0
+        if not use.any():
+            return float("nan"), float("nan")
+        s = np.hypot(d[use, 0], d[use, 1]) / np.sqrt((self.ideal ** 2).sum(axis=1).mean())
+        return float(s.mean()), float(s.std())
+
+    @property
+    def phase_jitter_deg(self):
+        """over the four corner points, from their second moments: sqrt(max(var_tangential - var_radial, 0)) / |corner|, in degrees"""
+        L = self.levels
+        p = self.points[[0, L - 1, L * (L - 1), L * L - 1]]
+        n = p["n"].astype(np.float64)
+        if not (n > 0).all():
+            return float("nan")
+        corners = self.ideal[[0, L - 1, L * (L - 1), L * L - 1]]
+        s = CONSTELLATION_STEP
+        mx, my = p["sum_re"] / (s * n), p["sum_im"] / (s * n)
+        vxx, vyy, vxy = p["sum_re2"] / (s * s * n) - mx * mx, p["sum_im2"] / (s * s * n) - my * my, p["sum_re_im"] / (s * s * n) - mx * my
+        rho = np.hypot(corners[:, 0], corners[:, 1])
+        ur, ui = corners[:, 0] / rho, corners[:, 1] / rho                      # radial unit vectors; the tangential one is (-ui, ur)
+        var_r = ur * ur * vxx + 2.0 * ur * ui * vxy + ui * ui * vyy
+        var_t = ui * ui * vxx - 2.0 * ur * ui * vxy + ur * ur * vyy
+        w = n / n.sum()
+        return float(np.degrees(np.sqrt(max(float((w * (var_t - var_r)).sum()), 0.0)) / float(rho[0])))
+
+
+class Constellation(_Handle):
+    """dvbt_constellation_*: a constellation analyser on the GPU.  It consumes equalised data cells -- rows of row_length complex64, the layout of the
+    receiver's TAP_EQ -- as one stream over any number of push() / push_device() calls and accumulates, in integers, the I/Q density, the error cloud of
+    every constellation point and the signal and error sums of every carrier (include/dvbt_hip.h has the definitions).  read() synchronises and returns a
+    ConstellationReading; it does not disturb the accumulation.  A stream cut into calls gives the same bits."""
+    _prefix = "dvbt_constellation"
+
+    def __init__(self, constellation, hierarchy=NH, row_length=1512, device=0):
+        self.L = _constellation_lib()
+        self.p = ConstellationParams(int(device), int(constellation), int(hierarchy), int(row_length))
+        self.h = C.c_void_p()
+        _chk(self.L.dvbt_constellation_create(C.byref(self.p), C.byref(self.h)))
+
+    def push(self, rows):
+        """rows [n][row_length] complex64 from the host; continues the stream"""
+        rows = np.ascontiguousarray(rows, dtype=np.complex64).reshape(-1, self.p.row_length)
+        _chk(self.L.dvbt_constellation_push(self.h, rows.ctypes.data_as(C.c_void_p), len(rows)))
+
+    def push_device(self, rows_ptr, nrows, stream=None):
+        """a device pointer (int) to nrows rows: enqueues on `stream` (a hipStream_t as int, None: the default stream)"""
+        _chk(self.L.dvbt_constellation_push_device(self.h, C.c_void_p(rows_ptr), nrows, C.c_void_p(stream) if stream else None))
+
+    def read(self):
+        r = ConstellationResult()
+        levels = constellation_grid(self.p.constellation, self.p.hierarchy)[0]
+        hist = np.zeros((CONSTELLATION_GRID, CONSTELLATION_GRID), np.uint64)
+        points, carriers = np.zeros(levels ** 2, POINT_DTYPE), np.zeros(self.p.row_length, CARRIER_DTYPE)
+        _chk(self.L.dvbt_constellation_read(self.h, C.byref(r), hist.ctypes.data_as(C.c_void_p), points.ctypes.data_as(C.c_void_p), len(points),
+                                            carriers.ctypes.data_as(C.c_void_p), len(carriers)))
+        assert r.points == len(points) and r.levels == levels
+        return ConstellationReading(hist, points, carriers, r.rows_pushed, r.cells, r.nonfinite, r.clipped, r.levels, r.alpha, r.span)
+
+    def push_rx(self, rx, first_row=0):
+        """the last finished segment of an Rx(taps=True) or Rx(quality=True): rows first_row .. n_out_symbols - 1 of its EQ tap (the rows from
+        first_out_symbol on) straight from the device"""
+        if rx.report is None:
+            raise DvbtError("the receiver has not run a segment")
+        if rx.dims.payload_length != self.p.row_length or (rx.p.constellation, rx.p.hierarchy) != (self.p.constellation, self.p.hierarchy):
+            raise DvbtError("the receiver's constellation, hierarchy or payload length is not the analyser's")
+        base = rx.tap_device_ptr(TAP_EQ)
+        if not base:
+            raise DvbtError("the receiver keeps no equalised cells: create it with taps=True or quality=True")
+        n = rx.report.n_out_symbols - int(first_row)
+        if first_row < 0:
+            raise DvbtError("first_row must not be negative")
+        if n <= 0:
+            return
+        self.push_device(base + 8 * self.p.row_length * (max(rx.report.first_out_symbol, 0) + int(first_row)), n)
+        _chk(self.L.dvbt_synchronize(None))        # the receiver's tap may change once this returns
+
+    @classmethod
+    def from_rx(cls, rx, first_row=0):
+        """an analyser of the receiver's constellation, hierarchy, payload length and device that has been pushed its last finished segment (push_rx)"""
+        if rx.report is None:
+            raise DvbtError("the receiver has not run a segment")
+        c = cls(rx.p.constellation, rx.p.hierarchy, rx.dims.payload_length, rx.p.device)
+        try:
+            c.push_rx(rx, first_row)
+        except Exception:
+            c.close()
+            raise
+        return c
+
+
 # ------------------------------------------------------------------ per-block C ABI (one triple per reference block)
 TAG_SYNC_START, TAG_SUPERFRAME_START, TAG_SYMBOL_INDEX = 1, 2, 3
 
