@@ -1,4 +1,4 @@
-"""gr_dvbt_amd -- host-side Python binding of libdvbt_hip.so (the MI355X DVB-T RX hot path, the modulator, the channel block, the sample-clock offset block, the fading block, the RF front-end block, the spectrum analyser, the channel sounder and the constellation analyser).
+"""gr_dvbt_amd -- host-side Python binding of libdvbt_hip.so (the MI355X DVB-T RX hot path, the modulator, the channel block, the sample-clock offset block, the fading block, the RF front-end block, the spectrum analyser, the channel sounder, the constellation analyser and the tuner).
 
 Thin ctypes layer over the C ABI declared in include/dvbt_hip.h.  There is no CPU
 fallback: importing works anywhere, but every compute entry point raises unless the HIP
@@ -8,6 +8,8 @@ from .binding import (  # noqa: F401
     lib, build, DvbtError, RxParams, RxReport, RxQuality, Rx, RxStream, TxParams, Tx, TX_SCALE, ChannelParams, Channel, CHANNEL_MAX_PATHS, CHANNEL_MAX_DELAY, ClockParams, ClockOffset, clock_outputs, FadingParams, Fading, fading_table, tu6_paths,
     FADING_MAX_PATHS, FADING_MAX_DELAY, FADING_MAX_SINUSOIDS, FADING_KNOT, RfParams, RfMask, RfFrontend, phase_noise_tones, RF_MAX_TONES, RF_MAX_MASK_POINTS, SpectrumParams, SpectrumResult, SpectrumReading, Spectrum,
     SounderParams, SounderResult, SounderReading, Sounder,
+    TunerParams, TunerDesc, Tuner, tuner_outputs, tuner_design, IQ_CF32, IQ_CS16, IQ_CS8, IQ_CU8, IQ_DTYPES, IQ_BYTES, IQ_SCALES,
+    TUNER_PASS_EDGE, TUNER_STOP_EDGE, TUNER_ATTEN_DB,
     ConstellationParams, ConstellationResult, ConstellationReading, Constellation, constellation_grid, CONSTELLATION_GRID, CONSTELLATION_STEP, POINT_DTYPE, CARRIER_DTYPE,
     spectrum_window, SPECTRUM_HIST_BINS, get_dims, device_count, Block, Tag, Sideband, BLOCK_PARAMS, TX_BLOCKS,
     TAG_SYNC_START, TAG_SUPERFRAME_START, TAG_SYMBOL_INDEX,

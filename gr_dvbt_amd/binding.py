@@ -678,6 +678,178 @@ class ClockOffset(_Handle):
         return n.value
 
 
+IQ_CF32, IQ_CS16, IQ_CS8, IQ_CU8 = range(4)
+IQ_DTYPES = (np.dtype(np.complex64), np.dtype(np.int16), np.dtype(np.int8), np.dtype(np.uint8))
+IQ_BYTES = (8, 4, 2, 2)                                     # per sample
+IQ_SCALES = (1.0, 1.0 / 32768, 1.0 / 128, 1.0 / 127.5)      # full scale -> 1
+TUNER_PASS_EDGE, TUNER_STOP_EDGE, TUNER_ATTEN_DB = 0.42, 0.58, 70.0
+
+
+class TunerParams(C.Structure):
+    _fields_ = [("format", C.c_int), ("interpolation", C.c_int), ("decimation", C.c_int), ("swap_iq", C.c_int), ("shift", C.c_double), ("scale", C.c_float),
+                ("pass_edge", C.c_double), ("stop_edge", C.c_double), ("atten_db", C.c_double), ("first_in", C.c_int64), ("device", C.c_int)]
+
+    @classmethod
+    def of(cls, format, interpolation, decimation, shift=0.0, scale=None, pass_edge=0, stop_edge=0, atten_db=0, swap_iq=False, first_in=0, device=0):
+        """the struct with the Python layer's defaults filled in: scale None is the format's full scale, an edge or attenuation of 0 the default"""
+        if format not in (IQ_CF32, IQ_CS16, IQ_CS8, IQ_CU8):
+            raise ValueError("format must be IQ_CF32, IQ_CS16, IQ_CS8 or IQ_CU8")
+        return cls(int(format), int(interpolation), int(decimation), int(bool(swap_iq)), float(shift), float(IQ_SCALES[format] if scale is None else scale),
+                   float(pass_edge or TUNER_PASS_EDGE), float(stop_edge or TUNER_STOP_EDGE), float(atten_db or TUNER_ATTEN_DB), int(first_in), int(device))
+
+
+class TunerDesc(C.Structure):
+    _fields_ = [("interpolation", C.c_int), ("decimation", C.c_int), ("ntaps", C.c_int), ("nt", C.c_int), ("delay_num", C.c_int64), ("delay_den", C.c_int64),
+                ("phase_inc", C.c_uint64)]
+
+
+@_typed_once
+def _tuner_lib(L):
+    L.dvbt_tuner_design.argtypes = [C.POINTER(TunerParams), C.c_void_p, C.c_int, C.POINTER(C.c_int)]
+    L.dvbt_tuner_outputs.argtypes = [C.POINTER(TunerParams), C.c_int, C.c_int64, C.POINTER(C.c_int64)]
+    L.dvbt_tuner_create.argtypes = [C.POINTER(TunerParams), C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]
+    L.dvbt_tuner_get_taps.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
+    L.dvbt_tuner_info.argtypes = [C.c_void_p, C.POINTER(TunerDesc)]
+    L.dvbt_tuner_outputs_for.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
+    L.dvbt_tuner_run.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
+    L.dvbt_tuner_run_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p]
+    L.dvbt_tuner_reset.argtypes = [C.c_void_p]
+    L.dvbt_tuner_destroy.argtypes = [C.c_void_p]
+    L.dvbt_device_malloc.restype = C.c_void_p
+    L.dvbt_device_malloc.argtypes = [C.c_size_t]
+    L.dvbt_device_free.argtypes = [C.c_void_p]
+    L.dvbt_copy_to_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+    L.dvbt_synchronize.argtypes = [C.c_void_p]
+
+
+def tuner_outputs(params, n_in_total, ntaps=0):
+    """dvbt_tuner_outputs: the outputs a stream with these TunerParams has emitted once n_in_total inputs have been pushed; ntaps is the length of the
+    caller's prototype, 0 for the designed one (host arithmetic, needs no GPU)"""
+    n = C.c_int64()
+    _chk(_tuner_lib().dvbt_tuner_outputs(C.byref(params), int(ntaps), int(n_in_total), C.byref(n)))
+    return n.value
+
+
+def tuner_design(params):
+    """dvbt_tuner_design: the prototype the library designs for these TunerParams, as float32 (host arithmetic, needs no GPU)"""
+    L = _tuner_lib()
+    n = C.c_int()
+    _chk(L.dvbt_tuner_design(C.byref(params), None, 0, C.byref(n)))
+    taps = np.empty(n.value, np.float32)
+    _chk(L.dvbt_tuner_design(C.byref(params), taps.ctypes.data_as(C.c_void_p), len(taps), C.byref(n)))
+    return taps
+
+
+class Tuner(_Handle):
+    """dvbt_tuner_*: raw interleaved I/Q as an SDR records it (`format`: IQ_CF32, IQ_CS16, IQ_CS8, IQ_CU8) to complex64 baseband at interpolation /
+    decimation times the capture's rate, on the GPU: conversion with `scale` (None: full scale -> 1), a mixer of `shift` cycles per input sample, a polyphase
+    low-pass with the caller's `taps` or one designed from pass_edge / stop_edge (fractions of the output rate; 0: 0.42 / 0.58) and atten_db (0: 70).  One
+    stream, delivered over any number of run() / run_device() calls of any size; the concatenated outputs are bit for bit those of one call."""
+    _prefix = "dvbt_tuner"
+
+    def __init__(self, format, interpolation, decimation, shift=0.0, scale=None, taps=None, pass_edge=0, stop_edge=0, atten_db=0, swap_iq=False, first_in=0,
+                 device=0):
+        self.L = _tuner_lib()
+        self.h = C.c_void_p()
+        self._bufs = [0, 0, 0, 0]                  # feed(): input pointer, its bytes, output pointer, its samples
+        self.p = TunerParams.of(format, interpolation, decimation, shift, scale, pass_edge, stop_edge, atten_db, swap_iq, first_in, device)
+        self.format = int(format)
+        if taps is not None:
+            taps = np.ascontiguousarray(taps, dtype=np.float32).reshape(-1)
+            _chk(self.L.dvbt_tuner_create(C.byref(self.p), taps.ctypes.data_as(C.c_void_p), len(taps), C.byref(self.h)))
+        else:
+            _chk(self.L.dvbt_tuner_create(C.byref(self.p), None, 0, C.byref(self.h)))
+        self.desc = TunerDesc()
+        _chk(self.L.dvbt_tuner_info(self.h, C.byref(self.desc)))
+
+    @classmethod
+    def for_capture(cls, sample_rate, format, channel_mhz=8, offset_hz=0.0, **kw):
+        """the tuner of a capture at sample_rate (Hz) whose DVB-T channel of channel_mhz lies offset_hz above the capture's centre: the ratio is exactly
+        (64/7 MHz * channel_mhz / 8) / sample_rate, the shift -offset_hz / sample_rate.  A ratio outside the block's limits raises."""
+        from fractions import Fraction
+        ratio = Fraction(64_000_000 * channel_mhz, 56) / Fraction(sample_rate)
+        if ratio.numerator > 128 or ratio.denominator > 1024 or ratio.denominator > 8 * ratio.numerator:
+            raise ValueError(f"the ratio {ratio} of a {sample_rate} Hz capture is outside the tuner's limits (L <= 128, M <= 1024, M / L <= 8)")
+        return cls(format, ratio.numerator, ratio.denominator, shift=-float(offset_hz) / float(sample_rate), **kw)
+
+    @property
+    def taps(self):
+        """the prototype in use, float32"""
+        t = np.empty(self.desc.ntaps, np.float32)
+        n = C.c_int()
+        _chk(self.L.dvbt_tuner_get_taps(self.h, t.ctypes.data_as(C.c_void_p), len(t), C.byref(n)))
+        return t
+
+    @property
+    def delay(self):
+        """the group delay in output samples"""
+        from fractions import Fraction
+        return Fraction(self.desc.delay_num, self.desc.delay_den)
+
+    def outputs_for(self, n_in):
+        """samples the NEXT call with n_in input samples will emit"""
+        n = C.c_size_t()
+        _chk(self.L.dvbt_tuner_outputs_for(self.h, n_in, C.byref(n)))
+        return n.value
+
+    def _raw(self, raw):
+        """the caller's samples as one contiguous array of the format's dtype and their count; flat and interleaved, or shaped (n, 2)"""
+        raw = np.asarray(raw)
+        want = IQ_DTYPES[self.format]
+        if raw.dtype != want:
+            raise ValueError(f"this tuner takes {want} samples, not {raw.dtype}")
+        raw = np.ascontiguousarray(raw).reshape(-1)
+        if self.format != IQ_CF32 and len(raw) % 2:
+            raise ValueError("interleaved I/Q has an even number of components")
+        return raw, (len(raw) if self.format == IQ_CF32 else len(raw) // 2)
+
+    def run(self, raw):
+        """raw samples in (complex64, or int16 / int8 / uint8 interleaved or shaped (n, 2)), the complex64 outputs they complete out; continues the stream"""
+        raw, n_in = self._raw(raw)
+        out = np.empty(self.outputs_for(n_in), np.complex64)
+        n = C.c_size_t()
+        _chk(self.L.dvbt_tuner_run(self.h, raw.ctypes.data_as(C.c_void_p), n_in, out.ctypes.data_as(C.c_void_p), len(out), C.byref(n)))
+        return out[:n.value]
+
+    def run_device(self, in_ptr, n_in, out_ptr, out_cap, stream=None):
+        """device pointers (ints), not overlapping: enqueues on `stream` (a hipStream_t as int, None: the default stream) and returns the output count at once"""
+        n = C.c_size_t()
+        _chk(self.L.dvbt_tuner_run_device(self.h, C.c_void_p(in_ptr), n_in, C.c_void_p(out_ptr), out_cap, C.byref(n), C.c_void_p(stream) if stream else None))
+        return n.value
+
+    def feed(self, stream, raw):
+        """raw samples through the tuner on the device and on into an RxStream (push_device); returns the number of samples pushed.  Correct rather than
+        fast: the stream object copies the samples on its own HIP stream, so this waits for the device before the next call reuses the buffers
+        (INTEGRATION.md 3j has the fast path)."""
+        raw, n_in = self._raw(raw)
+        n_out = self.outputs_for(n_in)
+        b = self._bufs
+        if raw.nbytes > b[1]:
+            self.L.dvbt_device_free(C.c_void_p(b[0]))
+            b[0], b[1] = self.L.dvbt_device_malloc(raw.nbytes), raw.nbytes
+        if n_out > b[3]:
+            self.L.dvbt_device_free(C.c_void_p(b[2]))
+            b[2], b[3] = self.L.dvbt_device_malloc(8 * n_out), n_out
+        if n_in and not b[0] or n_out and not b[2]:
+            raise DvbtError("device allocation failed")
+        if n_in:
+            _chk(self.L.dvbt_copy_to_device(C.c_void_p(b[0]), raw.ctypes.data_as(C.c_void_p), raw.nbytes))
+        got = self.run_device(b[0], n_in, b[2], b[3])
+        _chk(self.L.dvbt_synchronize(None))
+        if got:
+            stream.push_device(b[2], got)
+            _chk(self.L.dvbt_synchronize(None))
+        return got
+
+    def close(self):
+        if self.h:
+            for i in (0, 2):
+                if self._bufs[i]:
+                    self.L.dvbt_device_free(C.c_void_p(self._bufs[i]))
+            self._bufs = [0, 0, 0, 0]
+        super().close()
+
+
 FADING_MAX_PATHS, FADING_MAX_DELAY, FADING_MAX_SINUSOIDS, FADING_KNOT = 24, 8192, 32, 64
 TU6_DELAYS_US = (0.0, 0.2, 0.5, 1.6, 2.3, 5.0)          # COST 207 TU6
 TU6_POWERS_DB = (-3.0, 0.0, -2.0, -6.0, -8.0, -10.0)

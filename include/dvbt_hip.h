@@ -1246,6 +1246,79 @@ int  dvbt_constellation_read(dvbt_constellation *h, dvbt_constellation_result *r
 int  dvbt_constellation_reset(dvbt_constellation *h);   /* back to the state after create */
 void dvbt_constellation_destroy(dvbt_constellation *h);
 
+/* ------------------------------------------------------------------ tuner: a recording from an SDR -> complex64 baseband at the elementary rate
+ * Raw interleaved I/Q in one of four formats, at the capture's rate and with the channel off-centre, to complex64 at L/M times that rate, in one kernel
+ * (csrc/k_tuner.hpp; tests/tunerref.py is this text in numpy).  All indices are absolute: the stream's first input sample is n = first_in, x[n] = 0 in
+ * front of it.
+ *   Formats    DVBT_IQ_CF32 (8 bytes per sample, float I then float Q), DVBT_IQ_CS16 (4, int16), DVBT_IQ_CS8 (2, int8), DVBT_IQ_CU8 (2, uint8).
+ *   1 Convert  swap_iq exchanges I and Q first.  Then per component v = (float)raw * scale; for CU8 v = ((float)raw - 127.5f) * scale (the difference is
+ *              exact).  One rounded multiply; CF32 with scale == 1 keeps the bits.  (The usual scales: 1, 1/32768, 1/128, 1/127.5.)
+ *   2 Mix      inc = nearbyint(shift 2^64) mod 2^64 (ties to even), shift in cycles per INPUT sample, |shift| <= 0.5.  ph(n) = n inc mod 2^64,
+ *              (c, s) = the cosine and sine of the top 32 bits of ph as a fraction of a turn (the channel block's float polynomial, csrc/k_channel.hpp),
+ *              z = (v.re c - v.im s, v.re s + v.im c), every product and every sum rounded on its own.  inc == 0: the stage is skipped, z = v bit for bit.
+ *   3 Resample by L/M = interpolation / decimation after gcd reduction.  h is a real prototype of ntaps taps at L times the input rate, its branches
+ *              br[b][k] = h[b + k L], zero padded to nt = ceil(ntaps / L) taps each.  Output m: n(m) = floor(m M / L), b = m M mod L,
+ *                y[m] = sum_{k = nt-1 .. 0} br[b][k] z[n(m) - k]
+ *              in that order (ascending input index), re and im apart, every product rounded, then every sum; no fused multiply-add.  The first product
+ *              starts the sum: that is a sum from +0 in every bit but one -- a sum whose products are all -0.0 stays -0.0, so L = M = 1 with the one tap
+ *              1.0 returns the input's bits, -0.0 included.  A numpy float32 loop over k reproduces an output literally.
+ *   Counts     once the inputs in front of Nabs = first_in + N have arrived, every m with n(m) < Nabs has been emitted: ceil(Nabs L / M) -
+ *              ceil(first_in L / M) outputs, host integer arithmetic (dvbt_tuner_outputs, dvbt_tuner_outputs_for).  Every input is consumed; no flush.
+ *   Streaming  the handle keeps the last 320 values of z on the device (z is a function of the raw sample and n alone).  A stream cut into calls of any
+ *              sizes (0, 1 and fewer than nt included; a CS8 or CU8 stream cut at an odd sample is 2-byte aligned) gives bit for bit what one call
+ *              gives, and a handle with first_in = n0 fed from n0 on equals the whole stream from output ceil((n0 + nt - 1) L / M) on.  Index
+ *              arithmetic is 64-bit: first_in in [0, 2^48], at most 2^48 inputs per stream.
+ *   Taps       dvbt_tuner_create takes the caller's prototype (taps, ntaps) or, with taps == NULL, designs one from pass_edge, stop_edge (fractions of
+ *              the OUTPUT rate) and atten_db (dB) -- a Kaiser-windowed sinc, computed in double (dvbt_tuner_design is the same rule, needs no device):
+ *                L > M: stop = min(stop, M / L - pass) (the images of the capture); refused unless stop > pass
+ *                fp = pass / M, fs = stop / M, fc = (fp + fs) / 2
+ *                beta = 0.1102 (A - 8.7) for A > 50, else 0.5842 (A - 21)^0.4 + 0.07886 (A - 21)
+ *                ntaps = ceil((A - 7.95) / (2.285 2 pi (fs - fp))) + 1, plus one if that is even
+ *                h[i] = 2 fc sinc(2 fc (i - c)) Io(beta sqrt(1 - ((i - c) / c)^2)) / Io(beta), c = (ntaps - 1) / 2, Io by its power series
+ *                scaled so that sum h = L, then rounded to float.
+ *              The group delay is (ntaps - 1) / (2 M) output samples (dvbt_tuner_info: delay_num / delay_den).
+ *   Limits     format one of the four; 1 <= L <= 128, 1 <= M <= 1024 after reduction, M / L <= 8; nt <= 320 and L nt <= 8192; scale finite and not 0;
+ *              shift finite, |shift| <= 0.5; atten_db in [40, 90]; 0 < pass_edge < stop_edge <= 1 (also where the caller brings the taps); swap_iq 0 or
+ *              1; taps finite.  Per call n_in <= 2^31; the input pointer aligned to one raw sample (8 / 4 / 2 / 2 bytes), the output to 8 bytes; input
+ *              and output ranges that overlap are DVBT_ERR_INVALID; out_cap below the call's count is DVBT_ERR_CAPACITY.  A failed call leaves the
+ *              stream position and the history as they were.
+ * dvbt_tuner_run_device only enqueues on `stream`; calls on different streams are ordered by the handle (an event).  One thread per handle.  Every
+ * parameter is checked before the device is asked for: a bad struct is DVBT_ERR_INVALID everywhere, a good one DVBT_ERR_NO_DEVICE without a GPU -- there is
+ * no CPU path, except dvbt_tuner_outputs and dvbt_tuner_design, which are host arithmetic.
+ * Deliberately not here: (1) DC blocking and AGC -- sequential filters, not a map over the stream; (2) a level or clip meter -- dvbt_spectrum_* measures
+ * the output; (3) ratios that are not rational -- a dvbt_clock_* handle behind the tuner takes the ppm; (4) any change to dvbt_rx_stream_*, which takes
+ * the tuner's output through dvbt_rx_stream_push_device; (5) GNU Radio shells around the block. */
+enum { DVBT_IQ_CF32 = 0, DVBT_IQ_CS16 = 1, DVBT_IQ_CS8 = 2, DVBT_IQ_CU8 = 3 };
+typedef struct {
+  int format;                                    /* DVBT_IQ_* */
+  int interpolation, decimation;                 /* L / M before reduction */
+  int swap_iq;                                   /* 0 or 1 */
+  double shift;                                  /* cycles per input sample, -0.5 .. 0.5 */
+  float scale;                                   /* finite, not 0 */
+  double pass_edge, stop_edge, atten_db;         /* of the designed prototype: fractions of the output rate, dB */
+  int64_t first_in; int device;
+} dvbt_tuner_params;
+typedef struct {
+  int interpolation, decimation;                 /* reduced */
+  int ntaps, nt;                                 /* of the prototype in use; taps per branch */
+  int64_t delay_num, delay_den;                  /* group delay in output samples: (ntaps - 1) / (2 M) */
+  uint64_t phase_inc;                            /* inc of the mixer */
+} dvbt_tuner_desc;
+typedef struct dvbt_tuner dvbt_tuner;
+/* the designed prototype of a valid struct: *ntaps = its length; taps (cap floats) may be NULL to ask for the length alone */
+int  dvbt_tuner_design(const dvbt_tuner_params *p, float *taps, int cap, int *ntaps);
+/* outputs emitted once n_in_total (<= 2^48) inputs have been pushed; ntaps = the caller's prototype length, 0: the designed one (it decides only whether
+ * the struct is accepted).  Host arithmetic, needs no device. */
+int  dvbt_tuner_outputs(const dvbt_tuner_params *p, int ntaps, int64_t n_in_total, int64_t *n_out_total);
+int  dvbt_tuner_create(const dvbt_tuner_params *p, const float *taps /* NULL: designed */, int ntaps, dvbt_tuner **out);
+int  dvbt_tuner_get_taps(const dvbt_tuner *h, float *taps /* may be NULL */, int cap, int *ntaps);
+int  dvbt_tuner_info(const dvbt_tuner *h, dvbt_tuner_desc *desc);
+int  dvbt_tuner_outputs_for(const dvbt_tuner *h, size_t n_in, size_t *n_out);   /* what the NEXT call of n_in samples emits */
+int  dvbt_tuner_run(dvbt_tuner *h, const void *raw_host, size_t n_in, void *out_host, size_t out_cap, size_t *n_out);
+int  dvbt_tuner_run_device(dvbt_tuner *h, const void *raw_device, size_t n_in, void *out_device, size_t out_cap, size_t *n_out, void *stream);
+int  dvbt_tuner_reset(dvbt_tuner *h);   /* back to first_in, history cleared */
+void dvbt_tuner_destroy(dvbt_tuner *h);
+
 #ifdef __cplusplus
 }
 #endif
