@@ -102,22 +102,18 @@ extern "C" int dvbt_fft_create(const dvbt_fft_params *p, dvbt_fft **out)
   BLK_CREATE_PROLOGUE(dvbt_fft);
   h->p = *p;
   int N = p->fft_size;
-  // forward: the RX flowgraphs' fft_vxx(forward, shift=True); forward = 0: the TX flowgraphs' fft_vxx(reverse, shift=True) (k_tx.hpp)
+  // forward: the RX flowgraphs' fft_vxx(forward, shift=True); forward = 0: the TX flowgraphs' fft_vxx(reverse, shift=True) (k_fft.hpp)
   if (!p->shift || N < 64 || N > 8192 || (N & (N - 1))) return fail(DVBT_ERR_INVALID, "only shifted, power-of-two sizes 64..8192 (the configuration of the RX and TX flowgraphs)");
-  WCHK(h->T.build_fft(N));
-  WCHK(set_lds(p->forward ? (const void *)fft_items_kernel : (const void *)ifft_items_kernel, (size_t)(N + N / 32 + N / 128 + 129) * 8));
+  WCHK(h->T.fft.build(N));
+  WCHK(set_lds(p->forward ? (const void *)fft_items_kernel : (const void *)ifft_items_kernel, h->T.fft.lds()));
   *out = hold.release(); return DVBT_OK;
 }
 extern "C" int dvbt_fft_forecast(const dvbt_fft *, int n, int *req) { if (req) *req = n; return DVBT_OK; }
 static void fft_run(dvbt_fft *h, int n, const void *din, void *dout, hipStream_t s)
 {
-  const size_t N = h->p.fft_size;
-  if (!h->p.forward) {
-    hipLaunchKernelGGL(ifft_items_kernel, dim3(n), dim3(FFT_THREADS), (N + N / 32 + N / 128 + 129) * 8, s, (const float2 *)din, (int)N, n, (const float2 *)h->T.tw, (float2 *)dout);
-    return;
-  }
-  hipLaunchKernelGGL(fft_items_kernel, dim3(n), dim3(FFT_THREADS), (N + N / 32 + N / 128 + 129) * 8, s, (const float2 *)din, (int)N, n, (const float2 *)h->T.tw,
-                     (const uint16_t *)h->T.perm, (float2 *)dout);
+  const FftPlan &f = h->T.fft;
+  if (h->p.forward) hipLaunchKernelGGL(fft_items_kernel, dim3(n), dim3(FFT_THREADS), f.lds(), s, (const float2 *)din, f.N, n, (const float2 *)f.tw, (float2 *)dout);
+  else hipLaunchKernelGGL(ifft_items_kernel, dim3(n), dim3(FFT_THREADS), f.lds(), s, (const float2 *)din, f.N, n, (const float2 *)f.tw, (float2 *)dout);
 }
 extern "C" int dvbt_fft_work(dvbt_fft *h, int nout, int nin, const void *in, void *out, dvbt_sideband *sb)
 {
@@ -793,7 +789,7 @@ extern "C" int dvbt_ofdm_sym_acquisition_create(const dvbt_ofdm_sym_acquisition_
   h->fp.N = N; h->fp.cp = cp;
   if (h->st.alloc(1) != hipSuccess || h->as.alloc(1) != hipSuccess || h->st_host.alloc(1) != hipSuccess || h->as_host.alloc(1) != hipSuccess) return fail(DVBT_ERR_HIP, "hipMalloc");
   if (hipMemset(h->st, 0, sizeof(RxState)) != hipSuccess || hipMemset(h->as, 0, sizeof(AcqState)) != hipSuccess) return fail(DVBT_ERR_HIP, "hipMemset");
-  WCHK(set_lds((const void *)derot_fft_kernel, (size_t)(N + N / 32 + N / 128 + 128) * 8));
+  WCHK(set_lds((const void *)derot_fft_kernel, fft_lds_bytes(N)));
   *out = hold.release(); return DVBT_OK;
 }
 // the tracking window may look 8 (+margin) samples past 2N+cp: ask for 16 more than the reference (:474-481)
@@ -827,8 +823,8 @@ static int acq_call(dvbt_ofdm_sym_acquisition *h, int nout, int nin, const void 
   // the wander of the reference's float phase accumulator inside every item (k_drift.hpp): the tracker above carries the accumulator's own value from call to call
   WCHK(h->drift.reserve(sizeof(float) * (size_t)C * (N / 32))); WCHK(h->drift_flags.reserve(16));
   hipLaunchKernelGGL(drift_table_entry_kernel, dim3(C), dim3(N / 32 < 256 ? N / 32 : 256), 0, s, fp, (const RxState *)h->st, (const SymMeta *)h->meta.p, (float *)h->drift.p, (int *)h->drift_flags.p);
-  hipLaunchKernelGGL(derot_fft_kernel, dim3(C), dim3(FFT_THREADS), (size_t)(N + N / 32 + N / 128 + 128) * 8, s, iq, fp, (const RxState *)h->st, (const SymMeta *)h->meta.p,
-                     (const float2 *)nullptr, (const uint16_t *)nullptr, items, (float2 *)nullptr, (const float *)h->drift.p, (const int *)h->drift_flags.p);
+  hipLaunchKernelGGL(derot_fft_kernel, dim3(C), dim3(FFT_THREADS), fft_lds_bytes(N), s, iq, fp, (const RxState *)h->st, (const SymMeta *)h->meta.p,
+                     (const float2 *)nullptr, items, (float2 *)nullptr, (const float *)h->drift.p, (const int *)h->drift_flags.p);
   // how many items came out and how much was consumed depends on the data: one small read-back and ONE synchronisation per call
   HIPCHK(hipMemcpyAsync(h->st_host, h->st, sizeof(RxState), hipMemcpyDeviceToHost, s));
   HIPCHK(hipMemcpyAsync(h->as_host, h->as, sizeof(AcqState), hipMemcpyDeviceToHost, s));

@@ -15,6 +15,7 @@
 #include "hip_own.hpp"
 #include "dvbt_tables.hpp"
 #include "ts_ring.hpp"
+#include "k_fft.hpp"
 #include "k_frontend.hpp"
 #include "k_drift.hpp"
 #include "k_backend.hpp"
@@ -155,9 +156,22 @@ static void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, ui
   w[0] = c0; w[1] = c1; w[2] = c2; w[3] = c3;
 }
 
+struct FftPlan {         // what the host holds for launches of a k_fft.hpp transform at N points: the global twiddle table tw[t] = W_N^t, the dynamic LDS
+  int N = 0; DevMem<float2> tw;
+  int build(int n)
+  {
+    const std::vector<float> t = fft_twiddles(n);
+    std::vector<float2> t2(n);
+    for (int i = 0; i < n; i++) t2[i] = make_float2(t[2 * i], t[2 * i + 1]);
+    N = n;
+    return upload(t2, tw);
+  }
+  size_t lds() const { return fft_lds_bytes(N); }
+};
+
 struct Tables {          // device lookup tables for one configuration
   Dims d;
-  DevMem<float2> tw; DevMem<uint16_t> perm;
+  FftPlan fft;
   DevMem<int16_t> cpilot, tps; DevMem<float> known, pref;
   DevMem<uint16_t> pay_c, pay_L, pay_R, tps_L, tps_R;
   DevMem<uint16_t> pil_k, pay_Li, pay_Ri, tps_Li, tps_Ri; DevMem<uint8_t> pay_d, tps_d; int np[4] = {0, 0, 0, 0};
@@ -167,14 +181,6 @@ struct Tables {          // device lookup tables for one configuration
   DevMem<uint8_t> mul_alpha, gexp, glog, prbs;
   bool front = false, inner = false, rs = false;
 
-  int build_fft(int N)
-  {
-    std::vector<float> tw_h = fft_twiddles(N);
-    std::vector<float2> t2(N);
-    for (int i = 0; i < N; i++) t2[i] = make_float2(tw_h[2 * i], tw_h[2 * i + 1]);
-    int r = upload(t2, tw); if (r) return r;
-    return upload(fft_out_perm(N), perm);
-  }
   int build_front()
   {
     std::vector<int> c = cpilot_table(d), t = tps_table(d);
@@ -508,7 +514,7 @@ extern "C" int dvbt_rx_create(const dvbt_rx_params *p, dvbt_rx **out)
   if (p->viterbi_warm_windows > 0) h->vp.warm = p->viterbi_warm_windows;
   h->max_samples = p->max_samples;
   h->max_calls = (int)((chain_max - (2 * d.N + d.cp + 16)) / (d.N + d.cp) + 1);
-  if ((r = h->T.build_fft(d.N)) || (r = h->T.build_front()) || (r = h->T.build_inner(1.0f)) || (r = h->T.build_rs())) return r;
+  if ((r = h->T.fft.build(d.N)) || (r = h->T.build_front()) || (r = h->T.build_inner(1.0f)) || (r = h->T.build_rs())) return r;
   HIPCHK(h->own_stream.create());
   if (p->front_priority) {
     int least = 0, greatest = 0; HIPCHK(hipDeviceGetStreamPriorityRange(&least, &greatest));
@@ -745,7 +751,7 @@ static void launch_symbols(dvbt_rx *h, hipStream_t s, const float2 *iq, const Fr
 {
   const Dims &d = h->d; const int N = d.N;
   const bool taps = h->acq_tap || h->fft_out || h->eq;
-#define SYM_ARGS iq, fp, (const RxState *)h->st, (const SymMeta *)h->meta, (const float2 *)h->T.tw, h->acq_tap, h->fft_out, h->T.demod_tables(), h->eq, h->tpsval, h->info, \
+#define SYM_ARGS iq, fp, (const RxState *)h->st, (const SymMeta *)h->meta, (const float2 *)h->T.fft.tw, h->acq_tap, h->fft_out, h->T.demod_tables(), h->eq, h->tpsval, h->info, \
                  h->T.inner_params(d.payload), (const float2 *)h->T.points, (const unsigned char *)h->T.label_tab, h->labels, h->sym_ticket, (const float *)h->drift.delta, (const int *)h->drift.flags, h->csi
   // 8k: persistent workgroups, two per CU (k_symbol8k.hpp); 2k: the same design, four symbols per workgroup (k_symbol2k.hpp).  The plain and the DRIFT
   // instantiation are both launched: the one that drift.flags[1] does not select returns before it takes a symbol

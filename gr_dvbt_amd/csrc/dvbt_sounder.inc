@@ -10,7 +10,8 @@
 struct dvbt_sounder {
   dvbt_sounder_params p;
   Dims d; int Kp = 0, M = 0;
-  DevMem<float> win, pref; DevMem<int16_t> cpilot; DevMem<float2> twN, twM;
+  DevMem<float> win, pref; DevMem<int16_t> cpilot;
+  FftPlan twN, twM;                                // twN: its table alone, as cis(-2 pi t / N) (snd_tau); twM: the profile's transform
   DevMem<float2> carry[2]; int cur = 0;            // the open group
   DevMem<float> open[2]; int ocur = 0;             // the open run: a slab as it stands
   DevMem<double> res;                              // M + Kp doubles (the sums of |h|^2 and |E|^2), then the count of used groups (a long long)
@@ -60,7 +61,7 @@ inline void sounder_extract(dvbt_sounder *h, const SndArgs &a, long long s_first
                             bool copy_old, hipStream_t st)
 {
   hipLaunchKernelGGL(sounder_extract_kernel, dim3((unsigned)(nsym + (copy_old ? 1 : 0))), dim3(SND_EXTRACT_THREADS), 0, st, a, s_first, nsym, g_base,
-                     (float2 *)h->ebuf, carry_out, g_open, copy_old ? 1 : 0, (const int16_t *)h->cpilot, (const float *)h->pref, (const float2 *)h->twN);
+                     (float2 *)h->ebuf, carry_out, g_open, copy_old ? 1 : 0, (const int16_t *)h->cpilot, (const float *)h->pref, (const float2 *)h->twN.tw);
 }
 
 // the call's launches on stream st; the caller has checked the buffers.  0 < n <= 2^24.
@@ -86,12 +87,12 @@ inline int sounder_enqueue(dvbt_sounder *h, const float2 *rows, const int *idx, 
       sounder_extract(h, a, s_lo, (int)(4 * g_hi - s_lo), g_lo, nullptr, -1, had_open && g_lo == ga, st);
       HIPCHK(hipGetLastError());
       if (a.N == 2048)
-        hipLaunchKernelGGL((sounder_profile_kernel<1024 / FFT_THREADS, (569 + FFT_THREADS - 1) / FFT_THREADS>), dim3((unsigned)runs), dim3(FFT_THREADS), snd_lds(M),
-                           st, a, (const float2 *)h->ebuf, g_lo, r, ga, gb, (const float *)h->win, (const float2 *)h->twM, (const float *)h->open[h->ocur],
+        hipLaunchKernelGGL((sounder_profile_kernel<1024 / FFT_THREADS, (569 + FFT_THREADS - 1) / FFT_THREADS>), dim3((unsigned)runs), dim3(FFT_THREADS), h->twM.lds(),
+                           st, a, (const float2 *)h->ebuf, g_lo, r, ga, gb, (const float *)h->win, (const float2 *)h->twM.tw, (const float *)h->open[h->ocur],
                            (float *)h->open[onxt], (float *)h->slabs);
       else
-        hipLaunchKernelGGL((sounder_profile_kernel<4096 / FFT_THREADS, (2273 + FFT_THREADS - 1) / FFT_THREADS>), dim3((unsigned)runs), dim3(FFT_THREADS), snd_lds(M),
-                           st, a, (const float2 *)h->ebuf, g_lo, r, ga, gb, (const float *)h->win, (const float2 *)h->twM, (const float *)h->open[h->ocur],
+        hipLaunchKernelGGL((sounder_profile_kernel<4096 / FFT_THREADS, (2273 + FFT_THREADS - 1) / FFT_THREADS>), dim3((unsigned)runs), dim3(FFT_THREADS), h->twM.lds(),
+                           st, a, (const float2 *)h->ebuf, g_lo, r, ga, gb, (const float *)h->win, (const float2 *)h->twM.tw, (const float *)h->open[h->ocur],
                            (float *)h->open[onxt], (float *)h->slabs);
       HIPCHK(hipGetLastError());
       const int closed = runs - ((r + runs - 1 == r1 && to_open) ? 1 : 0);
@@ -141,17 +142,13 @@ extern "C" int dvbt_sounder_create(const dvbt_sounder_params *p, dvbt_sounder **
   h->Kp = Kp; h->M = M;
   const std::vector<float> w = sounder_window(Kp, p->window);
   for (int j = 0; j < Kp; j++) h->sum_w += (double)w[j];
-  const std::vector<float> tn = fft_twiddles(N), tm = fft_twiddles(M);
-  std::vector<float2> t2n(N), t2m(M);
-  for (int i = 0; i < N; i++) t2n[i] = make_float2(tn[2 * i], tn[2 * i + 1]);
-  for (int i = 0; i < M; i++) t2m[i] = make_float2(tm[2 * i], tm[2 * i + 1]);
   const std::vector<int> c = cpilot_table(h->d);
   const std::vector<int16_t> c16(c.begin(), c.end());
-  if ((r = upload(w, h->win)) || (r = upload(t2n, h->twN)) || (r = upload(t2m, h->twM)) || (r = upload(c16, h->cpilot)) ||
+  if ((r = upload(w, h->win)) || (r = h->twN.build(N)) || (r = h->twM.build(M)) || (r = upload(c16, h->cpilot)) ||
       (r = upload(pilot_ref_table(h->d), h->pref))) return r;
   const void *fn = N == 2048 ? (const void *)sounder_profile_kernel<1024 / FFT_THREADS, (569 + FFT_THREADS - 1) / FFT_THREADS>
                              : (const void *)sounder_profile_kernel<4096 / FFT_THREADS, (2273 + FFT_THREADS - 1) / FFT_THREADS>;
-  if ((r = set_lds(fn, snd_lds(M)))) return r;
+  if ((r = set_lds(fn, h->twM.lds()))) return r;
   HIPCHK(h->ord.create());
   const size_t words = snd_slab_words(M, Kp);
   for (int i = 0; i < 2; i++) {

@@ -7,7 +7,7 @@
 
 struct dvbt_spectrum {
   dvbt_spectrum_params p;             // hop already resolved (0 -> N/2)
-  DevMem<float> win; DevMem<float2> tw;
+  DevMem<float> win; FftPlan fft;
   DevMem<float2> hist[2]; int cur = 0;
   DevMem<double> open[2]; int ocur = 0;            // the open group: its power sum, then N floats (the open slab)
   DevMem<double> res;                              // N doubles (PSD sums), 1 (power sum), SPEC_HIST_BINS uint64, 1 word (the peak's bits)
@@ -72,7 +72,7 @@ inline void spectrum_launch(dvbt_spectrum *h, const float2 *in, const SpecArgs &
   double *const psums = (double *)((char *)h->slabs.p + (size_t)SPEC_MAX_GROUPS * N * sizeof(float));
   double *const res = h->res;
   hipLaunchKernelGGL(spectrum_kernel<NB>, dim3((unsigned)groups), dim3(FFT_THREADS), spec_lds(N), st, in, (const float2 *)h->hist[h->cur],
-                     (const float *)h->win, (const float2 *)h->tw, a, g_first, open_in, open_out, slabs, psums,
+                     (const float *)h->win, (const float2 *)h->fft.tw, a, g_first, open_in, open_out, slabs, psums,
                      (unsigned long long *)(res + N + 1), (unsigned *)(res + N + 1 + SPEC_HIST_BINS));
 }
 
@@ -147,10 +147,7 @@ extern "C" int dvbt_spectrum_create(const dvbt_spectrum_params *p, dvbt_spectrum
   const int N = p->fft_size;
   const std::vector<float> w = spectrum_window(N, p->window);
   for (int n = 0; n < N; n++) h->sum_w2 += (double)w[n] * (double)w[n];
-  const std::vector<float> tw_h = fft_twiddles(N);
-  std::vector<float2> t2(N);
-  for (int i = 0; i < N; i++) t2[i] = make_float2(tw_h[2 * i], tw_h[2 * i + 1]);
-  if ((r = upload(w, h->win)) || (r = upload(t2, h->tw))) return r;
+  if ((r = upload(w, h->win)) || (r = h->fft.build(N))) return r;
   const void *fn = N <= FFT_THREADS ? (const void *)spectrum_kernel<1> : N == 2 * FFT_THREADS ? (const void *)spectrum_kernel<2>
                  : N == 4 * FFT_THREADS ? (const void *)spectrum_kernel<4> : N == 8 * FFT_THREADS ? (const void *)spectrum_kernel<8>
                  : (const void *)spectrum_kernel<16>;

@@ -188,32 +188,9 @@ inline PatternTables pattern_tables(const Dims &d, int s)
   return t;
 }
 
-// FFT plan: DIF passes of radix 16 (then 4 and/or 2), in place, natural-order
-// input.  After the last stage position p holds X[k(p)] with k the digit reversal of p.
-// perm[b] = position holding the bin that the shifted output index b must receive:
-// out[b] = X[(b - N/2) mod N]   (gr::fft::fft_vcc forward, shift=True; SURVEY C-2).
-inline std::vector<int> fft_radices(int N)
-{ // the pass sequence of k_frontend.hpp::fft_dif_lds: radix 16 while the span allows, then 4 and/or 2
-  std::vector<int> r;
-  int L = N;
-  while (L >= 16) { r.push_back(16); L /= 16; }
-  if (L >= 4) { r.push_back(4); L /= 4; }
-  if (L == 2) r.push_back(2);
-  return r;
-}
-inline std::vector<uint16_t> fft_out_perm(int N)
-{
-  std::vector<int> rad = fft_radices(N);
-  std::vector<int> pos_of_k(N);
-  for (int p = 0; p < N; p++) {
-    int span = N, weight = 1, k = 0;
-    for (int r : rad) { span /= r; int dgt = (p / span) % r; k += dgt * weight; weight *= r; }
-    pos_of_k[k] = p;
-  }
-  std::vector<uint16_t> perm(N);
-  for (int b = 0; b < N; b++) perm[b] = (uint16_t)pos_of_k[(b + N / 2) % N];
-  return perm;
-}
+// The FFT's global twiddle table: tw[t] = W_N^t = cis(-2 pi t / N), the angle in double, rounded to float (re, im interleaved).
+// The kernels of k_fft.hpp build their two-level LDS tables from it; where bin k stands after their passes is device
+// arithmetic (fft_pos_of_bin), pinned against the digit reversal over the pass radices by tests/test_fft_index_host.py.
 inline std::vector<float> fft_twiddles(int N)
 {
   std::vector<float> tw(2 * N);

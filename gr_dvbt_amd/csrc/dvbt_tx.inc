@@ -138,7 +138,7 @@ extern "C" int dvbt_tx_create(const dvbt_tx_params *p, dvbt_tx **out)
   std::unique_ptr<dvbt_tx> hold(new dvbt_tx()); dvbt_tx *const h = hold.get();   // released on every early return below
   h->p = *p; h->d = d; h->T.d = d;
   HIPCHK(h->ord.create());
-  if ((r = h->T.build_fft(d.N))) return r;
+  if ((r = h->T.fft.build(d.N))) return r;
   if ((r = h->T.build_inner(1.0f))) return r;
 
   // outer coder tables: the PRBS of one dispersal group and the RS encoder's feedback rows
@@ -174,7 +174,7 @@ extern "C" int dvbt_tx_create(const dvbt_tx_params *p, dvbt_tx **out)
   memcpy(sp.hoff, hoff, 6);
   sp.nmagic = (uint32_t)((((uint64_t)1 << 32) + d.n - 1) / d.n);
   TxTables &tt = h->tt;
-  tt.tw = h->T.tw; tt.H = h->T.H; tt.Hinv = h->T.Hinv; tt.points = h->T.points; tt.pay = h->pay; tt.pil = h->pil; tt.pref = h->pref;
+  tt.tw = h->T.fft.tw; tt.H = h->T.H; tt.Hinv = h->T.Hinv; tt.points = h->T.points; tt.pay = h->pay; tt.pil = h->pil; tt.pref = h->pref;
   tt.tps = h->tps; tt.tps_base = h->tps_base; tt.tps_sign = h->tps_sign;
 
   // buffers: RS history covers the interleaver's 2244 bytes plus the bits of a symbol not yet emitted (+ the 6 in front of them)

@@ -1,5 +1,5 @@
 // k_sounder.hpp -- the channel sounder's kernels (dvbt_sounder.inc): the echo profile and the amplitude response of the channel from the scattered pilots of
-// fft-shifted symbol rows.  The specification stands in include/dvbt_hip.h.  Needs k_frontend.hpp (fft_dif_lds, fpad, fft_pos_of_bin, FFT_THREADS, cmul).
+// fft-shifted symbol rows.  The specification stands in include/dvbt_hip.h.
 //
 // Three kernels per call:
 //   sounder_extract_kernel   one workgroup per symbol: the continual-pilot sum c_i (and c_0 of its group, formed again from the group's first row where that
@@ -14,6 +14,8 @@
 //   sounder_fold_kernel      adds the call's slabs in ascending run order into doubles, and their counts of used groups into an integer.
 // Every floating-point sum is thereby formed in an order fixed by the stream, never by the call, and there is no atomic in floating point.
 #pragma once
+#include <stdint.h>
+#include "k_fft.hpp"
 
 namespace dvbt {
 
@@ -34,7 +36,6 @@ struct SndGroup { int idx0, off0, cps0, bad; };
 
 __host__ __device__ inline size_t snd_carry_float2(int Kp) { return (size_t)Kp + 1 + 2; }        // entries, c_0, four ints
 __host__ __device__ inline size_t snd_slab_words(int M, int Kp) { return (size_t)M + Kp + 1; }   // |h|^2 sums, |E|^2 sums, the count of used groups
-__host__ __device__ inline size_t snd_lds(int M) { return (size_t)(M + M / 32 + M / 128 + 129) * 8; }
 
 // index, offset and cp_start of the call's symbol at stream position s >= pos0
 __device__ __forceinline__ void snd_meta(const SndArgs &a, long long s, int &x, int &o, int &c)
@@ -178,6 +179,7 @@ __global__ __launch_bounds__(SND_EXTRACT_THREADS) void sounder_extract_kernel(Sn
 //   open_out  where a run that this call leaves open is stored (another buffer than open_in)
 //   slabs     [gridDim.x][M + Kp + 1]: the closed runs of this launch
 // NB = M / FFT_THREADS bins and NR = ceil(Kp / FFT_THREADS) carriers per thread.  Only the accumulators live across the transform (see spectrum_kernel).
+// Dynamic LDS: the FFT's workspace at M points (fft_lds_bytes(M)).
 template <int NB, int NR>
 __global__ __launch_bounds__(FFT_THREADS, 4) void sounder_profile_kernel(SndArgs a, const float2 *__restrict__ ebuf, long long g_base, long long r_first,
                                                                          long long ga, long long gb, const float *__restrict__ win,
@@ -185,12 +187,10 @@ __global__ __launch_bounds__(FFT_THREADS, 4) void sounder_profile_kernel(SndArgs
                                                                          float *__restrict__ open_out, float *__restrict__ slabs)
 {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-  float2 *x = reinterpret_cast<float2 *>(smem_raw);
   const int M = a.M, Kp = a.Kp, tid = threadIdx.x;
-  const int nc = M / 128;
-  float2 *tw_c = x + (M + M / 32), *tw_f = tw_c + nc;
-  for (int i = tid; i < nc; i += FFT_THREADS) tw_c[i] = twM[i * 128];
-  if (tid < 128) tw_f[tid] = twM[tid];
+  const FftWork fw = fft_work(smem_raw, M);
+  float2 *const x = fw.x;
+  fft_work_fill(fw, M, twM, tid);
 
   const long long r = r_first + blockIdx.x;
   const long long ka = ga > r * SND_RUN ? ga : r * SND_RUN, kb = gb < (r + 1) * SND_RUN ? gb : (r + 1) * SND_RUN;
@@ -229,7 +229,7 @@ __global__ __launch_bounds__(FFT_THREADS, 4) void sounder_profile_kernel(SndArgs
       x[fpad(b)] = v;
     }
     __syncthreads();
-    fft_dif_lds(x, M, tw_c, tw_f, tid);            // ends behind a barrier
+    fft_dif_lds(fw, M, tid);                       // ends behind a barrier
     int u = tid, Mk = M;
     asm volatile("" : "+v"(u), "+s"(Mk));
 #pragma unroll

@@ -1,5 +1,5 @@
 // k_spectrum.hpp -- the spectrum analyser's kernels (dvbt_spectrum.inc): an averaged, windowed periodogram (Welch) and amplitude statistics of a complex64
-// stream, accumulated in one pass.  Needs k_frontend.hpp (fft_dif_lds, fpad, fft_pos_of_bin, FFT_THREADS).
+// stream, accumulated in one pass.
 //
 // Segment k is the stream's samples [k hop, k hop + N).  Everything that is summed in floating point is summed in an order fixed by the STREAM, never by
 // the call: SPEC_GROUP consecutive segments, [32 g, 32 g + 32) in the stream's numbering, are one group, summed by one workgroup in segment order into
@@ -12,6 +12,7 @@
 // Statistics cover the first `hop` samples of every complete segment, i.e. the samples [0, S hop) once each.  |x|^2 = fmaf(re, re, im im); its bits without
 // the sign (only a NaN can carry one) shifted right by 20 are the histogram bin: 8 bins per octave over the whole float range, 2040.. = inf and NaN.
 #pragma once
+#include "k_fft.hpp"
 
 namespace dvbt {
 
@@ -26,9 +27,8 @@ struct SpecArgs {
   long long hbase;                                 // stream index of the carried history's first sample (s0 hop)
 };
 
-// the dynamic LDS of spectrum_kernel: dvbt_fft's image and twiddles, then the histogram's counters
-__host__ __device__ inline size_t spec_fft_lds(int N) { return (size_t)(N + N / 32 + N / 128 + 129) * 8; }
-__host__ __device__ inline size_t spec_lds(int N) { return spec_fft_lds(N) + SPEC_HIST_BINS * sizeof(unsigned); }
+// the dynamic LDS of spectrum_kernel: the FFT's workspace, then the histogram's counters
+inline size_t spec_lds(int N) { return fft_lds_bytes(N) + SPEC_HIST_BINS * sizeof(unsigned); }
 
 // One workgroup per group of the launch: group g_first + blockIdx.x.  NB = max(N / FFT_THREADS, 1) accumulators per thread.
 //   in        the call's input; hist: the carried samples [hbase, pos0)
@@ -50,13 +50,11 @@ __global__ __launch_bounds__(FFT_THREADS, 4) void spectrum_kernel(const float2 *
   __shared__ double s_w[SPEC_WAVES];
   __shared__ double s_gsum;
   __shared__ unsigned s_peak;
-  float2 *x = reinterpret_cast<float2 *>(smem_raw);
   const int N = a.N, hop = a.hop, tid = threadIdx.x;
-  const int nc = N >= 128 ? N / 128 : 1;
-  float2 *tw_c = x + (N + N / 32), *tw_f = tw_c + nc;
-  unsigned *cnt = reinterpret_cast<unsigned *>(smem_raw + spec_fft_lds(N));
-  for (int i = tid; i < nc; i += FFT_THREADS) tw_c[i] = tw[i * 128 < N ? i * 128 : 0];
-  if (tid < 128 && tid < N) tw_f[tid] = tw[tid];
+  const FftWork fw = fft_work(smem_raw, N);
+  float2 *const x = fw.x;
+  unsigned *cnt = reinterpret_cast<unsigned *>(fw.end);
+  fft_work_fill(fw, N, tw, tid);
   for (int i = tid; i < SPEC_HIST_BINS; i += FFT_THREADS) cnt[i] = 0u;
 
   const long long g = g_first + blockIdx.x;
@@ -105,14 +103,14 @@ __global__ __launch_bounds__(FFT_THREADS, 4) void spectrum_kernel(const float2 *
       for (int w = 0; w < SPEC_WAVES; w++) s += s_w[w];
       s_gsum = s;
     }
-    fft_dif_lds(x, N, tw_c, tw_f, tid);            // ends behind a barrier
+    fft_dif_lds(fw, N, tid);                       // ends behind a barrier
     int u = tid, Nk = N;
     asm volatile("" : "+v"(u), "+s"(Nk));
 #pragma unroll
     for (int j = 0; j < NB; j++) {
       const int b = u + j * FFT_THREADS;
       if (b < Nk) {
-        const float2 X = x[fpad(fft_pos_of_bin((b + (Nk >> 1)) & (Nk - 1), Nk))];   // shifted, as dvbt_fft: bin b is X[(b - N/2) mod N]
+        const float2 X = fft_shifted_bin(fw, b, Nk);   // as dvbt_fft: bin b is X[(b - N/2) mod N]
         acc[j] = acc[j] + (X.x * X.x + X.y * X.y);
       }
     }

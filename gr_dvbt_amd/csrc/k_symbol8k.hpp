@@ -139,7 +139,7 @@ __device__ __forceinline__ void s8_bfly4(v2f a0, v2f a1, v2f a2, v2f a3, v2f &y0
   const v2f s02 = a0 + a2, d02 = a0 - a2, s13 = a1 + a3, d13 = a1 - a3;
   y0 = s02 + s13; y2 = s02 - s13; y1 = s8_add_mi(d02, d13); y3 = s8_add_pi(d02, d13);
 }
-// 16-point forward DFT in registers, as dft16() (k_frontend.hpp): 64 adds + 17 instructions of fixed twiddles
+// 16-point forward DFT in registers, as dft16() (k_fft.hpp): 64 adds + 17 instructions of fixed twiddles
 __device__ __forceinline__ void s8_dft16(v2f (&a)[16], const S8Roots &R)
 {
   v2f t[16];

@@ -10,7 +10,8 @@
 // and the encoder's state is the 6 bits in front of them (inner_coder_impl.cc:33-48).  Every symbol starts at puncture phase 0
 // because ibits is a whole number of puncture periods.  Reference chain: apps/dvbt_tx_demo*.grc.
 #pragma once
-#include "k_frontend.hpp"
+#include <stdint.h>
+#include "k_fft.hpp"
 
 namespace dvbt {
 
@@ -95,9 +96,8 @@ struct TxTables {
   const float *tps_sign;      // [4][68] (-1)^(tps_f[1] + .. + tps_f[s])
 };
 
-__device__ __forceinline__ float2 cswap(float2 a) { return make_float2(a.y, a.x); }
-
-inline size_t tx_symbol_lds_bytes(int N, int payload) { return (size_t)(N + N / 32 + N / 128 + 128) * 8 + (size_t)payload + 16; }
+// the dynamic LDS of tx_symbol_kernel: the FFT's workspace, then the carrier labels
+inline size_t tx_symbol_lds_bytes(int N, int payload) { return fft_lds_bytes(N) + (size_t)payload + 16; }
 
 // the inverse DFT through the forward one: swap(FFT(swap(X))) = IFFT(X) unnormalised (swap(z) = i conj(z)), exact in the swaps.
 template <int N>
@@ -105,16 +105,15 @@ __global__ __launch_bounds__(FFT_THREADS) void tx_symbol_kernel(const uint8_t *_
                                                                 float2 *__restrict__ out, float2 *__restrict__ carriers)
 {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-  float2 *x = reinterpret_cast<float2 *>(smem_raw);
-  float2 *tw_c = x + (N + N / 32), *tw_f = tw_c + N / 128;
-  uint8_t *word = reinterpret_cast<uint8_t *>(tw_f + 128);     // [payload] symbol-interleaved carrier labels
+  const FftWork w = fft_work(smem_raw, N);
+  float2 *const x = w.x;
+  uint8_t *word = w.end;                                        // [payload] symbol-interleaved carrier labels
   uint8_t *il = smem_raw;                                       // the symbol's interleaved bytes (aliases x until the carriers are placed)
   const int tid = threadIdx.x, ls = blockIdx.x;
   if (ls >= p.nsym) return;
   const long long sg = p.S0 + ls;
   const int si = (int)(sg % 68), fi = (int)((sg / 68) & 3);
-  for (int i = tid; i < N / 128; i += FFT_THREADS) tw_c[i] = T.tw[i * 128];
-  if (tid < 128) tw_f[tid] = T.tw[tid];
+  fft_work_fill(w, N, T.tw, tid);
 
   // gather: interleaved bytes gb0 .. last, gb0 one byte in front of the first info bit (the encoder's 6-bit history)
   const long long Bg = sg * p.ibits;
@@ -176,7 +175,7 @@ __global__ __launch_bounds__(FFT_THREADS) void tx_symbol_kernel(const uint8_t *_
     __syncthreads();                                            // the FFT's first pass overwrites x in place
   }
 
-  fft_dif_lds(x, N, tw_c, tw_f, tid);
+  fft_dif_lds(w, N, tid);
 
   // cyclic prefix first, then the body; time sample t = swap(FFT output bin t)
   const int cp = p.cp;
@@ -187,25 +186,6 @@ __global__ __launch_bounds__(FFT_THREADS) void tx_symbol_kernel(const uint8_t *_
     const float2 v = x[fpad(fft_pos_of_bin(t, N))];
     o[j] = make_float2(sc * v.y, sc * v.x);
   }
-}
-
-// the inverse shifted FFT alone (dvbt_fft with forward = 0: gr::fft::fft_vcc(reverse, shift=True) of the TX flowgraphs):
-// out[t] = sum_k in[(k + N/2) mod N] e^{+2 pi i t k / N}, unnormalised
-__global__ __launch_bounds__(FFT_THREADS) void ifft_items_kernel(const float2 *__restrict__ in, int N, int nitems,
-                                                                 const float2 *__restrict__ tw, float2 *__restrict__ out)
-{
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-  float2 *x = reinterpret_cast<float2 *>(smem_raw);
-  const int s = blockIdx.x, tid = threadIdx.x;
-  if (s >= nitems) return;
-  const int nc = N >= 128 ? N / 128 : 1;
-  float2 *tw_c = x + (N + N / 32), *tw_f = tw_c + nc;
-  for (int i = tid; i < nc; i += FFT_THREADS) tw_c[i] = tw[i * 128 < N ? i * 128 : 0];
-  if (tid < 128 && tid < N) tw_f[tid] = tw[tid];
-  for (int b = tid; b < N; b += FFT_THREADS) x[fpad((b + (N >> 1)) & (N - 1))] = cswap(in[(size_t)s * N + b]);
-  __syncthreads();
-  fft_dif_lds(x, N, tw_c, tw_f, tid);
-  for (int t = tid; t < N; t += FFT_THREADS) out[(size_t)s * N + t] = cswap(x[fpad(fft_pos_of_bin(t, N))]);
 }
 
 }  // namespace dvbt
