@@ -1,4 +1,7 @@
-/* bit_inner_interleaver_impl.cc -- gr::dvbt::bit_inner_interleaver on libdvbt_hip (replaces lib/bit_inner_interleaver_impl.cc).  Non-hierarchical only: one input (the reference's io_signature(1, 2)); hierarchy != NH is refused (include/dvbt_hip.h T5). */
+/* bit_inner_interleaver_impl.cc -- gr::dvbt::bit_inner_interleaver on libdvbt_hip (replaces lib/bit_inner_interleaver_impl.cc).  
+ * Non-hierarchical only: hierarchy != NH is refused (include/dvbt_hip.h T5), so the block declares ONE input where the reference declares (1, 2): the reference's
+ * second input carries the low-priority stream of a hierarchical transmission and is never read otherwise (:127-176), and its forecast asks for as much of it
+ * as of the first.  A flowgraph that connects a second input is refused when it is built, not left waiting for items nobody reads. */
 #include "bit_inner_interleaver_impl.h"
 
 namespace gr {

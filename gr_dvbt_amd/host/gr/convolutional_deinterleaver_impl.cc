@@ -13,7 +13,8 @@ namespace gr {
     static dvbt_convolutional_deinterleaver_params cdi_params(int blocks, int I, int M)
     { dvbt_convolutional_deinterleaver_params p = { blocks, I, M }; return p; }
 
-    /* io signatures, rate and output multiple: lib/convolutional_deinterleaver_impl.cc:55-61 */
+    /* io signatures and output multiple: lib/convolutional_deinterleaver_impl.cc:55-61.  The rate is items out per byte in, 1 / (I * blocks); the reference's
+     * expression (:60) is 1.0 / I * blocks = blocks / I (11.3) */
     convolutional_deinterleaver_impl::convolutional_deinterleaver_impl(int blocks, int I, int M)
       : block("convolutional_deinterleaver", io_signature::make(1, 1, sizeof(unsigned char)), io_signature::make(1, 1, sizeof(unsigned char) * I * blocks)),
         DVBT_HIP_CORE_INIT(convolutional_deinterleaver, cdi_params(blocks, I, M))

@@ -8,9 +8,14 @@
  *                      back into stream tags, consume_each(n_consumed), return the items produced
  * Tag keys: SURVEY Appendix D ("sync_start", "superframe_start", "symbol_index", values pmt longs).
  *
- * GNU Radio 3.7 is absent from the authoring container: this directory is built only where find_package(Gnuradio) succeeds
- * (CMakeLists.txt); tests/test_gr_shells.py checks the sources against the reference's public headers with g++ -fsyntax-only and
- * throw-away declarations of the few GNU Radio names used (tests/gr_syntax/, declarations only -- nothing is executed or linked).
+ * A block with a second stream (bit_inner_deinterleaver's low-priority output) passes its own call to core::work_with; the marshalling is the same.
+ *
+ * GNU Radio 3.7 is absent from the authoring container: this directory is built for a flowgraph only where find_package(Gnuradio) succeeds
+ * (CMakeLists.txt).  The shells are nevertheless compiled, linked and RUN without it: oracle/Makefile (target `ref`) builds all of them against the
+ * behaving stand-in gr::block of oracle/ref_standin/ into oracle/_ref/libdvbt_shells_hip.so, driven by oracle/ref_driver.cc like the reference's own
+ * blocks; tests/test_gpu_gr_shells.py holds them to the reference's recorded calls, outputs, tags and scheduler hints, tests/test_hip_shell_host.py runs
+ * core<H, P> over recording fakes of the four C-ABI functions on the CPU, tests/test_gr_shells_link.py links every shell against libdvbt_hip.so.
+ * tests/test_gr_shells.py remains the syntax check against the declarations of tests/gr_syntax/.
  */
 #ifndef INCLUDED_DVBT_HIP_SHELL_H
 #define INCLUDED_DVBT_HIP_SHELL_H
@@ -62,6 +67,13 @@ namespace gr {
         /* one general_work call of block b; returns the items produced on output 0 */
         int work(gr::block *b, int noutput_items, int ninput_items, const void *in, void *out)
         {
+          return work_with(b, ninput_items, call_work(d_work, d_h, noutput_items, ninput_items, in, out));
+        }
+
+        /* the same around any call of the library: call(sb) gets the sideband with the input window's tags and returns the items produced */
+        template <class F>
+        int work_with(gr::block *b, int ninput_items, F call)
+        {
           const uint64_t r0 = b->nitems_read(0);
           std::vector<tag_t> tags;
           b->get_tags_in_range(tags, 0, r0, r0 + (uint64_t)ninput_items);
@@ -77,7 +89,7 @@ namespace gr {
           dvbt_sideband sb;
           sb.in_tags = d_in.empty() ? 0 : &d_in[0]; sb.n_in_tags = (int)d_in.size();
           sb.out_tags = &d_out[0]; sb.out_cap = (int)d_out.size(); sb.n_out_tags = 0; sb.n_consumed = 0;
-          const int produced = d_work(d_h, noutput_items, ninput_items, in, out, &sb);
+          const int produced = call(&sb);
           if (produced < 0) throw std::runtime_error(std::string("libdvbt_hip: ") + dvbt_last_error());
           const uint64_t w0 = b->nitems_written(0);
           for (int i = 0; i < sb.n_out_tags && i < sb.out_cap; i++)
@@ -89,6 +101,11 @@ namespace gr {
         H *handle() const { return d_h; }
 
       private:
+        struct call_work {
+          work_fn w; H *h; int noutput_items, ninput_items; const void *in; void *out;
+          call_work(work_fn w_, H *h_, int no, int ni, const void *in_, void *out_) : w(w_), h(h_), noutput_items(no), ninput_items(ni), in(in_), out(out_) {}
+          int operator()(dvbt_sideband *sb) const { return w(h, noutput_items, ninput_items, in, out, sb); }
+        };
         core(const core &); core &operator=(const core &);
         H *d_h; forecast_fn d_forecast; work_fn d_work; destroy_fn d_destroy;
         std::vector<dvbt_tag> d_in, d_out;

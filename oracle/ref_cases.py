@@ -2,7 +2,8 @@
 tests/test_oracle_ref_blocks.py (oracle against the running reference, or against its recordings), tests/golden/make_golden.py --ref-blocks (the recordings)
 and tests/test_gpu_ref_blocks.py (the GPU entries against the recordings).
 
-Every case is a dict of plain parameters with a seed; make_input(po, case) regenerates its input from them.  run_ref(case, inp) drives the reference block,
+Every case is a dict of plain parameters with a seed; make_input(po, case) regenerates its input from them.  run_ref(case, inp) drives the reference block
+(run_ref(case, inp, which="hip"): the project's GNU Radio shell of the same name, on a GPU; tests/test_gpu_gr_shells.py replays the recorded calls instead),
 run_oracle(po, case, inp) the oracle's stage function in the same calls; both return
     {"out": [uint8 array per output port], "log": [[noutput_items, returned, consumed], ...] per general_work call, "tags": [[port, offset, key, value], ...]}
 (the oracle's "log" / "tags" are None where the oracle has no counterpart of the block's scheduling: then only the reference's are recorded).
@@ -23,6 +24,8 @@ import hashlib
 import numpy as np
 
 from . import refblocks as rb
+
+_refblocks = rb
 
 P2K, P8K = 1512, 6048
 RS_ARGS = [2, 8, 0x11d, 255, 239, 8, 51, 8]
@@ -309,7 +312,7 @@ def make_input(po, case):
     raise KeyError(k)
 
 
-def refsig_payload(case, inp):
+def refsig_payload(case, inp, which="ref"):
     """reference_signals' input for the case: the payload cells of the generator's symbols inp["F"], read where THE REFERENCE BLOCK puts payload -- found by a run
     of its own over cells that carry their own number -- so that its output must be the generator's symbols, pilots and TPS included, bit for bit"""
     c = inp["cfg"]
@@ -317,7 +320,7 @@ def refsig_payload(case, inp):
     mark = np.zeros((n, P), np.complex64)
     mark.real = 1000 + np.arange(P)
     mark.imag = 7
-    r = _refsig_block(case, c).stream([mark.reshape(-1).view(np.uint8)], n, [n])
+    r = _refsig_block(case, c, which).stream([mark.reshape(-1).view(np.uint8)], n, [n])
     out = r["out"][0].view(np.complex64).reshape(n, N)
     pos = np.zeros((n, P), np.int64)
     for s in range(n):
@@ -327,9 +330,9 @@ def refsig_payload(case, inp):
     return np.take_along_axis(inp["F"], pos, axis=1)
 
 
-def _refsig_block(case, c):
+def _refsig_block(case, c, which="ref"):
     cell = case.get("cell", (0, 0))
-    return rb.Block("reference_signals", [8, c.payload, c.N, case["const"], 0, case["rate"], case["rate"], 0, case["mode"], cell[0], cell[1]])
+    return rb.Block("reference_signals", [8, c.payload, c.N, case["const"], 0, case["rate"], case["rate"], 0, case["mode"], cell[0], cell[1]], which=which)
 
 
 # ------------------------------------------------------------------------------------------------------------------------------------------
@@ -355,8 +358,14 @@ def _mask_lp(case, a):
     return a
 
 
-def run_ref(case, inp):
+def run_ref(case, inp, which="ref"):
+    """drive the case's block(s) of library `which` (refblocks.lib: "ref" the reference's own blocks, "hip" the project's GNU Radio shells, which need a GPU)"""
     k = case["kind"]
+
+    class rb:                                                                          # refblocks.Block of the library asked for
+        @staticmethod
+        def Block(*a, **kw):
+            return _refblocks.Block(*a, which=which, **kw)
     if k == "sym":
         P = P8K if case["mode"] else P2K
         b = rb.Block("symbol_inner_interleaver", [P, case["mode"], case["direction"]])
@@ -403,6 +412,7 @@ def run_ref(case, inp):
         r["log_big"] = big["log"]
         n = min(len(r["out"][0]), len(big["out"][0]))
         r["big_equals_small"] = bool(n > 0 and (r["out"][0][:n] == big["out"][0][:n]).all())
+        r["hints"]["forecast"] = sorted(r["hints"]["forecast"] + big["hints"]["forecast"])
         return r
     if k == "coder":
         b = rb.Block("inner_coder", [1, P2K, case["const"], case["hier"], case["rate"]])
@@ -451,11 +461,12 @@ def run_ref(case, inp):
                 kept_bytes.append(outs[4][pos:pos + cons])
             pos += cons
         outs[4] = np.concatenate(kept_bytes + [outs[4][pos:]])
-        return {"out": outs, "log": [[len(x), 0, 0] for x in outs], "tags": eq["tags"][:1] + vit["tags"]}
+        return {"out": outs, "log": [[len(x), 0, 0] for x in outs], "tags": eq["tags"][:1] + vit["tags"],
+                "hints": [r["hints"] for r in (eq, demap, symd, bitd, vit, dei, rs, ts)]}
     if k == "refsig":
         c = inp["cfg"]
-        pay = refsig_payload(case, inp)
-        return _refsig_block(case, c).stream([pay.reshape(-1).view(np.uint8)], inp["nitems"], case["calls"])
+        pay = refsig_payload(case, inp, which)
+        return _refsig_block(case, c, which).stream([pay.reshape(-1).view(np.uint8)], inp["nitems"], case["calls"])
     raise KeyError(k)
 
 
@@ -673,6 +684,11 @@ def record(res):
         if key in res:
             r[key] = rle(res[key]) if key == "log_big" else res[key]
     return r
+
+
+def sched(res):
+    """what the block(s) of a run asked of the scheduler (refblocks.Block.hints; a list, block by block, for the chain cases): the recording keeps it as its key `sched`"""
+    return res["hints"]
 
 
 def kept(case, res):

@@ -7,6 +7,10 @@
  * the items consumed per input and the output tags.  The scheduler's part that remains -- item
  * counters advancing by what was consumed and produced -- is done here, behind each call.
  * The stand-in headers under ref_standin/ supply gr::block (see block.h there).
+ *
+ * With REF_DRIVER_HIP_SHELLS defined the same driver is compiled with the block sources of gr_dvbt_amd/host/gr in place of the reference's
+ * (oracle/_ref/libdvbt_shells_hip.so, tests/test_gpu_gr_shells.py): the block classes are then the HIP shells.  Everything that exists only for them
+ * stands under that one switch; without it this file is what it was.
  */
 #include <dvbt/bit_inner_deinterleaver.h>
 #include <dvbt/bit_inner_interleaver.h>
@@ -23,6 +27,21 @@
 #include <dvbt/reference_signals.h>
 #include <dvbt/symbol_inner_interleaver.h>
 #include <dvbt/viterbi_decoder.h>
+
+#ifdef REF_DRIVER_HIP_SHELLS
+#include <dvbt/ofdm_sym_acquisition.h>
+#include <dvbt/fft_hip.h>
+#include <dvbt/rx_hip.h>
+#include <gnuradio/block_detail.h>
+#include <stdexcept>
+/* a shell throws std::runtime_error where the library refuses; nothing may throw through extern "C": the message is kept, the call returns `ret` */
+static thread_local std::string si_error;
+#define SHELL_TRY try {
+#define SHELL_CATCH(ret) } catch (const std::exception &e) { si_error = e.what(); return ret; }
+#else
+#define SHELL_TRY
+#define SHELL_CATCH(ret)
+#endif
 
 #include <algorithm>
 #include <fcntl.h>
@@ -63,6 +82,7 @@ void *refblk_make(const char *name, const int *a, int na, float g)
   std::string n(name);
   gr::block_sptr b;
   quiet q;
+  SHELL_TRY
   if (n == "demod_reference_signals" && na == 11)
     b = demod_reference_signals::make(a[0], a[1], a[2], en<dvbt_constellation_t>(a[3]), en<dvbt_hierarchy_t>(a[4]), en<dvbt_code_rate_t>(a[5]),
                                       en<dvbt_code_rate_t>(a[6]), en<dvbt_guard_interval_t>(a[7]), en<dvbt_transmission_mode_t>(a[8]), a[9], a[10]);
@@ -95,6 +115,20 @@ void *refblk_make(const char *name, const int *a, int na, float g)
     b = energy_descramble::make(a[0]);
   else if (n == "energy_dispersal" && na == 1)
     b = energy_dispersal::make(a[0]);
+#ifdef REF_DRIVER_HIP_SHELLS
+  else if (n == "ofdm_sym_acquisition" && na == 4)
+    b = ofdm_sym_acquisition::make(a[0], a[1], a[2], a[3], g);
+  else if (n == "fft_hip" && na == 3)
+    b = fft_hip::make(a[0], a[1] != 0, a[2] != 0);
+  else if (n == "rx_hip" && na == 8)
+    b = rx_hip::make(en<dvbt_constellation_t>(a[0]), en<dvbt_hierarchy_t>(a[1]), en<dvbt_code_rate_t>(a[2]), en<dvbt_guard_interval_t>(a[3]),
+                     en<dvbt_transmission_mode_t>(a[4]), g, a[5], a[6], a[7] != 0);
+  else
+    si_error = "no block " + n + " with " + std::to_string(na) + " integer arguments";
+  if (b)
+    b->si_detail = gr::block_detail_sptr(new gr::block_detail(b->input_signature()->max_streams()));
+#endif
+  SHELL_CATCH(0)
   if (!b)
     return 0;
   handle *h = new handle;
@@ -150,7 +184,9 @@ int refblk_work(void *hv, int noutput, const int *ninput_items, const void *cons
   int r;
   {
     quiet q;
+    SHELL_TRY
     r = b.general_work(noutput, ni, iv, ov);
+    SHELL_CATCH(-1000)
   }
   for (int i = 0; i < nin; i++) {
     consumed[i] = b.si_consumed[i];
@@ -176,5 +212,25 @@ int refblk_output_tag(void *hv, int i, int *port, unsigned long long *offset, ch
   *value = pmt::to_long(t.value);
   return 0;
 }
+
+#ifdef REF_DRIVER_HIP_SHELLS
+/* what() of the last exception that refblk_make (returned 0) or refblk_work (returned -1000) caught on this thread */
+const char *refblk_last_error(void) { return si_error.c_str(); }
+int refblk_tag_propagation_policy(void *hv) { return (int)static_cast<handle *>(hv)->blk->tag_propagation_policy(); }
+/* streams the block declared: output = 0 / 1 as in refblk_itemsize, which = 0 the fewest, 1 the most */
+int refblk_nstreams(void *hv, int output, int which)
+{
+  gr::block &b = *static_cast<handle *>(hv)->blk;
+  gr::io_signature::sptr s = output ? b.output_signature() : b.input_signature();
+  return which ? s->max_streams() : s->min_streams();
+}
+/* the scheduler's view of input `input`: whether the block upstream has finished, and the items that wait unread */
+void refblk_set_input_state(void *hv, int input, int done, int items)
+{
+  gr::buffer_reader_sptr r = static_cast<handle *>(hv)->blk->detail()->input(input);
+  r->si_done = done != 0;
+  r->si_items = items;
+}
+#endif
 
 }

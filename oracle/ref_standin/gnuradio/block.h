@@ -4,6 +4,8 @@
  *   - one output tag list that add_item_tag appends to
  *   - item counters nitems_read / nitems_written, advanced by whoever drives the block
  *   - consume / consume_each record what the block took in the current call
+ *   - the tag propagation policy a block asks for is kept for the driver to read
+ *   - detail() hands out what the driver set up (gnuradio/block_detail.h): null until it did, as for a block outside a flowgraph
  * The members named si_* are the driver's side (oracle/ref_driver.cc). */
 #ifndef REF_STANDIN_GR_BLOCK_H
 #define REF_STANDIN_GR_BLOCK_H
@@ -12,6 +14,9 @@
 #include <pmt/pmt.h>
 
 namespace gr {
+
+  class block_detail;
+  typedef std::shared_ptr<block_detail> block_detail_sptr;
 
   struct tag_t {
     uint64_t offset;
@@ -22,6 +27,8 @@ namespace gr {
   class block {
   public:
     enum { WORK_CALLED_PRODUCE = -2, WORK_DONE = -1 };
+    /* what the scheduler does with the tags of the input items: nothing / every input's to every output / input i's to output i */
+    enum tag_propagation_policy_t { TPP_DONT = 0, TPP_ALL_TO_ALL = 1, TPP_ONE_TO_ONE = 2 };
 
     virtual ~block() {}
 
@@ -48,6 +55,10 @@ namespace gr {
     int output_multiple() const { return si_output_multiple; }
     void set_alignment(int m) { si_alignment = m; }
     int alignment() const { return si_alignment; }
+    void set_tag_propagation_policy(tag_propagation_policy_t p) { si_tpp = p; }
+    tag_propagation_policy_t tag_propagation_policy() const { return si_tpp; }
+    block_detail_sptr detail() const { return si_detail; }
+    virtual bool stop() { return true; }
     bool is_unaligned() const { return false; }   /* the stand-in VOLK kernel is the same either way */
 
     uint64_t nitems_read(unsigned int which_input) { return which_input < si_nread.size() ? si_nread[which_input] : 0; }
@@ -85,6 +96,8 @@ namespace gr {
     io_signature::sptr si_in_sig, si_out_sig;
     double si_relative_rate = 1.0;
     int si_output_multiple = 1, si_alignment = 1;
+    tag_propagation_policy_t si_tpp = TPP_ALL_TO_ALL;   /* GNU Radio's default */
+    block_detail_sptr si_detail;
     std::vector<uint64_t> si_nread, si_nwritten;
     std::vector<int> si_consumed;
     std::vector<std::vector<tag_t> > si_in_tags;   /* kept sorted by offset, in the order given within one offset */

@@ -23,5 +23,7 @@ namespace pmt {
     if (!a || !b) return a == b;
     return a->is_symbol == b->is_symbol && (a->is_symbol ? a->name == b->name : a->number == b->number);
   }
+  /* eqv: eq, and numbers of the same type with the same value; symbols and longs are all there is here, so the two coincide */
+  inline bool eqv(const pmt_t &a, const pmt_t &b) { return eq(a, b); }
 }
 #endif

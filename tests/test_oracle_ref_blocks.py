@@ -48,7 +48,10 @@ def check_case(po, golden, name):
     ref = None
     if LIVE:
         ref = rc.run_ref(case, inp)
-        assert rc.record(ref) == {k: v for k, v in want.items() if k != "kept"}, "the recording is not what the reference block produces"
+        assert rc.record(ref) == {k: v for k, v in want.items() if k not in ("kept", "sched")}, "the recording is not what the reference block produces"
+        # what the block asks of the scheduler -- output multiple, relative rate, item sizes, forecast at every noutput_items of its calls -- as recorded for
+        # tests/test_gpu_gr_shells.py (the project's GNU Radio shells are held to it there)
+        assert rc.sched(ref) == want["sched"], "the recorded scheduler hints are not the reference block's"
         for j, o in enumerate(ora["out"]):
             _same(o, ref["out"][j], "%s output %d, oracle against reference" % (name, j))
         for key in ("log", "tags"):
@@ -72,6 +75,12 @@ def _names(*kinds):
 
 def test_every_case_is_recorded(golden):
     assert sorted(golden[0]["cases"]) == sorted(rc.CASES)
+    for name, want in golden[0]["cases"].items():                                      # ... with its scheduler hints, forecast at every call size of its log
+        for h in want["sched"] if isinstance(want["sched"], list) else [want["sched"]]:
+            assert sorted(h) == ["forecast", "in_itemsize", "out_itemsize", "output_multiple", "relative_rate"], name
+        if rc.CASES[name]["kind"] != "chain":
+            sizes = {e[0] for key in ("log", "log_big") for e in rc.unrle(want.get(key, []))}
+            assert {f[0] for f in want["sched"]["forecast"]} == sizes, name
 
 
 @pytest.mark.parametrize("name", _names("sym"))
