@@ -1546,6 +1546,160 @@ class Constellation(_Handle):
         return c
 
 
+TS_PACKET, TS_PIDS, TS_TILE = 188, 8192, 1024
+TS_NULL_PID = 0x1FFF
+TS_PCR_HZ = 27e6
+TS_PID_FIELDS = ("pid", "packets", "pusi", "scrambled", "payload", "adaptation", "discontinuity", "random_access", "pcr", "tei", "duplicates", "cc_errors",
+                 "first", "last", "pcr_pairs", "pcr_discontinuity_signalled", "pcr_over_100ms", "pcr_over_40ms", "sum_dt", "sum_dp", "min_dt", "max_dt",
+                 "max_dp")
+TS_PID_DTYPE = np.dtype([(f, np.int64) for f in TS_PID_FIELDS])
+TS_TOTALS = ("packets_pushed", "sync_errors", "transport_errors", "afc_reserved", "af_length_errors", "pids_seen")
+
+
+class TsParams(C.Structure):
+    _fields_ = [("device", C.c_int), ("max_packets", C.c_int)]
+
+
+class TsResult(C.Structure):
+    _fields_ = [(f, C.c_longlong) for f in TS_TOTALS]
+
+
+@_typed_once
+def _ts_lib(L):
+    L.dvbt_ts_create.argtypes = [C.POINTER(TsParams), C.POINTER(C.c_void_p)]
+    L.dvbt_ts_push.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+    L.dvbt_ts_push_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+    L.dvbt_ts_read.argtypes = [C.c_void_p, C.POINTER(TsResult), C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
+    L.dvbt_ts_reset.argtypes = [C.c_void_p]
+    L.dvbt_ts_destroy.argtypes = [C.c_void_p]
+
+
+def ts_align(data):
+    """the first offset at which five consecutive packets start with 0x47 (a file from elsewhere need not start on a packet); raises if there is none"""
+    d = np.frombuffer(data, np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else np.ascontiguousarray(data, dtype=np.uint8).reshape(-1)
+    n = len(d) - 4 * TS_PACKET
+    if n > 0:
+        ok = d[:n] == 0x47
+        for k in range(1, 5):
+            ok &= d[k * TS_PACKET:k * TS_PACKET + n] == 0x47
+        hit = np.flatnonzero(ok)
+        if len(hit):
+            return int(hit[0])
+    raise DvbtError("no five consecutive packets that start with 0x47")
+
+
+class TsReading:
+    """What TsAnalyser.read() returns: the totals of dvbt_ts_result and `pids`, the entries (TS_PID_DTYPE) of the PIDs seen, ascending.  The figures are
+    float64 on the host from these integers and need no GPU; each is nan where its inputs are empty."""
+
+    def __init__(self, totals, pids):
+        for f in TS_TOTALS:
+            setattr(self, f, int(totals[f] if isinstance(totals, dict) else getattr(totals, f)))
+        self.pids = np.asarray(pids, dtype=TS_PID_DTYPE).reshape(-1)
+
+    def entry(self, pid):
+        """the entry of one PID (all zero, first = min_dt = -1, where it was never seen)"""
+        hit = np.flatnonzero(self.pids["pid"] == pid)
+        if len(hit):
+            return self.pids[hit[0]]
+        e = np.zeros((), TS_PID_DTYPE)
+        e["pid"], e["first"], e["min_dt"] = pid, -1, -1
+        return e
+
+    @property
+    def members(self):
+        return int(self.pids["packets"].sum())
+
+    def share(self, pid):
+        """the PID's members over all members"""
+        return float(self.entry(pid)["packets"]) / self.members if self.members else float("nan")
+
+    @property
+    def null_share(self):
+        return self.share(TS_NULL_PID)
+
+    def ts_bitrate(self, pid):
+        """bits per second of the whole stream by the PCRs of `pid`: sum_dp 188 8 27e6 / sum_dt"""
+        e = self.entry(pid)
+        return float(e["sum_dp"]) * (TS_PACKET * 8) * TS_PCR_HZ / float(e["sum_dt"]) if e["sum_dt"] > 0 else float("nan")
+
+    def pid_bitrate(self, pid, ts_bitrate):
+        """bits per second of one PID, given the stream's (ts_bitrate(pcr_pid)): its share of all packets pushed"""
+        return float(self.entry(pid)["packets"]) / self.packets_pushed * float(ts_bitrate) if self.packets_pushed else float("nan")
+
+    def pcr_interval_ms(self, pid):
+        """(min, mean, max) of the PID's PCR intervals that entered pcr_pairs"""
+        e = self.entry(pid)
+        if e["pcr_pairs"] <= 0:
+            return float("nan"), float("nan"), float("nan")
+        ms = 1e3 / TS_PCR_HZ
+        return float(e["min_dt"]) * ms, float(e["sum_dt"]) / float(e["pcr_pairs"]) * ms, float(e["max_dt"]) * ms
+
+    def tr101290(self):
+        """the first- and second-priority indicators of TR 101 290 that this block can state, as event counts"""
+        return {"sync_byte_error": self.sync_errors, "continuity_count_error": int(self.pids["cc_errors"].sum()), "transport_error": self.transport_errors,
+                "PCR_repetition_error": int(self.pids["pcr_over_40ms"].sum() + self.pids["pcr_over_100ms"].sum()),
+                "PCR_discontinuity_indicator_error": int(self.pids["pcr_over_100ms"].sum())}
+
+
+class TsAnalyser(_Handle):
+    """dvbt_ts_*: a transport-stream analyser on the GPU.  It consumes 188-byte packets -- the layout of the receiver's TAP_TS -- as one stream over any
+    number of push() / push_device() calls and accumulates, in 64-bit integers, the packets, flags and continuity errors of every PID and the timing of its
+    PCRs (include/dvbt_hip.h has the specification).  read() synchronises and returns a TsReading; it does not disturb the accumulation.  A stream cut
+    into calls gives the same bits."""
+    _prefix = "dvbt_ts"
+
+    def __init__(self, max_packets=1 << 19, device=0):
+        self.L = _ts_lib()
+        self.p = TsParams(int(device), int(max_packets))
+        self.h = C.c_void_p()
+        _chk(self.L.dvbt_ts_create(C.byref(self.p), C.byref(self.h)))
+
+    def push(self, packets):
+        """whole packets from the host (bytes or a uint8 array of any shape); continues the stream"""
+        d = np.frombuffer(packets, np.uint8) if isinstance(packets, (bytes, bytearray, memoryview)) else np.ascontiguousarray(packets, dtype=np.uint8).reshape(-1)
+        if len(d) % TS_PACKET:
+            raise DvbtError("whole packets of 188 bytes only")
+        _chk(self.L.dvbt_ts_push(self.h, C.c_void_p(d.ctypes.data) if len(d) else None, len(d) // TS_PACKET))
+
+    def push_device(self, packets_ptr, npackets, stream=None):
+        """a device pointer (int, any byte alignment) to npackets packets: enqueues on `stream` (a hipStream_t as int, None: the default stream)"""
+        _chk(self.L.dvbt_ts_push_device(self.h, C.c_void_p(packets_ptr), npackets, C.c_void_p(stream) if stream else None))
+
+    def read(self):
+        r, n = TsResult(), C.c_size_t()
+        pids = np.zeros(TS_PIDS, TS_PID_DTYPE)
+        _chk(self.L.dvbt_ts_read(self.h, C.byref(r), pids.ctypes.data_as(C.c_void_p), len(pids), C.byref(n)))
+        assert n.value == r.pids_seen
+        return TsReading(r, pids[:n.value].copy())
+
+    def push_rx(self, rx):
+        """the last finished segment of an Rx: the whole packets of its TS tap (the receiver's output buffer) straight from the device"""
+        if rx.report is None:
+            raise DvbtError("the receiver has not run a segment")
+        base = rx.tap_device_ptr(TAP_TS)
+        if not base:
+            raise DvbtError("the receiver keeps no transport-stream tap")
+        n = max(int(rx.report.n_ts_bytes), 0) // TS_PACKET
+        if n <= 0:
+            return
+        self.push_device(base, n)
+        _chk(self.L.dvbt_synchronize(None))        # the receiver's tap may change once this returns
+
+    @classmethod
+    def from_rx(cls, rx, max_packets=1 << 19):
+        """an analyser on the receiver's device that has been pushed its last finished segment (push_rx)"""
+        if rx.report is None:
+            raise DvbtError("the receiver has not run a segment")
+        a = cls(max_packets, rx.p.device)
+        try:
+            a.push_rx(rx)
+        except Exception:
+            a.close()
+            raise
+        return a
+
+
 # ------------------------------------------------------------------ per-block C ABI (one triple per reference block)
 TAG_SYNC_START, TAG_SUPERFRAME_START, TAG_SYMBOL_INDEX = 1, 2, 3
 

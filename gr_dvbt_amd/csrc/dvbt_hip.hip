@@ -35,6 +35,7 @@
 #include "k_sounder.hpp"
 #include "k_constellation.hpp"
 #include "k_tuner.hpp"
+#include "k_ts.hpp"
 
 using namespace dvbt;
 using hip_own::DevMem; using hip_own::PinMem; using hip_own::Stream; using hip_own::Event; using hip_own::CallOrder;
@@ -1910,3 +1911,4 @@ extern "C" int dvbt_debug_acquire(dvbt_rx *h, const void *iq_host, size_t nsampl
 #include "dvbt_sounder.inc"
 #include "dvbt_constellation.inc"
 #include "dvbt_tuner.inc"
+#include "dvbt_ts.inc"

@@ -1319,6 +1319,62 @@ int  dvbt_tuner_run_device(dvbt_tuner *h, const void *raw_device, size_t n_in, v
 int  dvbt_tuner_reset(dvbt_tuner *h);   /* back to first_in, history cleared */
 void dvbt_tuner_destroy(dvbt_tuner *h);
 
+/* ------------------------------------------------------------------ transport stream: the PIDs, their continuity and the timing of their PCRs
+ * A measurement block (csrc/k_ts.hpp; tests/tsref.py is this text in Python): it consumes a stream of 188-byte packets -- the layout of DVBT_TAP_TS --
+ * changes nothing and accumulates on the device.  Every accumulated quantity is a 64-bit INTEGER.  The checks are those of ETSI TR 101 290's first two
+ * priority tables that need no section parsing.  Packets are numbered i = 0, 1, ... from create / reset, across calls; a packet's bytes are b0 .. b187.
+ *   1 Sync        b0 != 0x47: count `sync_errors`.  The packet adds nothing else and belongs to no PID.
+ *   2 Header      tei = b1 >> 7, pusi = (b1 >> 6) & 1, pid = ((b1 & 0x1f) << 8) | b2, tsc = b3 >> 6, afc = (b3 >> 4) & 3, cc = b3 & 15, pay = afc & 1,
+ *                 af = afc >> 1.
+ *   3 Transport   tei set: count `transport_errors` and the PID's `tei`.  The packet adds nothing else and is not a MEMBER (its other fields are unreliable).
+ *   4 Members     every other packet is a member of its PID's sequence.  Per PID: `packets`, `pusi`, `scrambled` (tsc != 0), `payload` (pay), `adaptation`
+ *                 (af), and `first` / `last`, the smallest and the largest i of a member.
+ *   5 Reserved    afc == 0: also count `afc_reserved` (a total).
+ *   6 Adaptation  only if af is set.  afl = b4.  afl is BAD if afl > 183 - pay: count `af_length_errors` (a total) and read nothing more of the field.
+ *                 Otherwise, if afl >= 1: di = b5 >> 7, rai = (b5 >> 6) & 1, pf = (b5 >> 4) & 1.  di counts `discontinuity`, rai `random_access`.
+ *                 pf set and afl < 7: count `af_length_errors` and take no PCR.  pf set and afl >= 7: base = b6 << 25 | b7 << 17 | b8 << 9 | b9 << 1 |
+ *                 b10 >> 7, ext = (b10 & 1) << 8 | b11, pcr = 300 base + ext; count the PID's `pcr`.  Without a readable field di = rai = pf = 0.
+ *   7 Continuity  not evaluated for PID 0x1FFF.  For a member i, j is the previous member of the same PID and k the one before j.
+ *                   same(i) = pay_i && pay_j && cc_i == cc_j && !di_i; 0 without a j.  (same(j) needs k and nothing older.)
+ *                   no j, or di_i set:                    nothing
+ *                   else cc_i == ((cc_j + pay_i) & 15):   in order
+ *                   else same(i) && !same(j):             count `duplicates` (the one repeat the standard allows)
+ *                   else:                                 count `cc_errors` (a third copy counts here)
+ *   8 PCR pairs   per PID, over its members that carry a PCR: a the previous such member, b the current one (no a: no pair, nothing is counted).
+ *                   di_b:                                 count `pcr_discontinuity_signalled`; the pair ends there
+ *                   else dt = (pcr_b - pcr_a) mod (2^33 300), dp = i_b - i_a
+ *                   dt > 2,700,000 (100 ms):              count `pcr_over_100ms`; the pair adds nothing else (a backwards jump lands here)
+ *                   else:                                 count `pcr_pairs`, sum_dt += dt, sum_dp += dp, update min_dt, max_dt, max_dp; dt > 1,080,000
+ *                                                         (40 ms): count `pcr_over_40ms`
+ *   9 Totals      packets_pushed, sync_errors, transport_errors, afc_reserved, af_length_errors, pids_seen (the PIDs with packets + tei > 0).
+ * `first` and `min_dt` are -1 while unset; max_dt and max_dp are 0.  The transport stream's rate follows on the host from a PCR PID's sums:
+ * sum_dp 188 8 27e6 / sum_dt bits per second.
+ * The continuity rule and the PCR pairs relate a packet to the previous packet of its PID wherever that was -- another tile, batch or call: the handle keeps
+ * per PID (cc, pay, same) of its last member and its last PCR with index.  A stream cut into calls of any sizes, through either entry, gives the same bits.
+ * The packet pointer may have ANY byte alignment.  A null pointer with npackets > 0 is DVBT_ERR_INVALID; npackets = 0 is accepted and adds nothing.  A call
+ * is worked off in batches of min(max_packets, 2^19) packets inside the call; the scratch is sized for one batch, once, at create.  max_packets 1 .. 2^24.
+ * More than 2^40 packets per stream is DVBT_ERR_CAPACITY.  dvbt_ts_read synchronises and does not disturb the accumulation: it returns the entries of the
+ * PIDs seen, ascending by pid, *n_pids of them (pids may be NULL to ask for the totals and the count alone; a cap below the count is DVBT_ERR_CAPACITY).
+ * dvbt_ts_push_device only enqueues on `stream`; calls on different streams are ordered by the handle (an event).  One thread per handle.  Every parameter
+ * is checked before the device is asked for: a bad struct is DVBT_ERR_INVALID everywhere, a good one DVBT_ERR_NO_DEVICE without a GPU -- there is no CPU
+ * path.  A refused call leaves the stream where it was.
+ * Deliberately not here: (1) section parsing -- PAT, PMT, CRC, the indicators 1.3, 1.5, 2.2; (2) PCR accuracy (jitter against a fit); (3) PTS; (4) whether a
+ * duplicate repeats its packet byte for byte; (5) a GNU Radio shell; (6) sync search on the device (the stream starts on a packet). */
+enum { DVBT_TS_PACKET = 188, DVBT_TS_PIDS = 8192, DVBT_TS_TILE = 1024 /* packets per workgroup tile: where the device's work is cut */ };
+typedef struct { int device; int max_packets; } dvbt_ts_params;
+typedef struct {
+  long long pid, packets, pusi, scrambled, payload, adaptation, discontinuity, random_access, pcr, tei, duplicates, cc_errors, first, last,
+            pcr_pairs, pcr_discontinuity_signalled, pcr_over_100ms, pcr_over_40ms, sum_dt, sum_dp, min_dt, max_dt, max_dp;
+} dvbt_ts_pid;
+typedef struct { long long packets_pushed, sync_errors, transport_errors, afc_reserved, af_length_errors, pids_seen; } dvbt_ts_result;
+typedef struct dvbt_ts dvbt_ts;
+int  dvbt_ts_create(const dvbt_ts_params *p, dvbt_ts **out);
+int  dvbt_ts_push(dvbt_ts *h, const void *packets_host, size_t npackets);
+int  dvbt_ts_push_device(dvbt_ts *h, const void *packets_dev, size_t npackets, void *stream);
+int  dvbt_ts_read(dvbt_ts *h, dvbt_ts_result *result, dvbt_ts_pid *pids /* may be NULL */, size_t cap, size_t *n_pids /* may be NULL */);
+int  dvbt_ts_reset(dvbt_ts *h);   /* back to the state after create */
+void dvbt_ts_destroy(dvbt_ts *h);
+
 #ifdef __cplusplus
 }
 #endif
