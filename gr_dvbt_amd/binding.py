@@ -1700,6 +1700,83 @@ class TsAnalyser(_Handle):
         return a
 
 
+KEEP_PILOTS, KEEP_TPS = 1, 2      # CfrParams.keep: DVBT_CFR_KEEP_*
+CFR_MAX_ITERATIONS = 8
+CFR_FIELDS = ("symbols", "symbols_clipped", "symbols_nonfinite", "samples_over", "peak_power_in")
+
+
+class CfrParams(C.Structure):
+    _fields_ = [("transmission_mode", C.c_int), ("guard_interval", C.c_int), ("threshold", C.c_float), ("iterations", C.c_int),
+                ("oversampling", C.c_int), ("keep", C.c_int), ("first_symbol", C.c_int64), ("device", C.c_int)]
+
+
+class CfrResult(C.Structure):
+    _fields_ = [(f, C.c_longlong) for f in CFR_FIELDS[:4]] + [("peak_power_in", C.c_float)]
+
+
+@_typed_once
+def _cfr_lib(L):
+    L.dvbt_cfr_create.argtypes = [C.POINTER(CfrParams), C.POINTER(C.c_void_p)]
+    L.dvbt_cfr_run.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+    L.dvbt_cfr_run_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+    L.dvbt_cfr_read.argtypes = [C.c_void_p, C.POINTER(CfrResult)]
+    L.dvbt_cfr_reset.argtypes = [C.c_void_p]
+    L.dvbt_cfr_destroy.argtypes = [C.c_void_p]
+
+
+class CfrReading:
+    """What Cfr.read() returns: dvbt_cfr_result's four counters as ints and peak_power_in as a float.  Two readings compare equal field by field."""
+
+    def __init__(self, r):
+        for f in CFR_FIELDS[:4]:
+            setattr(self, f, int(r[f] if isinstance(r, dict) else getattr(r, f)))
+        self.peak_power_in = float(r["peak_power_in"] if isinstance(r, dict) else r.peak_power_in)
+
+    def as_tuple(self):
+        return tuple(getattr(self, f) for f in CFR_FIELDS)
+
+    def __eq__(self, other):
+        return isinstance(other, CfrReading) and self.as_tuple() == other.as_tuple()
+
+    def __repr__(self):
+        return "CfrReading(" + ", ".join(f"{f}={getattr(self, f)!r}" for f in CFR_FIELDS) + ")"
+
+    def peak_db(self, ref_power):
+        """the highest peak seen in a first iteration, in dB over the mean power ref_power (Channel.power)"""
+        return float(_db(self.peak_power_in, ref_power))
+
+
+class Cfr(_SampleBlock):
+    """dvbt_cfr_*: crest-factor reduction of DVB-T baseband on the GPU by iterative clipping and filtering, one OFDM symbol at a time (include/dvbt_hip.h has
+    the specification, tests/cfrref.py is it in numpy).  Samples above `threshold` in magnitude -- looked for at `oversampling` times the sample rate -- are
+    clipped, and the clipping error is kept to the occupied carriers and, by default, off the pilots and the TPS carriers; `iterations` times.  The stream is
+    whole symbols of guard + useful part, starting at the frame's symbol `first_symbol` (what matters is the scattered-pilot phase, first_symbol mod 4), over
+    any number of run() / run_device() calls; the concatenated outputs are bit for bit those of one call.  read() synchronises and returns a CfrReading.
+    The mean power drops by about 1 % at 7 dB; the block does not make up for it."""
+    _prefix = "dvbt_cfr"
+
+    def __init__(self, mode, guard, threshold, iterations=4, oversampling=2, keep=KEEP_PILOTS | KEEP_TPS, first_symbol=0, device=0):
+        self.L = _cfr_lib()
+        self.p = CfrParams(int(mode), int(guard), float(threshold), int(iterations), int(oversampling), int(keep), int(first_symbol), int(device))
+        self.h = C.c_void_p()
+        _chk(self.L.dvbt_cfr_create(C.byref(self.p), C.byref(self.h)))
+
+    @staticmethod
+    def threshold_for(papr_db, ref_power):
+        """the threshold that stands papr_db above the mean power ref_power (Channel.power)"""
+        return float(np.sqrt(ref_power * 10.0 ** (papr_db / 10.0)))
+
+    def run_device(self, in_ptr, nsamples, out_ptr, stream=None):
+        """device pointers (ints) to nsamples complex64 each (whole symbols), the same buffer (in place) or not overlapping: enqueues on `stream` (a
+        hipStream_t as int, None: the default stream)"""
+        super().run_device(in_ptr, nsamples, out_ptr, stream)
+
+    def read(self):
+        r = CfrResult()
+        _chk(self.L.dvbt_cfr_read(self.h, C.byref(r)))
+        return CfrReading(r)
+
+
 # ------------------------------------------------------------------ per-block C ABI (one triple per reference block)
 TAG_SYNC_START, TAG_SUPERFRAME_START, TAG_SYMBOL_INDEX = 1, 2, 3
 

@@ -36,6 +36,7 @@
 #include "k_constellation.hpp"
 #include "k_tuner.hpp"
 #include "k_ts.hpp"
+#include "k_cfr.hpp"
 
 using namespace dvbt;
 using hip_own::DevMem; using hip_own::PinMem; using hip_own::Stream; using hip_own::Event; using hip_own::CallOrder;
@@ -1912,3 +1913,4 @@ extern "C" int dvbt_debug_acquire(dvbt_rx *h, const void *iq_host, size_t nsampl
 #include "dvbt_constellation.inc"
 #include "dvbt_tuner.inc"
 #include "dvbt_ts.inc"
+#include "dvbt_cfr.inc"
