@@ -1,4 +1,4 @@
-"""gr_dvbt_amd -- host-side Python binding of libdvbt_hip.so (the MI355X DVB-T RX hot path, the modulator, the channel block, the sample-clock offset block, the fading block, the RF front-end block, the spectrum analyser, the channel sounder, the constellation analyser, the tuner, the transport-stream analyser and the crest-factor reduction block).
+"""gr_dvbt_amd -- host-side Python binding of libdvbt_hip.so (the MI355X DVB-T RX hot path, the modulator, the channel block, the sample-clock offset block, the fading block, the RF front-end block, the spectrum analyser, the channel sounder, the constellation analyser, the tuner, the transport-stream analyser, the crest-factor reduction block and the signal scanner).
 
 Thin ctypes layer over the C ABI declared in include/dvbt_hip.h.  There is no CPU
 fallback: importing works anywhere, but every compute entry point raises unless the HIP
@@ -13,6 +13,7 @@ from .binding import (  # noqa: F401
     ConstellationParams, ConstellationResult, ConstellationReading, Constellation, constellation_grid, CONSTELLATION_GRID, CONSTELLATION_STEP, POINT_DTYPE, CARRIER_DTYPE,
     TsParams, TsResult, TsReading, TsAnalyser, ts_align, TS_PID_DTYPE, TS_PID_FIELDS, TS_PACKET, TS_PIDS, TS_TILE, TS_NULL_PID,
     CfrParams, CfrResult, CfrReading, Cfr, KEEP_PILOTS, KEEP_TPS, CFR_MAX_ITERATIONS, CFR_FIELDS,
+    ScanParams, ScanResult, ScanReading, Scanner, scan_evaluate, scan_dims, SCAN_GROUP, SCAN_MIN_SAMPLES, SCAN_HYPOTHESES,
     spectrum_window, SPECTRUM_HIST_BINS, get_dims, device_count, Block, Tag, Sideband, BLOCK_PARAMS, TX_BLOCKS,
     TAG_SYNC_START, TAG_SUPERFRAME_START, TAG_SYMBOL_INDEX,
     QPSK, QAM16, QAM64, NH, C1_2, C2_3, C3_4, C5_6, C7_8, T2k, T8k, G1_32, G1_16, G1_8, G1_4,

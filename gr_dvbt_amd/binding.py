@@ -1777,6 +1777,138 @@ class Cfr(_SampleBlock):
         return CfrReading(r)
 
 
+SCAN_HYPOTHESES = 8
+SCAN_GROUP = 16
+SCAN_MIN_SAMPLES = 8 * 10240 + 8192
+
+
+class ScanParams(C.Structure):
+    _fields_ = [("device", C.c_int), ("rho_min", C.c_double), ("ratio_min", C.c_double)]
+
+
+class ScanResult(C.Structure):
+    _fields_ = [("detected", C.c_int), ("mode", C.c_int), ("guard", C.c_int), ("symbol_start", C.c_int * 8),
+                ("samples_pushed", C.c_longlong), ("nonfinite", C.c_longlong), ("symbols", C.c_longlong * 8),
+                ("rho", C.c_double * 8), ("cfo", C.c_double * 8)]
+
+
+_PD = C.POINTER(C.c_double)
+
+
+@_typed_once
+def _scan_lib(L):
+    L.dvbt_scan_create.argtypes = [C.POINTER(ScanParams), C.POINTER(C.c_void_p)]
+    L.dvbt_scan_push.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+    L.dvbt_scan_push_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+    L.dvbt_scan_read.argtypes = [C.c_void_p, C.POINTER(ScanResult)]
+    L.dvbt_scan_accumulators.argtypes = [C.c_void_p, C.c_int, _PD, _PD, C.c_int]
+    L.dvbt_scan_evaluate.argtypes = [C.POINTER(ScanParams), C.POINTER(C.c_int64), C.POINTER(_PD), C.POINTER(_PD), C.c_int64, C.c_int64, C.POINTER(ScanResult)]
+    L.dvbt_scan_reset.argtypes = [C.c_void_p]
+    L.dvbt_scan_destroy.argtypes = [C.c_void_p]
+
+
+def scan_dims(h):
+    """(N, G, S) of hypothesis h = 4 mode + guard: the useful part, the guard interval and the symbol, in samples"""
+    N = 8192 if h >> 2 else 2048
+    G = N >> (5 - (h & 3))
+    return N, G, N + G
+
+
+class ScanReading:
+    """What Scanner.read() and scan_evaluate() return: the fields of dvbt_scan_result.  `detected` says whether `mode` and `guard` (T2k / T8k, G1_32 ..
+    G1_4; -1 otherwise) are to be believed; rho, symbol_start, cfo and symbols hold all eight hypotheses (h = 4 mode + guard) either way."""
+
+    def __init__(self, r, device=0):
+        self.detected, self.mode, self.guard = bool(r.detected), int(r.mode), int(r.guard)
+        self.samples_pushed, self.nonfinite = int(r.samples_pushed), int(r.nonfinite)
+        self.symbols = [int(v) for v in r.symbols]
+        self.symbol_start = [int(v) for v in r.symbol_start]
+        self.rho, self.cfo = [float(v) for v in r.rho], [float(v) for v in r.cfo]
+        self.device = int(device)
+
+    @property
+    def hypothesis(self):
+        """4 mode + guard of the detected signal, None if nothing was detected"""
+        return 4 * self.mode + self.guard if self.detected else None
+
+    def rx_stream(self, **kw):
+        """an RxStream for the detected mode and guard; constellation, hierarchy and code rate come from the stream's TPS word (AUTO) unless given"""
+        if not self.detected:
+            raise DvbtError("the scanner detected no DVB-T signal: there is no mode and guard to build a receiver from")
+        kw.setdefault("device", self.device)
+        return RxStream(kw.pop("constellation", AUTO), kw.pop("code_rate", AUTO), self.mode, guard=self.guard, hierarchy=kw.pop("hierarchy", AUTO), **kw)
+
+    def __repr__(self):
+        return (f"ScanReading(detected={self.detected}, mode={self.mode}, guard={self.guard}, samples_pushed={self.samples_pushed}, "
+                f"nonfinite={self.nonfinite}, rho={[round(v, 4) for v in self.rho]})")
+
+
+def scan_evaluate(symbols, A, E, samples, nonfinite=0, rho_min=0, ratio_min=0):
+    """dvbt_scan_evaluate: the scanner's verdict from its sums, on the host (needs no GPU).  symbols[8]; A[8] complex and E[8] real, S bins each (None
+    where symbols[h] is 0)."""
+    L = _scan_lib()
+    keep, Ap, Ep = [], (_PD * 8)(), (_PD * 8)()
+    for h in range(SCAN_HYPOTHESES):
+        if A[h] is None or E[h] is None:
+            continue
+        S = scan_dims(h)[2]
+        a, e = np.ascontiguousarray(A[h], dtype=np.complex128).reshape(-1), np.ascontiguousarray(E[h], dtype=np.float64).reshape(-1)
+        if len(a) != S or len(e) != S:
+            raise DvbtError(f"hypothesis {h} has {S} bins")
+        keep += [a, e]
+        Ap[h], Ep[h] = a.ctypes.data_as(_PD), e.ctypes.data_as(_PD)
+    r = ScanResult()
+    _chk(L.dvbt_scan_evaluate(C.byref(ScanParams(0, float(rho_min), float(ratio_min))), (C.c_int64 * 8)(*[int(v) for v in symbols]), Ap, Ep,
+                              int(samples), int(nonfinite), C.byref(r)))
+    return ScanReading(r)
+
+
+class Scanner(_Handle):
+    """dvbt_scan_*: what an unknown DVB-T capture is -- FFT size, guard interval, where a symbol starts and the fractional carrier offset -- from the
+    cyclic-prefix correlation at the lags 2048 and 8192, folded at the eight candidate symbol lengths on the GPU (include/dvbt_hip.h has the specification,
+    tests/scanref.py is it in numpy).  It consumes complex64 baseband at the elementary rate as one stream over any number of push() / push_device() calls of
+    any size and changes nothing; read() synchronises, evaluates on the host and does not disturb the accumulation.  SCAN_MIN_SAMPLES is the least a verdict
+    takes; rho_min and ratio_min (0: the defaults 0.1 and 1.5) are the floor of the winner's correlation and of its lead over the runner-up."""
+    _prefix = "dvbt_scan"
+
+    def __init__(self, rho_min=0, ratio_min=0, device=0):
+        self.L = _scan_lib()
+        self.p = ScanParams(int(device), float(rho_min), float(ratio_min))
+        self.h = C.c_void_p()
+        _chk(self.L.dvbt_scan_create(C.byref(self.p), C.byref(self.h)))
+
+    def push(self, iq):
+        """complex64 samples from the host; continues the stream"""
+        iq = np.ascontiguousarray(iq, dtype=np.complex64).reshape(-1)
+        _chk(self.L.dvbt_scan_push(self.h, iq.ctypes.data_as(C.c_void_p), len(iq)))
+
+    def push_device(self, ptr, nsamples, stream=None):
+        """a device pointer (int) to nsamples complex64: enqueues on `stream` (a hipStream_t as int, None: the default stream)"""
+        _chk(self.L.dvbt_scan_push_device(self.h, C.c_void_p(ptr), nsamples, C.c_void_p(stream) if stream else None))
+
+    def read(self):
+        r = ScanResult()
+        _chk(self.L.dvbt_scan_read(self.h, C.byref(r)))
+        return ScanReading(r, self.p.device)
+
+    def accumulators(self, h):
+        """(A complex128 [S], E float64 [S]) of hypothesis h as they stand: the folded sums read() evaluates"""
+        S = scan_dims(h)[2] if 0 <= h < SCAN_HYPOTHESES else 1
+        a, e = np.zeros(S, np.complex128), np.zeros(S, np.float64)
+        _chk(self.L.dvbt_scan_accumulators(self.h, int(h), a.ctypes.data_as(_PD), e.ctypes.data_as(_PD), S))
+        return a, e
+
+    @classmethod
+    def detect(cls, iq, **kw):
+        """one push and one read of a whole capture"""
+        s = cls(**kw)
+        try:
+            s.push(iq)
+            return s.read()
+        finally:
+            s.close()
+
+
 # ------------------------------------------------------------------ per-block C ABI (one triple per reference block)
 TAG_SYNC_START, TAG_SUPERFRAME_START, TAG_SYMBOL_INDEX = 1, 2, 3
 

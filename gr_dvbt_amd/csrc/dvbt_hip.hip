@@ -10,6 +10,8 @@
 #include <map>
 #include <deque>
 #include <algorithm>
+#include <cmath>
+#include <limits>
 #include <memory>
 #include "../../include/dvbt_hip.h"
 #include "hip_own.hpp"
@@ -37,6 +39,7 @@
 #include "k_tuner.hpp"
 #include "k_ts.hpp"
 #include "k_cfr.hpp"
+#include "k_scan.hpp"
 
 using namespace dvbt;
 using hip_own::DevMem; using hip_own::PinMem; using hip_own::Stream; using hip_own::Event; using hip_own::CallOrder;
@@ -1914,3 +1917,4 @@ extern "C" int dvbt_debug_acquire(dvbt_rx *h, const void *iq_host, size_t nsampl
 #include "dvbt_tuner.inc"
 #include "dvbt_ts.inc"
 #include "dvbt_cfr.inc"
+#include "dvbt_scan.inc"

@@ -1428,6 +1428,64 @@ int  dvbt_cfr_read(dvbt_cfr *h, dvbt_cfr_result *result);
 int  dvbt_cfr_reset(dvbt_cfr *h);   /* back to first_symbol, accumulators zeroed */
 void dvbt_cfr_destroy(dvbt_cfr *h);
 
+/* ------------------------------------------------------------------ scan: FFT size, guard interval, symbol timing and fractional carrier offset of an unknown signal
+ * A measurement block (csrc/k_scan.hpp): it consumes complex64 baseband at the elementary rate as a stream, changes nothing and accumulates on the device, in
+ * one pass, the cyclic-prefix correlation at the lags 2048 and 8192 folded at the eight symbol lengths a DVB-T signal can have.  dvbt_rx_stream_* reads
+ * constellation, hierarchy and code rate from the TPS word (DVBT_AUTO) but must be given mode and guard: this block finds them.  tests/scanref.py is this
+ * text in numpy.
+ *   Hypotheses h = 0 .. 7, mode = h >> 2, guard = h & 3: N = 2048 or 8192, G = N / 32, N / 16, N / 8 or N / 4, S = N + G.
+ *   Positions  n = 0 is the first sample pushed since create or reset.
+ *   Terms      for a = x[n], b = x[n + N], in float32, every product and every sum rounded on its own (no FMA):
+ *                p.re = (a.re b.re) + (a.im b.im)      p.im = (a.im b.re) - (a.re b.im)      e = ((a.re a.re) + (a.im a.im)) + ((b.re b.re) + (b.im b.im))
+ *   Symbols    symbol j of hypothesis h is the positions [j S, j S + S), its bin m = n - j S.  A symbol is folded once it is complete, i.e. when
+ *              (j + 1) S + N <= samples pushed: J_h = (samples - N) / S symbols (0 below N), the same count in every bin of a hypothesis.
+ *   Sums       a group is DVBT_SCAN_GROUP = 16 consecutive symbols [16 g, 16 g + 16) of a hypothesis.  Per bin, the terms of a group are added in float32 in
+ *              ascending j, starting from +0 (acc = acc + term); closed groups are added to double accumulators in ascending g; the open group is kept
+ *              as it stands and dvbt_scan_read / dvbt_scan_accumulators add it, converted to double, last.  This gives A_h[m] (complex) and E_h[m], m < S.
+ *   Evaluation in double on the host, per hypothesis, every operation rounded on its own, sums running from 0.0 in ascending index:
+ *                mean   = (sum_m A[m]) / S, re and im each;   A'[m] = A[m] - mean.  (What correlates at every lag -- DC, a CW spur, the pilots' comb --
+ *                         reads rho ~ 0.9 on all eight hypotheses without this and ~ 0.02 with it.)
+ *                C[0]   = sum_{k < G} A'[k];   C[m + 1] = (C[m] - A'[m]) + A'[(m + G) mod S].   Phi[m] likewise from E, the mean not removed.
+ *                m*     = the smallest m that maximises q[m] = (C.re C.re) + (C.im C.im)  (found with >, so a NaN never wins)
+ *                rho    = sqrt(q[m*]) / (Phi[m*] / 2); 0 when J_h = 0 or Phi[m*] <= 0; NaN when sum_m A[m] or sum_m E[m] is not finite
+ *                symbol_start = m*: the stream position, modulo S, of the first sample of a guard interval
+ *                cfo    = -atan2(C.im, C.re) / (2 pi) at m*, in carrier spacings, in (-0.5, 0.5]  (-0.5 is returned as 0.5)
+ *   Verdict    b = the hypothesis of the largest rho, r = the largest of the others (the smallest h among equals, both).  detected = 1 iff every J_h >= 8
+ *              (i.e. samples >= DVBT_SCAN_MIN_SAMPLES), nonfinite == 0 and every rho finite, rho[b] >= rho_min, and rho[b] >= ratio_min rho[r].  mode and
+ *              guard are b's when detected, else -1; symbols (J_h), rho, symbol_start and cfo are filled for all eight either way.
+ *              rho_min = 0 means 0.1 and ratio_min = 0 means 1.5 (DESIGN.md 4h7 has the figures behind them); otherwise 0 < rho_min <= 1, 1 <= ratio_min <= 1e6.
+ * A stream cut into calls of any sizes (1 and 0 included, 8-byte aligned only) gives the accumulators of one call, bit for bit, through either entry, on any
+ * device; no atomics in floating point.  Non-finite samples (either part inf or NaN) are counted, each once, by an integer atomic.  The handle carries the up to
+ * 10240 + 8192 - 1 newest samples in two buffers written alternately; which symbols a call completes is host arithmetic on the sample count, so a device push
+ * never waits.  dvbt_scan_push_device only enqueues on `stream`; calls on different streams are ordered by the handle (an event).  dvbt_scan_read synchronises,
+ * evaluates through dvbt_scan_evaluate, and does not disturb the accumulation.  n <= 2^31 per call, 2^56 per stream.  One thread per handle.  Every parameter
+ * is checked before the device is asked for: a bad struct is DVBT_ERR_INVALID everywhere, a good one DVBT_ERR_NO_DEVICE without a GPU -- there is no CPU path,
+ * except dvbt_scan_evaluate, which is host arithmetic.  A refused call leaves the stream where it was.
+ *   dvbt_scan_accumulators  hypothesis hyp's sums as dvbt_scan_read sees them: A as S pairs (re, im), E as S doubles; cap = the bins the buffers hold, >= S.
+ *   dvbt_scan_evaluate      the evaluation alone.  symbols[h] = J_h >= 0; A[h] (S pairs) and E[h] (S doubles) may be NULL where symbols[h] = 0.  p->device is
+ *                           checked like the rest and not used.
+ * Deliberately not here: (1) the integer part of the carrier offset -- the receiver's continual-pilot search finds it; (2) a search over 6 and 7 MHz
+ * channels -- the caller's tuner sets the elementary rate; (3) any change to dvbt_rx_stream_*: the detected pair goes into its parameters. */
+enum { DVBT_SCAN_HYPOTHESES = 8, DVBT_SCAN_GROUP = 16, DVBT_SCAN_MIN_SAMPLES = 8 * 10240 + 8192 };
+typedef struct { int device; double rho_min, ratio_min; } dvbt_scan_params;
+typedef struct {
+  int detected, mode, guard;                     /* mode: dvbt_transmission_mode_t, guard: dvbt_guard_interval_t, -1 unless detected */
+  int symbol_start[8];
+  long long samples_pushed, nonfinite;
+  long long symbols[8];
+  double rho[8], cfo[8];
+} dvbt_scan_result;
+typedef struct dvbt_scan dvbt_scan;
+int  dvbt_scan_create(const dvbt_scan_params *p, dvbt_scan **out);
+int  dvbt_scan_push(dvbt_scan *h, const void *iq_host, size_t n);
+int  dvbt_scan_push_device(dvbt_scan *h, const void *iq_device, size_t n, void *stream);
+int  dvbt_scan_read(dvbt_scan *h, dvbt_scan_result *result);
+int  dvbt_scan_accumulators(dvbt_scan *h, int hyp, double *A_re_im /* 2 S */, double *E /* S */, int cap);
+int  dvbt_scan_evaluate(const dvbt_scan_params *p, const int64_t symbols[8], const double *const A[8], const double *const E[8], int64_t samples,
+                        int64_t nonfinite, dvbt_scan_result *result);
+int  dvbt_scan_reset(dvbt_scan *h);   /* back to the state after create */
+void dvbt_scan_destroy(dvbt_scan *h);
+
 #ifdef __cplusplus
 }
 #endif
